@@ -10,9 +10,17 @@ BCE strong + BCE weak -> backward -> (RCCL all-reduce of the flat gradient arena
 BASELINE.json configs[2] ("main_baseline.py full CRNN train step on SYN, batch 256 per GPU"), the
 configuration the metric is quoted on; data parallel = weak scaling (256 clips per GPU).
 
-Prints ONE JSON line on rank 0 with `roofline` (the kernel with the largest total time of the step, every
-launch HIP-event timed inside the timed region), `roofline_step` (whole-step fraction by SURVEY.md 8(d)'s formula)
-and `cpu_baseline` (the CPU oracle timed on this box's host cores on a bounded sample, before the GPU is touched).
+Prints ONE JSON line on rank 0 with the headline (`value` clips/s, `ms_per_step`) and `roofline_step` (whole-step
+fraction by SURVEY.md 8(d)'s formula).  A plain run does only what that line needs: set up, warm up, time the
+--steps steps, print.  --full adds the measurements that cost runs or timed-region events of their own: `roofline`
+(the kernel with the largest total time of the step, every launch HIP-event timed inside the timed region, with the
+per-kernel table on stderr), `cpu_baseline` (the CPU oracle timed on the host cores on a bounded sample, before the
+GPU is touched) and, with N > 1 ranks, the `data_parallel` exchange figures.
+
+--dump-outputs DIR writes what the last timed step returned (the loss terms of the train step, or the tagger's strong /
+weak outputs for --mode cnn) and the parameters and buffers of the trained modules after it, as DIR/<name>.npy
+(float32, float64 where the tensor is float64; at most 64 MB, larger sets as a fixed seeded sample).  Inputs and
+weights are seeded: two runs with the same arguments start from the same data.
 """
 import argparse
 import json
@@ -193,6 +201,28 @@ def kernel_roofline(name, launches, total_ms, flops_total, bytes_total):
     return r
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT_BYTES):
+    """arrays: {name: tensor}.  Writes path/<name>.npy in float32 (float64 kept); if the set exceeds `limit` bytes, every
+    array is thinned to the same fraction at fixed seeded positions (flattened, index order kept)."""
+    os.makedirs(path, exist_ok=True)
+    host = {}
+    for k, t in arrays.items():
+        t = t.detach()
+        host[k] = t.double().cpu().numpy() if t.dtype == torch.float64 else t.float().cpu().numpy()
+    total = sum(a.nbytes for a in host.values())
+    frac = 1.0 if total <= limit else limit / total * 0.99
+    for i, (k, a) in enumerate(sorted(host.items())):
+        if frac < 1.0:
+            n = a.size
+            keep = max(1, int(n * frac))
+            a = a.reshape(-1)[np.sort(np.random.default_rng(1000 + i).choice(n, keep, replace=False))]
+        np.save(os.path.join(path, k + ".npy"), a)
+    return len(host), min(total, limit)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -212,10 +242,16 @@ def main():
     ap.add_argument("--graph", action="store_true",
                     help="--mode crnn: capture the step in a HIP graph (SEDTrainer.capture_step) and time replays; the "
                          "per-launch kernel timer is off (events are not captured).  For the reference's batch: --batch 24")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the CPU oracle baseline, the per-launch kernel "
+                         "timer (roofline object and per-kernel table) and, with N > 1 ranks, the gradient-exchange figures")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (returned loss terms / outputs and the "
+                         "trained parameters and buffers) as DIR/<name>.npy, float32 or float64, at most 64 MB")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU oracle baseline")
     ap.add_argument("--no-pipeline", action="store_true",
                     help="mel transform inside the step instead of one step ahead on the feature stream")
-    ap.add_argument("--no-kernel-timer", action="store_true")
+    ap.add_argument("--no-kernel-timer", action="store_true", help="--full without the per-launch kernel timer")
     ap.add_argument("--host-waves", action="store_true",
                     help="diagnostic: waveform batches in pinned HOST memory, uploaded one step ahead on the trainer's copy "
                          "stream (PCIe-inclusive rate; the headline keeps its inputs resident in HBM)")
@@ -249,7 +285,7 @@ def main():
     # CPU baseline first, on rank 0 at N = 1 only, BEFORE this process initialises the GPU: its process pool starts
     # fresh interpreters, which a GPU-initialised parent must not do on the GPU boxes
     cpu = None
-    if not args.no_cpu_baseline and world == 1 and args.mode == "crnn":
+    if args.full and not args.no_cpu_baseline and world == 1 and args.mode == "crnn":
         try:
             ncpu = len(os.sched_getaffinity(0))
         except AttributeError:
@@ -302,6 +338,7 @@ def main():
     T = fe.num_frames(n)
     Tp = T // 4
     tr = None
+    trained = {}     # modules whose parameters / buffers the timed steps update (--dump-outputs)
     if args.mode == "cnn":
         # BASELINE configs[1]: the reference's CNN-only tagger (CRNN_pred, models/CRNN_GRL.py:206-290) in eval mode:
         # waveform -> mel/dB -> 7 conv blocks -> sigmoid features + class-softmax attention pooling
@@ -330,6 +367,11 @@ def main():
             optimizer = FlatSGD([crnn, pred], lr=1e-3, momentum=0.9, weight_decay=1e-4, nesterov=True)
             extra = dict(domain_loss=ConditionalDomainAdversarialLoss(disc),
                          optimizer_d=FlatSGD([disc], lr=1e-4, momentum=0.9, weight_decay=1e-4, nesterov=True))
+        trained = {"crnn": crnn, "pred": pred}
+        if args.mode == "mt":
+            trained.update(ema_crnn=ema_c, ema_pred=ema_p)
+        elif args.mode == "ada":
+            trained["disc"] = disc
         tr = SEDTrainer(crnn, pred, optimizer=optimizer, frontend=fe, seed=2023, **extra)
         tr.broadcast_parameters()
         y = strong_labels(ev, Tp, args.sr, mcfg.hop_size, 4, dev)
@@ -370,9 +412,9 @@ def main():
         else:
             batches = [(b[0].cpu().pin_memory(), b[1], b[2].cpu().pin_memory(), b[3]) for b in batches]
     if tr is not None:
-        tr.arena.timing = world > 1 or tr.arena.exchange_single_rank
+        tr.arena.timing = args.full and (world > 1 or tr.arena.exchange_single_rank)
     log(f"data ready: B={B} n={n} T={T} Tp={Tp}")
-    use_timer = not args.no_kernel_timer and rank == 0 and not args.graph
+    use_timer = args.full and not args.no_kernel_timer and rank == 0 and not args.graph
     if args.graph:
         if args.mode != "crnn" or world != 1:
             raise SystemExit("--graph covers --mode crnn on one rank")
@@ -421,7 +463,7 @@ def main():
         torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(tmax)
     dp = None
-    if tr is not None and (world > 1 or tr.arena.exchange_single_rank):
+    if args.full and tr is not None and (world > 1 or tr.arena.exchange_single_rank):
         # what the gradient exchange cost: (a) how long the step's stream actually WAITED in GradArena.finish() for the
         # early + tail all-reduces (events around the waits, inside the timed region: the exposed part of the exchange);
         # (b) the two all-reduces alone, back to back on an otherwise idle GPU, after the timed region (every rank takes
@@ -458,6 +500,18 @@ def main():
         if torch.distributed.is_initialized():
             torch.distributed.destroy_process_group()
         return
+    if args.dump_outputs:
+        if args.mode == "cnn":
+            arrays = {"strong": out[0], "weak": out[1]}
+        else:
+            arrays = {"out_" + k: v if torch.is_tensor(v) else torch.tensor(v, dtype=torch.float64)
+                      for k, v in out.items() if torch.is_tensor(v) or isinstance(v, float)}
+        for mname, m in trained.items():
+            for k, v in m.state_dict().items():
+                if torch.is_tensor(v) and v.numel():
+                    arrays[f"{mname}.{k}"] = v
+        nfiles, nbytes = dump_outputs(args.dump_outputs, arrays)
+        log(f"dumped {nfiles} arrays ({nbytes / 1e6:.1f} MB) to {args.dump_outputs}")
 
     value = world * B * args.steps / elapsed
     roofline = None

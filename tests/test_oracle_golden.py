@@ -383,12 +383,3 @@ def test_oracle_frame_discriminator_matches_reference_golden(golden_dir):
     for k, p in m.named_parameters():
         np.testing.assert_allclose(p.grad.numpy(), g["grad/" + k], atol=1e-6, rtol=1e-4)
 
-
-@pytest.mark.skipif(not os.path.isdir("/root/reference/src"), reason="the reference only exists in the build container")
-def test_committed_fixtures_are_what_the_generator_writes():
-    """tools/check_golden.py: regenerate every fixture from the reference into a scratch directory and compare bit for bit"""
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "tools", "check_golden.py")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
