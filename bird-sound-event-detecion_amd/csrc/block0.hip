@@ -410,9 +410,7 @@ __global__ __launch_bounds__(B0F_THREADS) void b0_fwd_kernel(
 // accumulator per lane instead of 64 VALU accumulators and 12 cross-lane shuffles per position.
 // ---------------------------------------------------------------------------------------------
 #define B0B_THREADS 256
-#ifndef B0B_WPE
 #define B0B_WPE 3
-#endif
 #define B0_TP 20   // pitch of the transpose tiles (floats)
 
 template <int PH, bool SMALL, int ABF>   // ABF: d_pooled is a bf16 tensor (bf16 mode)
@@ -663,8 +661,7 @@ extern "C" int bsed_block0_fwd(const float* x, const float* cw, const float* cb,
   BSED_CHECK_ARG(B > 0 && H > 0 && W > 0 && (ph == 1 || ph == 2) && (pw == 1 || pw == 2) && W % pw == 0 && H >= ph &&
                      (long)B * H * W < (1L << 31), "bsed_block0_fwd: bad shape");
   const long items = (long)B * (H / ph) * ((W + B0F_THREADS / 4 - 1) / (B0F_THREADS / 4));
-  static const long gmax = getenv("BSED_B0_FWD_G") ? atol(getenv("BSED_B0_FWD_G")) : 8192;   // A/B knob
-  const dim3 grid((unsigned)std::min<long>(items, gmax));
+  const dim3 grid((unsigned)std::min<long>(items, 8192));
   hipStream_t s = (hipStream_t)stream;
   // SMALL: fewer than 2^28 positions (every tensor below 4 GB, element counters below 2^32): 32-bit offsets
   const bool small = (long)B * H * W < (1L << 28);

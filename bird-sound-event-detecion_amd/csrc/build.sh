@@ -20,11 +20,11 @@ for f in *.hip; do
     extra=""; [ "$f" = "mel.hip" ] && extra="-fno-slp-vectorize -mllvm -amdgpu-use-amdgpu-trackers=1"
     # glu3.hip / head.hip: no SLP vectorizer either.  (1) Speed: the packed v_pk_* forms it makes of the epilogues'
     # per-element fp32 arithmetic are SLOWER here (GLU backward family 2.14 -> 1.91 ms per step at B = 256, same-box
-    # A/B; igemm.hip, block0.hip and gru.hip lose without it and keep it).  (2) Correctness: with the vectorizer on, a
-    # build of glu_bwd3n_kernel whose tile width is a compile-time constant is mis-generated by hipcc 7.2 (the pool /
+    # A/B; igemm.hip, block0.hip and gru.hip lose without it and keep it).  (2) Repeatability: with the vectorizer on, a
+    # build of glu_bwd3n_kernel whose tile width is a compile-time constant is not bitwise repeatable (the pool /
     # dropout mask of one element class flips in lanes 48..63 from launch to launch; no wait state, scheduling fence or
-    # s_waitcnt changes it -- tools/asm_variant.sh experiments, DESIGN.md section 5 -- and it is gone without the
-    # vectorizer); tests/test_glu_repeat_gpu.py checks every built instance over repeated launches.
+    # s_waitcnt changes it -- tools/asm_variant.sh experiments).  Cause not identified; masked by
+    # -fno-slp-vectorize; see ADVICE.md.  tests/test_glu_repeat_gpu.py checks every built instance over repeated launches.
     { [ "$f" = "glu3.hip" ] || [ "$f" = "head.hip" ]; } && extra="-fno-slp-vectorize"
     $HIPCC $FLAGS $extra -c "$f" -o "$o" &
     pids+=($!)

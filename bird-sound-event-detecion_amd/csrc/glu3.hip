@@ -47,10 +47,7 @@ struct Glu3Params {
   const uint64_t* seed_add;   // device-resident addend of the seed (HIP-graph replays), or null
 };
 
-static bool glu3_const_tw(const Glu3Params& P) {   // BSED_GLU3_LGTW=-1: runtime-geometry instances only (A/B runs)
-  static const bool off = getenv("BSED_GLU3_LGTW") && atoi(getenv("BSED_GLU3_LGTW")) < 0;
-  return P.lgTW == 4 && !off;
-}
+static bool glu3_const_tw(const Glu3Params& P) { return P.lgTW == 4; }
 
 // Orders this wave's LDS writes before its later LDS reads.  The hardware executes one wave's LDS instructions in
 // issue order, but the COMPILER may move a 16-byte fragment load above the 2-byte element stores that produce it (type
@@ -170,9 +167,7 @@ __device__ __forceinline__ float drop_mul32(uint32_t e, uint32_t key, uint32_t t
   return (h >> 8) >= thr ? scale : 0.f;
 }
 
-#ifndef G3_B32_WPE
 #define G3_B32_WPE 3
-#endif
 template <int C, int LGTW, int ABF>
 __global__ __launch_bounds__(G3_THREADS, C == 32 ? G3_B32_WPE : 2) void glu_bwd3_kernel(const Glu3Params P) {
   constexpr int NT = C / 32, KS = C / 16;
@@ -473,11 +468,12 @@ __global__ __launch_bounds__(G3N_THREADS) void glu_bwd3n_kernel(const Glu3Params
   // tolerance test green).  Round 3 reproduced it (G3N_LGTW=4, 216 x 16 map: EVERY launch differs -- the pool / dropout
   // mask of the first row group flips for lanes 48..63 of channel tiles 1..3) and ruled out, by assembling patched
   // listings (tools/asm_variant.sh), every wait-state explanation: an s_nop after each vector instruction of the
-  // epilogue, after each v_cmp, before each s_and_b64, after each load, s_waitcnt 0 everywhere -- none changes it.  It
-  // is a code-generation problem of hipcc 7.2 tied to the SLP vectorizer's packed (v_pk_* with op_sel swizzles) form
-  // of this epilogue: with -fno-slp-vectorize (csrc/build.sh, this file) BOTH geometries are bit-repeatable at all
-  // four tile widths over 100 launches each (tools/glu3n_repeat.py), and the kernel is 5-12 % faster.  Compile-time
-  // geometry is slower here (hoisted index arithmetic spills: 533 vs 423 us at 216 x 16), so it stays a runtime value.
+  // epilogue, after each v_cmp, before each s_and_b64, after each load, s_waitcnt 0 everywhere -- none changes it.  The
+  // cause is not identified (no faulty instruction was found); it is masked by -fno-slp-vectorize (csrc/build.sh, this
+  // file), without the SLP vectorizer's packed (v_pk_* with op_sel swizzles) form of this epilogue: BOTH geometries are
+  // then bit-repeatable at all four tile widths over 100 launches each (tools/glu3n_repeat.py), and the kernel is 5-12 %
+  // faster.  See ADVICE.md.  Compile-time geometry is slower here (hoisted index arithmetic spills: 533 vs 423 us at
+  // 216 x 16), so it stays a runtime value.
   constexpr int DQ = 2 * 16 + 8;  // ushorts per row of the 16-channel chunk tile: 16 hi | 16 lo | 8 pad (80 B = 5 x 16 B)
   extern __shared__ __align__(16) unsigned char smem_raw[];
   bf16x8* WF = reinterpret_cast<bf16x8*>(smem_raw);
@@ -919,11 +915,7 @@ static int fill_params(Glu3Params& P, int NB, int H, int W, int C, int TH, int T
 extern "C" int bsed_glu_bwd3_slabs(int C) { (void)C; return 4; }
 
 // workgroups of one resident round (persistent kernel): LDS- and register-limited occupancy x 256 CUs
-static int env_g(const char* name, int dflt) {   // A/B knob: workgroups of the persistent grid
-  const char* v = getenv(name);
-  return v && atoi(v) > 0 ? atoi(v) : dflt;
-}
-extern "C" int bsed_glu_bwd3_auto_g(int C) { return C == 32 ? env_g("BSED_GLU_BWD3_G32", 768) : env_g("BSED_GLU_BWD3_G64", 512); }
+extern "C" int bsed_glu_bwd3_auto_g(int C) { return C == 32 ? 768 : 512; }
 
 extern "C" int bsed_glu_bwd3(const float* y, const float* scale, const float* shift, const float* w, const float* bias,
                              const float* dpool, float* g, float* part_dw, float* part_db, float* part_st, int G,
@@ -948,7 +940,7 @@ extern "C" int bsed_glu_bwd3(const float* y, const float* scale, const float* sh
 extern "C" int bsed_glu_fwd3_auto_g(int C) {
   // measured (B = 256): C = 32: 512 / 768 / 1024 / 1536 workgroups 0.447 / 0.367 / 0.412 / 0.350 ms; C = 64: 0.180 / 0.160 / 0.167 / 0.155;
   // C = 128 (64 KB of weight fragments in LDS, two per CU): 256 / 512 / 768 / 1024 0.514 / 0.422 / 0.454 / 0.435
-  return C == 32 ? env_g("BSED_GLU_FWD3_G32", 1536) : C == 64 ? env_g("BSED_GLU_FWD3_G64", 1536) : env_g("BSED_GLU_FWD3_G128", 512);
+  return C == 32 ? 1536 : C == 64 ? 1536 : 512;
 }
 
 extern "C" int bsed_glu_fwd3(const float* y, const float* scale, const float* shift, const float* w, const float* bias,

@@ -478,8 +478,6 @@ extern "C" int bsed_decode_write(const float* mask, const int* offsets, int B, i
 // time splits per clip: enough workgroups for ~4 per CU, whole 32-frame chunks each
 extern "C" int bsed_head_splits(int B, int T) {
   const int chunks = (T + HD_FR - 1) / HD_FR;
-  static const int forced = getenv("BSED_HEAD_SPLITS") ? atoi(getenv("BSED_HEAD_SPLITS")) : 0;   // A/B knob
-  if (forced > 0) return forced <= chunks ? forced : chunks;
   int S = 1;
   // (B = 256: two splits -- 512 workgroups, one per CU at a time: 85-90 KB of LDS each; four were 15 % slower backward)
   while (S < 8 && (long)B * S < 512 && S * 2 <= chunks) S *= 2;

@@ -488,12 +488,9 @@ __device__ __forceinline__ f32x16 w3_mfma(const w3_bf16x8& a_hi, const w3_bf16x8
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_hi, b_hi, acc, 0, 0, 0);
 }
 
-#ifndef W3_SMALL_WPE
-#define W3_SMALL_WPE 4
-#endif
 // the 1- and 2-slot 4-wave forms (conv1 16 -> 32 channels: 39 KB of LDS) are pinned to 128 registers so that FOUR
-// workgroups share a CU: 0.753 (three, 136 registers) -> 0.651 ms, 4.9 TB/s (A/B: -DW3_SMALL_WPE=2)
-#define W3_WPE(MAXS, NW) ((MAXS) <= 2 && (NW) == 4 ? W3_SMALL_WPE : 2)
+// workgroups share a CU: 0.753 (three, 136 registers) -> 0.651 ms, 4.9 TB/s
+#define W3_WPE(MAXS, NW) ((MAXS) <= 2 && (NW) == 4 ? 4 : 2)
 template <int MAXS, int NW, bool BS, int ABF>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(W3_WPE(MAXS, NW)))) void wgrad3_kernel(const WgradParams P) {
   constexpr int NTHR = NW * 64;
@@ -886,24 +883,6 @@ __host__ __device__ constexpr W3Geo w3_geo(int g) {
 }
 #define W3_NGEO 6
 
-// Diagnostic build (-DW3P_STAMP, tools/build_variant.sh + tools/wgrad_stamp.py): s_memtime stamps of the fourth tile period
-// of every workgroup -- slots 0..3 producer wave 4 (period start, loads landed, conversions + refills issued, barrier
-// passed), 4..6 consumer wave 0 (period start, MFMAs issued, barrier passed), 7 HW_ID.
-#ifdef W3P_STAMP
-__device__ unsigned long long w3p_stamp_buf[1024 * 8];
-extern "C" int bsed_w3p_stamps(unsigned long long* host) {
-  return hipMemcpyFromSymbol(host, HIP_SYMBOL(w3p_stamp_buf), sizeof(w3p_stamp_buf)) == hipSuccess ? 0 : 1;
-}
-#define W3P_ST(slot, cond)                                                                                         \
-  if (cond) {                                                                                                      \
-    const unsigned long long t_ = __builtin_amdgcn_s_memtime();                                                    \
-    if ((threadIdx.x & 63) == 0)                                                                                   \
-      w3p_stamp_buf[((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) % 1024 * 8 + (slot)] = t_;    \
-  }
-#else
-#define W3P_ST(slot, cond)
-#endif
-
 template <int MAXS, int GEO, int ABF>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void wgrad3p_kernel(const WgradParams P) {
   constexpr int NTHR = 256, NW = 4, UX = W3P_UX, UD = W3P_UD;
@@ -1199,12 +1178,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         const TGeo gn = tgeo(nxt < P.ntiles ? nxt : tile);
         // (the buffer being written was last read before the previous barrier)
         const int bo = buf * buf_u16;
-#ifdef W3P_STAMP
-        const bool st_ = tile == (int)blockIdx.x + 3 * (int)gridDim.x && tid < 64;
-        W3P_ST(0, st_);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        W3P_ST(1, st_);
-#endif
 #pragma unroll
         for (int u = 0; u < UD; ++u) {
           if (GEO && u * NTHR >= d_tot) continue;
@@ -1238,14 +1211,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
           if (tid + u * NTHR < x_tot) w3_store4<ABF>(Xh, Xl, bo + xo[u], w);
           vx[u] = ld16(p.in, gn.in_img, x_at(u, gn, okn));
         }
-#ifdef W3P_STAMP
-        W3P_ST(2, st_);
-#endif
         gc = gn; tile = nxt;
         __syncthreads();
-#ifdef W3P_STAMP
-        W3P_ST(3, st_);
-#endif
       }
     };
     if (!bnb) produce(std::false_type{}, std::false_type{});
@@ -1293,10 +1260,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   // fragments of slot group g+1 are requested before the MFMAs of group g issue (two groups live at a time)
   constexpr int SG = 2, NG = (MAXS + SG - 1) / SG;
   for (int tile = blockIdx.x; tile < P.ntiles; tile += gridDim.x, buf ^= 1) {
-#ifdef W3P_STAMP
-    const bool st_ = tile == (int)blockIdx.x + 3 * (int)gridDim.x && tid < 64;
-    W3P_ST(4, st_);
-#endif
     if constexpr (GEO > 0) {
       constexpr W3Geo Gm = w3_geo(GEO);
       constexpr uint32_t kstep = 2 * (16 >> Gm.lgTW) * Gm.PW * Gm.CC, bstep = 2 * 16 * 32 * Gm.ntw;
@@ -1376,18 +1339,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         }
       }
     }
-#ifdef W3P_STAMP
-    W3P_ST(5, st_);
-#endif
     __syncthreads();
-#ifdef W3P_STAMP
-    W3P_ST(6, st_);
-    if (st_ && lane == 0) {
-      unsigned hw_;
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw_));
-      w3p_stamp_buf[((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) % 1024 * 8 + 7] = hw_;
-    }
-#endif
   }
   const int NPo = gridDim.y * DYW;
 #pragma unroll
@@ -1678,12 +1630,6 @@ static int wgrad_prepare(const BsedWgradDesc* desc, WgradParams& P, size_t& smem
   BSED_CHECK_ARG(!d.bn_y || mode3, "bsed_wgrad: BatchNorm backward on load is built into the split-fp32 kernels (bsed_wgrad3) only");
   BSED_CHECK_ARG(!d.dy_out || (d.dy_out != d.dy && d.dy_out != d.bn_y), "bsed_wgrad: dy_out must not alias dy or bn_y "
                  "(other workgroups still read them)");
-  BSED_CHECK_ARG((d.bn_y == nullptr) == (d.bn_coef == nullptr) && (d.bn_y == nullptr) == (d.bn_mean == nullptr),
-                 "bsed_wgrad: bn_y, bn_coef and bn_mean come together (BatchNorm backward applied on load) or not at all");
-  BSED_CHECK_ARG(d.bn_y || !d.dy_out, "bsed_wgrad: dy_out only goes with bn_y");
-  BSED_CHECK_ARG(!d.bn_y || mode3, "bsed_wgrad: BatchNorm backward on load is built into the split-fp32 kernels (bsed_wgrad3) only");
-  BSED_CHECK_ARG(!d.dy_out || (d.dy_out != d.dy && d.dy_out != d.bn_y), "bsed_wgrad: dy_out must not alias dy or bn_y "
-                 "(other workgroups still read them)");
   d.tilesH = ceil_div(d.H, d.TH);
   d.tilesW = d.W / d.TW;
   P.PW = d.TW + 2 * d.hw;
@@ -1691,10 +1637,7 @@ static int wgrad_prepare(const BsedWgradDesc* desc, WgradParams& P, size_t& smem
   P.PP = P.PW * P.PH;
   // input channels are contracted in chunks of CC per workgroup (grid.z): 64 for the 9-tap convolutions so that
   // two workgroups fit in a CU's LDS and one's tile load overlaps the other's MFMAs, 128 for the 1-tap forms
-  // (A/B knob: BSED_WGRAD3_1TAP_PIPE=1 gives the split-fp32 1-tap forms the multi-tap geometry -- 64-channel chunks, an
-  //  80 KB tile -- so that the producer / consumer kernel with its two tile buffers can take them)
-  static const bool onetap_pipe = getenv("BSED_WGRAD3_1TAP_PIPE") && getenv("BSED_WGRAD3_1TAP_PIPE")[0] == '1';
-  const bool wide1 = d.ntaps == 1 && !(mode3 && onetap_pipe);
+  const bool wide1 = d.ntaps == 1;
   P.CC = 32;
   for (int cand = (wide1 ? 128 : 64); cand >= 32; cand >>= 1)
     if (d.CINP % cand == 0) { P.CC = cand; break; }
@@ -1793,9 +1736,8 @@ extern "C" int bsed_wgrad(const BsedWgradDesc* desc, void* stream) {
   return BSED_ERR_ARG;
 }
 
-
 template <int MAXS, int NW, bool BS>
-static int launch_wgrad3_bs(const WgradParams& P, dim3 grid, size_t smem, hipStream_t s) {
+static int launch_wgrad3(const WgradParams& P, dim3 grid, size_t smem, hipStream_t s) {
   static BsedLdsOnce once, onceb;
   if (P.d.act_bf16) {
     BSED_HIP(bsed_max_lds(onceb, (const void*)wgrad3_kernel<MAXS, NW, BS, 1>));
@@ -1806,12 +1748,6 @@ static int launch_wgrad3_bs(const WgradParams& P, dim3 grid, size_t smem, hipStr
   }
   BSED_LAUNCH_CHECK();
   return BSED_OK;
-}
-
-template <int MAXS, int NW>
-static int launch_wgrad3(const WgradParams& P, dim3 grid, size_t smem, hipStream_t s) {
-  if (NW % (P.nct * P.ntw) == 0) return launch_wgrad3_bs<MAXS, NW, true>(P, grid, smem, s);
-  return launch_wgrad3_bs<MAXS, NW, false>(P, grid, smem, s);
 }
 
 template <int MAXS, int GEO>
@@ -1837,17 +1773,8 @@ static int wgrad3p_geo(const WgradParams& P) {
   return 0;
 }
 
-template <int MAXS>
-static int launch_wgrad3p(const WgradParams& P, dim3 grid, size_t smem, hipStream_t s) {
-  const int g = getenv("BSED_WGRAD3_NOGEO") ? 0 : wgrad3p_geo(P);
-  if (MAXS == 9 && g == 1) return launch_wgrad3p_geo<9, 1>(P, grid, smem, s);
-  if (MAXS == 9 && g == 2) return launch_wgrad3p_geo<9, 2>(P, grid, smem, s);
-  if (MAXS == 5 && g == 3) return launch_wgrad3p_geo<5, 3>(P, grid, smem, s);
-  if (MAXS == 5 && g == 4) return launch_wgrad3p_geo<5, 4>(P, grid, smem, s);
-  if (MAXS == 5 && g == 5) return launch_wgrad3p_geo<5, 5>(P, grid, smem, s);
-  if (MAXS == 3 && g == 6) return launch_wgrad3p_geo<3, 6>(P, grid, smem, s);
-  return launch_wgrad3p_geo<MAXS, 0>(P, grid, smem, s);
-}
+// the MAXS each compile-time geometry is built for (GEO = 0, run-time geometry, is built for MAXS = 3, 5 and 9)
+static constexpr int w3p_geo_maxs(int g) { return g <= 2 ? 9 : (g <= 5 ? 5 : 3); }
 
 // the pipelined kernel takes the multi-tap shapes whose two tile buffers fit in LDS and whose per-thread prefetch fits
 // its register arrays; everything else (1-tap forms, tall narrow patches) stays on wgrad3_kernel
@@ -1856,23 +1783,67 @@ static bool wgrad3_pipelined(const WgradParams& P, size_t smem) {
   // fewest (tap, chunk) items the pipelined kernel takes: 4, i.e. the 16 -> 32 channel layer (5 items: two taps per MFMA
   // tile) included.  With run-time geometry the pipelined kernel lost to wgrad3_kernel there with fp32 activations (0.78
   // vs 0.69 ms; bf16: 0.41 vs 0.65); with the layer's geometry compiled in (w3_geo(6)) it wins in both modes: 0.60 ms
-  // fp32, 0.28 ms bf16.  BSED_WGRAD3_PIPE_MIN: A/B knob (8 = the old choice)
-  static const int pipe_env = getenv("BSED_WGRAD3_PIPE_MIN") ? atoi(getenv("BSED_WGRAD3_PIPE_MIN")) : 0;
-  const int pipe_min = pipe_env > 0 ? pipe_env : 4;
-  static const bool onetap_pipe = getenv("BSED_WGRAD3_1TAP_PIPE") && getenv("BSED_WGRAD3_1TAP_PIPE")[0] == '1';
-  if (P.d.ntaps == 1 && !onetap_pipe) return false;
-  return nitems > (P.d.ntaps == 1 ? 3 : pipe_min) &&
+  // fp32, 0.28 ms bf16 (against 8 items, the earlier threshold).  BSED_WGRAD3_NOPIPE (read per call: tests switch
+  // inside one process) keeps every shape on wgrad3_kernel.
+  return P.d.ntaps > 1 && nitems > 4 &&
          P.d.H < 16384 && P.d.W < 16384 && 2 * smem <= 160 * 1024 && 4 % (P.nct * P.ntw) == 0 && nitems <= 36 &&
          P.PP * (P.CC / 4) <= W3P_UX * 256 && IG_TILE_M * 8 * P.ntw <= W3P_UD * 256 && !getenv("BSED_WGRAD3_NOPIPE");
 }
 
-// the streaming 1-tap kernel takes the shapes whose slabs tile into 128 x 128 blocks (BSED_WGRAD1=0: A/B against
-// wgrad3_kernel)
+// the streaming 1-tap kernel takes the shapes whose slabs tile into 128 x 128 blocks
 static bool wgrad1_streaming(const WgradParams& P) {
-  static const bool off = getenv("BSED_WGRAD1") && getenv("BSED_WGRAD1")[0] == '0';
   const BsedWgradDesc& d = P.d;
-  return !off && d.ntaps == 1 && P.CC == 128 && P.ntw == 4 && d.CINP % 128 == 0 && d.NP % 128 == 0 && !d.bn_y &&
+  return d.ntaps == 1 && P.CC == 128 && P.ntw == 4 && d.CINP % 128 == 0 && d.NP % 128 == 0 && !d.bn_y &&
          (long)d.NB * d.H * d.W < (1L << 31) - 4 * 65536;
+}
+
+// The ONE choice of the split-fp32 weight-gradient kernel for a shape: bsed_wgrad3 launches it, bsed_wgrad3_variant
+// reports it and bsed_wgrad3_auto_g sizes its grid.
+enum W3Kind { W3_TILE, W3_PIPE, W3_STREAM1 };
+struct W3Plan {
+  W3Kind kind;
+  int maxs, nw, geo;   // wgrad3_kernel<MAXS, NW, BS>, wgrad3p_kernel<MAXS, GEO>
+  bool bs, shifted;    // BS; wgrad1_kernel<SHIFT>
+};
+static W3Plan wgrad3_plan(const WgradParams& P, size_t smem) {
+  if (wgrad1_streaming(P)) return {W3_STREAM1, 0, 0, 0, false, P.d.dh[0] != 0 || P.d.dw[0] != 0};
+  const int v = wgrad_variant(P), maxs = v / 16, nw = v % 16;
+  if (wgrad3_pipelined(P, smem)) {
+    const int m = maxs <= 3 ? 3 : (maxs <= 5 ? 5 : 9), g = wgrad3p_geo(P);
+    return {W3_PIPE, m, 1, g && w3p_geo_maxs(g) == m ? g : 0, false, false};
+  }
+  return {W3_TILE, maxs, nw, 0, nw % (P.nct * P.ntw) == 0, false};
+}
+
+template <int GEO = W3_NGEO>
+static int launch_wgrad3p(const W3Plan& pl, const WgradParams& P, dim3 grid, size_t smem, hipStream_t s) {
+  if constexpr (GEO > 0) {
+    if (pl.geo == GEO) return launch_wgrad3p_geo<w3p_geo_maxs(GEO), GEO>(P, grid, smem, s);
+    return launch_wgrad3p<GEO - 1>(pl, P, grid, smem, s);
+  } else {
+    if (pl.maxs == 3) return launch_wgrad3p_geo<3, 0>(P, grid, smem, s);
+    if (pl.maxs == 5) return launch_wgrad3p_geo<5, 0>(P, grid, smem, s);
+    return launch_wgrad3p_geo<9, 0>(P, grid, smem, s);
+  }
+}
+
+template <bool SHIFT>
+static int launch_wgrad1(const WgradParams& P, dim3 grid, hipStream_t s) {
+  static BsedLdsOnce once, onceb;
+  if (P.d.act_bf16) {
+    BSED_HIP(bsed_max_lds(onceb, (const void*)wgrad1_kernel<SHIFT, 1>));
+    hipLaunchKernelGGL((wgrad1_kernel<SHIFT, 1>), grid, dim3(W1_THREADS), 2 * W1_STAGE, s, P);
+  } else {
+    BSED_HIP(bsed_max_lds(once, (const void*)wgrad1_kernel<SHIFT, 0>));
+    hipLaunchKernelGGL((wgrad1_kernel<SHIFT, 0>), grid, dim3(W1_THREADS), 2 * W1_STAGE, s, P);
+  }
+  BSED_LAUNCH_CHECK();
+  return BSED_OK;
+}
+
+template <int MAXS, int NW>
+static int launch_wgrad3_tile(const W3Plan& pl, const WgradParams& P, dim3 grid, size_t smem, hipStream_t s) {
+  return pl.bs ? launch_wgrad3<MAXS, NW, true>(P, grid, smem, s) : launch_wgrad3<MAXS, NW, false>(P, grid, smem, s);
 }
 
 extern "C" int bsed_wgrad3_auto_g(const BsedWgradDesc* desc) {
@@ -1880,34 +1851,29 @@ extern "C" int bsed_wgrad3_auto_g(const BsedWgradDesc* desc) {
   size_t smem;
   dim3 gyz;
   if (wgrad_prepare(desc, P, smem, gyz, 1) != BSED_OK) return -1;
-  long slots = wgrad3_pipelined(P, smem) ? 256 : smem <= 80 * 1024 ? 512 : 256;
+  const W3Plan pl = wgrad3_plan(P, smem);
+  long slots = pl.kind == W3_PIPE ? 256 : smem <= 80 * 1024 ? 512 : 256;
   // small tiles (conv1 16 -> 32 channel gradient: 39 KB, 136 registers): a third workgroup per CU fits and hides more of
   // the stage / barrier / MFMA serialisation: 0.956 -> 0.753 ms; a fourth (the kernel pinned to 128 registers) 0.651 ms
-  // (BSED_WGRAD3_SLOTS_SMALL for A/B runs)
-  static const int small_slots = getenv("BSED_WGRAD3_SLOTS_SMALL") ? atoi(getenv("BSED_WGRAD3_SLOTS_SMALL")) : 1024;
-  if (!wgrad3_pipelined(P, smem) && smem <= 52 * 1024 && wgrad_variant(P) / 16 <= 2) slots = small_slots;
+  if (pl.kind != W3_PIPE && smem <= 52 * 1024 && wgrad_variant(P) / 16 <= 2) slots = 1024;
   long want = std::max<long>(1, slots / ((long)gyz.y * gyz.z));
   // XCD affinity: workgroup (x, y, z) has linear id x + G * (y + gy * z) and lands on XCD id % 8.  The gy * gz
   // workgroups of one tile sequence x read the same activation / dy tiles at about the same time; with G a multiple of
-  // 8 they share an XCD, hence its L2, and the re-reads stop going to HBM (BSED_WGRAD3_G8=0 disables, for A/B runs)
-  const char* g8 = getenv("BSED_WGRAD3_G8");
-  if (gyz.y * gyz.z > 1 && (want % 8) * 16 <= want && !(g8 && g8[0] == '0')) want -= want % 8;  // <= 6 % fewer workgroups
+  // 8 they share an XCD, hence its L2, and the re-reads stop going to HBM
+  if (gyz.y * gyz.z > 1 && (want % 8) * 16 <= want) want -= want % 8;  // <= 6 % fewer workgroups
   return (int)std::max<long>(1, std::min<long>(want, P.ntiles));
 }
 
+// bench / profile labels: wgrad1_kernel<SHIFT> = 1 << 13 | SHIFT; otherwise MAXS * 16 + NW with NW = 1 for
+// wgrad3p_kernel<MAXS, GEO> (GEO in bits 8..11) and bit 12 = the BS template argument of wgrad3_kernel
 extern "C" int bsed_wgrad3_variant(const BsedWgradDesc* desc) {
   WgradParams P;
   size_t smem;
   dim3 gyz;
   if (wgrad_prepare(desc, P, smem, gyz, 1) != BSED_OK) return -1;
-  if (wgrad1_streaming(P)) return (1 << 13) | ((P.d.dh[0] != 0 || P.d.dw[0] != 0) ? 1 : 0);  // wgrad1_kernel<SHIFT>
-  const int v = wgrad_variant(P);
-  if (wgrad3_pipelined(P, smem)) {  // NW field 1 = wgrad3p_kernel<MAXS, GEO>, GEO in bits 8..11
-    const int maxs = v / 16 <= 3 ? 3 : (v / 16 <= 5 ? 5 : 9), g = getenv("BSED_WGRAD3_NOGEO") ? 0 : wgrad3p_geo(P);
-    const bool built = (maxs == 9 && (g == 1 || g == 2)) || (maxs == 5 && g >= 3 && g <= 5) || (maxs == 3 && g == 6);
-    return maxs * 16 + 1 + ((built ? g : 0) << 8);
-  }
-  return v | (((v % 16) % (P.nct * P.ntw) == 0) ? 1 << 12 : 0);  // bit 12 = the BS template argument
+  const W3Plan pl = wgrad3_plan(P, smem);
+  if (pl.kind == W3_STREAM1) return (1 << 13) | (pl.shifted ? 1 : 0);
+  return pl.maxs * 16 + pl.nw + (pl.geo << 8) + (pl.bs ? 1 << 12 : 0);
 }
 
 extern "C" int bsed_wgrad3(const BsedWgradDesc* desc, void* stream) {
@@ -1921,41 +1887,19 @@ extern "C" int bsed_wgrad3(const BsedWgradDesc* desc, void* stream) {
   BSED_CHECK_ARG(d.G > 0 && d.G <= P.ntiles, "bsed_wgrad3: G (%d) must be in 1..%d tiles", d.G, P.ntiles);
   dim3 grid((unsigned)d.G, gyz.y, gyz.z);
   hipStream_t s = (hipStream_t)stream;
-  if (wgrad1_streaming(P)) {
-    const bool shifted = d.dh[0] != 0 || d.dw[0] != 0;
-    static BsedLdsOnce once0, once1, once0b, once1b;
-    if (d.act_bf16 && shifted) {
-      BSED_HIP(bsed_max_lds(once1b, (const void*)wgrad1_kernel<true, 1>));
-      hipLaunchKernelGGL((wgrad1_kernel<true, 1>), grid, dim3(W1_THREADS), 2 * W1_STAGE, s, P);
-    } else if (d.act_bf16) {
-      BSED_HIP(bsed_max_lds(once0b, (const void*)wgrad1_kernel<false, 1>));
-      hipLaunchKernelGGL((wgrad1_kernel<false, 1>), grid, dim3(W1_THREADS), 2 * W1_STAGE, s, P);
-    } else if (shifted) {
-      BSED_HIP(bsed_max_lds(once1, (const void*)wgrad1_kernel<true, 0>));
-      hipLaunchKernelGGL((wgrad1_kernel<true, 0>), grid, dim3(W1_THREADS), 2 * W1_STAGE, s, P);
-    } else {
-      BSED_HIP(bsed_max_lds(once0, (const void*)wgrad1_kernel<false, 0>));
-      hipLaunchKernelGGL((wgrad1_kernel<false, 0>), grid, dim3(W1_THREADS), 2 * W1_STAGE, s, P);
-    }
-    BSED_LAUNCH_CHECK();
-    return BSED_OK;
+  const W3Plan pl = wgrad3_plan(P, smem);
+  if (pl.kind == W3_STREAM1) return pl.shifted ? launch_wgrad1<true>(P, grid, s) : launch_wgrad1<false>(P, grid, s);
+  if (pl.kind == W3_PIPE) return launch_wgrad3p(pl, P, grid, smem, s);
+  if (pl.nw == 8) {
+    if (pl.maxs == 2) return launch_wgrad3_tile<2, 8>(pl, P, grid, smem, s);
+    if (pl.maxs == 3) return launch_wgrad3_tile<3, 8>(pl, P, grid, smem, s);
+    return launch_wgrad3_tile<5, 8>(pl, P, grid, smem, s);
   }
-  const int v = wgrad_variant(P), maxs = v / 16, nw = v % 16;
-  if (wgrad3_pipelined(P, smem)) {
-    if (maxs <= 3) return launch_wgrad3p<3>(P, grid, smem, s);
-    if (maxs <= 5) return launch_wgrad3p<5>(P, grid, smem, s);
-    return launch_wgrad3p<9>(P, grid, smem, s);
-  }
-  if (nw == 8) {
-    if (maxs == 2) return launch_wgrad3<2, 8>(P, grid, smem, s);
-    if (maxs == 3) return launch_wgrad3<3, 8>(P, grid, smem, s);
-    return launch_wgrad3<5, 8>(P, grid, smem, s);
-  }
-  if (maxs == 1) return launch_wgrad3<1, 4>(P, grid, smem, s);
-  if (maxs == 2) return launch_wgrad3<2, 4>(P, grid, smem, s);
-  if (maxs == 3) return launch_wgrad3<3, 4>(P, grid, smem, s);
-  if (maxs == 5) return launch_wgrad3<5, 4>(P, grid, smem, s);
-  return launch_wgrad3<9, 4>(P, grid, smem, s);
+  if (pl.maxs == 1) return launch_wgrad3_tile<1, 4>(pl, P, grid, smem, s);
+  if (pl.maxs == 2) return launch_wgrad3_tile<2, 4>(pl, P, grid, smem, s);
+  if (pl.maxs == 3) return launch_wgrad3_tile<3, 4>(pl, P, grid, smem, s);
+  if (pl.maxs == 5) return launch_wgrad3_tile<5, 4>(pl, P, grid, smem, s);
+  return launch_wgrad3_tile<9, 4>(pl, P, grid, smem, s);
 }
 
 extern "C" int bsed_reduce_partials(const float* part, int G, int ntaps, int KP, int NP, int K, int N, float* dst,

@@ -17,12 +17,6 @@
 #define I3_M 128
 #define I3_KC 32
 #define I3_ROW 72  // ushorts per LDS row: 32 hi + 32 lo + 8 pad
-// Ablation builds (diagnostic, tools/build_variant.sh <tag> igemm3.hip "-DI3_ABL=<bits>"; results are WRONG by design):
-//   1 = no MFMAs (fragments kept live), 2 = no fragment reads from LDS (constant fragments), 4 = no epilogue stores,
-//   8 = no weight-slab staging (one slab, no per-tap barriers), 16 = no activation-patch loads after the first chunk
-#ifndef I3_ABL
-#define I3_ABL 0
-#endif
 
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -42,7 +36,8 @@ __device__ __forceinline__ int crow3(int r, int lh) { return (r & 3) + 8 * (r >>
 // RB = 32-row blocks per wave: 1 -> a workgroup covers 128 positions, 2 -> 256 (TH*TW = 256).  With RB = 2 every B
 // fragment read from LDS feeds two MFMA row blocks: 24 ds_read_b128 per 48 MFMAs instead of 20 per 24 -- the LDS pipe
 // (one per CU, shared by all resident waves) was the co-limiter of the RB = 1 kernel at ~30 % of the MFMA peak -- and a
-// weight slab is staged once per 256 positions instead of once per 128.
+// weight slab is staged once per 256 positions instead of once per 128.  Measured no faster than RB = 1: only RB = 1
+// is instantiated.
 template <int BN, int STATS, int RB, int PV>
 // (waves_per_eu caps the register budget the allocator aims for: without it the prefetch registers were spilled to
 // scratch right after their loads, which serialised the loads again)
@@ -51,12 +46,9 @@ template <int BN, int STATS, int RB, int PV>
 // third resident workgroup is worth 7 %, so there the minimum is pinned to 3 as well)
 __global__ __launch_bounds__(I3_THREADS)
 // (BN <= 64: pinned to FOUR waves per SIMD, i.e. 128 registers and a fourth resident workgroup: 0.446 / 0.335 / 0.312 ms ->
-//  0.41 / 0.295 / 0.271 on the 64- and 32-channel layers; A/B: -DI3_WPE_SMALL=3)
-#ifndef I3_WPE_SMALL
-#define I3_WPE_SMALL 4
-#endif
-__attribute__((amdgpu_waves_per_eu(RB == 2 ? 1 : ((BN == 128 && PV <= 9) ? 3 : (BN <= 64 && I3_WPE_SMALL > 3 ? I3_WPE_SMALL : 1)),
-                                   RB == 2 ? 2 : (BN <= 64 ? I3_WPE_SMALL : 3))))  // (PV = 12 would spill at 3)
+//  0.41 / 0.295 / 0.271 on the 64- and 32-channel layers, against three waves per SIMD)
+__attribute__((amdgpu_waves_per_eu(RB == 2 ? 1 : ((BN == 128 && PV <= 9) ? 3 : (BN <= 64 ? 4 : 1)),
+                                   RB == 2 ? 2 : (BN <= 64 ? 4 : 3))))  // (PV = 12 would spill at 3)
 void igemm3_kernel(const Igemm3Params P) {
   constexpr int NT = BN / 32;
   const BsedIgemmDesc& p = P.d;
@@ -129,7 +121,6 @@ void igemm3_kernel(const Igemm3Params P) {
 #pragma unroll
     for (int u = 0; u < NT; ++u) pre[u] = wthr[u * I3_THREADS];
     for (int tap = 0; tap < p.ntaps; ++tap) {
-      if (!(I3_ABL & 8) || tap == 0) {
       if (tap > 0) __syncthreads();  // every wave is done reading the previous slab
 #pragma unroll
       for (int u = 0; u < NT; ++u) {
@@ -137,13 +128,12 @@ void igemm3_kernel(const Igemm3Params P) {
         *reinterpret_cast<u32x4*>(Bs + (e >> 3) * I3_ROW + (e & 7) * 8) = pre[u];
       }
       __syncthreads();
-      }
-      if (tap == 0 && ch + 1 < nchunks && !(I3_ABL & 16)) {  // next chunk's patch: in flight during this chunk's taps
+      if (tap == 0 && ch + 1 < nchunks) {  // next chunk's patch: in flight during this chunk's taps
 #pragma unroll
         for (int u = 0; u < PV; ++u)
           pv[u] = poff[u] >= 0 ? *reinterpret_cast<const f32x4*>(inb + poff[u] + (ch + 1) * I3_KC) : f32x4{0.f, 0.f, 0.f, 0.f};
       }
-      if (!(I3_ABL & 8)) {  // next tap's slab (the last tap re-reads its own: no branch around the loads)
+      {  // next tap's slab (the last tap re-reads its own: no branch around the loads)
         const u32x4* wn = wthr + (size_t)min(tap + 1, p.ntaps - 1) * tap_stride;
 #pragma unroll
         for (int u = 0; u < NT; ++u) pre[u] = wn[u * I3_THREADS];
@@ -158,33 +148,16 @@ void igemm3_kernel(const Igemm3Params P) {
       for (int kk = 0; kk < 2; ++kk) {
 #pragma unroll
         for (int rb = 0; rb < RB; ++rb) {
-          if (I3_ABL & 2) {
-            a_hi[kk][rb] = bf16x8{(short)toff, 1, 2, 3, 4, 5, 6, (short)tid}; a_lo[kk][rb] = a_hi[kk][rb];
-          } else {
           a_hi[kk][rb] = *reinterpret_cast<const bf16x8*>(As + abase[rb] + toff + 16 * kk);
           a_lo[kk][rb] = *reinterpret_cast<const bf16x8*>(As + abase[rb] + toff + 32 + 16 * kk);
-          }
         }
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
-          if (I3_ABL & 2) {
-            b_hi[kk][j] = bf16x8{(short)tap, 1, 2, 3, 4, 5, 6, (short)(tid + j)}; b_lo[kk][j] = b_hi[kk][j];
-          } else {
           b_hi[kk][j] = *reinterpret_cast<const bf16x8*>(brow + 32 * j * I3_ROW + 16 * kk);
           b_lo[kk][j] = *reinterpret_cast<const bf16x8*>(brow + 32 * j * I3_ROW + 32 + 16 * kk);
-          }
         }
       }
       // independent accumulators are interleaved so that consecutive MFMAs never depend on each other
-      if (I3_ABL & 1) {   // keep the fragments live without multiplying
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-#pragma unroll
-          for (int rb = 0; rb < RB; ++rb) asm volatile("" :: "v"(a_hi[kk][rb]), "v"(a_lo[kk][rb]));
-#pragma unroll
-          for (int j = 0; j < NT; ++j) asm volatile("" :: "v"(b_hi[kk][j]), "v"(b_lo[kk][j]));
-        }
-      } else
 #pragma unroll
       for (int kk = 0; kk < 2; ++kk) {
 #pragma unroll
@@ -226,7 +199,7 @@ void igemm3_kernel(const Igemm3Params P) {
       for (int j = 0; j < NT; ++j) {
         if (pok && nok[j]) {
           const float v = acc[rb][j][r] + bias[j];
-          if (!(I3_ABL & 4) || v == 123.456f) orow[32 * j] = v;
+          orow[32 * j] = v;
           if (STATS) { s0[j] += v; s1[j] = fmaf(v, v, s1[j]); }
         }
       }
@@ -663,13 +636,13 @@ static int launch_i3pv(const Igemm3Params& P, dim3 grid, size_t smem, hipStream_
 }
 
 // PV = float4 patch elements per thread: ceil(PP * 8 / 256), instantiated for 6 (up to 192 patch positions: the 18x10
-// patch of a 16x8 tile), 9 (288: tall narrow tiles) and 12 (384: the 256-position tiles)
-template <int BN, int STATS, int RB>
+// patch of a 16x8 tile), 9 (288: tall narrow tiles) and 12 (384)
+template <int BN, int STATS>
 static int launch_i3(const Igemm3Params& P, dim3 grid, size_t smem, hipStream_t s) {
   const int need = ceil_div(P.PP * 8, I3_THREADS);
-  if (RB == 1 && need <= 6) return launch_i3pv<BN, STATS, RB, 6>(P, grid, smem, s);
-  if (RB == 1 && need <= 9) return launch_i3pv<BN, STATS, RB, 9>(P, grid, smem, s);
-  if (need <= 12) return launch_i3pv<BN, STATS, RB, 12>(P, grid, smem, s);
+  if (need <= 6) return launch_i3pv<BN, STATS, 1, 6>(P, grid, smem, s);
+  if (need <= 9) return launch_i3pv<BN, STATS, 1, 9>(P, grid, smem, s);
+  if (need <= 12) return launch_i3pv<BN, STATS, 1, 12>(P, grid, smem, s);
   bsed_set_error("bsed_igemm3: patch of %d positions exceeds the 384 supported", P.PP);
   return BSED_ERR_ARG;
 }
@@ -683,9 +656,7 @@ extern "C" int bsed_igemm3(const BsedIgemmDesc* desc, void* stream) {
   BSED_CHECK_ARG(d.epilogue == BSED_EPI_PLAIN || d.epilogue == BSED_EPI_STATS, "bsed_igemm3: PLAIN / STATS epilogues only");
   BSED_CHECK_ARG(d.epilogue != BSED_EPI_STATS || d.stats, "bsed_igemm3: STATS needs a stats buffer");
   BSED_CHECK_ARG(d.NB > 0 && d.H > 0 && d.W > 0 && d.CIN > 0 && d.CIN % 32 == 0 && d.N > 0, "bsed_igemm3: CIN must be a multiple of 32");
-  BSED_CHECK_ARG((d.TH * d.TW == I3_M || d.TH * d.TW == 2 * I3_M) && d.W % d.TW == 0,
-                 "bsed_igemm3: TH*TW must be 128 or 256 (N a multiple of 128 only) and TW divide W");
-  const int RB = d.TH * d.TW / I3_M;
+  BSED_CHECK_ARG(d.TH * d.TW == I3_M && d.W % d.TW == 0, "bsed_igemm3: TH*TW must be 128 and TW divide W");
   P.lgTW = 0;
   while ((1 << P.lgTW) < d.TW) ++P.lgTW;
   BSED_CHECK_ARG((1 << P.lgTW) == d.TW, "bsed_igemm3: TW must be a power of two");
@@ -694,12 +665,7 @@ extern "C" int bsed_igemm3(const BsedIgemmDesc* desc, void* stream) {
     BSED_CHECK_ARG(abs(d.dh[t]) <= d.hh && abs(d.dw[t]) <= d.hw, "bsed_igemm3: tap %d outside the halo", t);
   BSED_CHECK_ARG(d.in_pitch >= d.CIN && d.in_pitch % 4 == 0 && d.out_pitch >= d.N, "bsed_igemm3: bad pitch");
   BSED_CHECK_ARG(d.NP % 32 == 0 && d.NP >= d.N, "bsed_igemm3: NP must be N rounded up to 32");
-  int BN = d.NP % 128 == 0 ? 128 : (d.NP % 64 == 0 ? 64 : 32);
-  {  // A/B knob: BSED_IGEMM3_BN=64 runs the 128-channel layers as two 64-channel workgroups per tile
-    static const int bn_cap = getenv("BSED_IGEMM3_BN") ? atoi(getenv("BSED_IGEMM3_BN")) : 128;
-    if (RB == 1 && BN > bn_cap && (bn_cap == 64 || bn_cap == 32)) BN = bn_cap;
-  }
-  BSED_CHECK_ARG(RB == 1 || BN == 128, "bsed_igemm3: 256-position tiles are built for N a multiple of 128");
+  const int BN = d.NP % 128 == 0 ? 128 : (d.NP % 64 == 0 ? 64 : 32);
   d.tilesH = ceil_div(d.H, d.TH);
   d.tilesW = d.W / d.TW;
   P.PW = d.TW + 2 * d.hw;
@@ -717,10 +683,9 @@ extern "C" int bsed_igemm3(const BsedIgemmDesc* desc, void* stream) {
   dim3 grid((unsigned)ntiles, d.NP / BN);
   hipStream_t s = (hipStream_t)stream;
   const bool st = d.epilogue == BSED_EPI_STATS;
-  if (BN == 128 && RB == 2) return st ? launch_i3<128, 1, 2>(P, grid, bytes, s) : launch_i3<128, 0, 2>(P, grid, bytes, s);
-  if (BN == 128) return st ? launch_i3<128, 1, 1>(P, grid, bytes, s) : launch_i3<128, 0, 1>(P, grid, bytes, s);
-  if (BN == 64) return st ? launch_i3<64, 1, 1>(P, grid, bytes, s) : launch_i3<64, 0, 1>(P, grid, bytes, s);
-  return st ? launch_i3<32, 1, 1>(P, grid, bytes, s) : launch_i3<32, 0, 1>(P, grid, bytes, s);
+  if (BN == 128) return st ? launch_i3<128, 1>(P, grid, bytes, s) : launch_i3<128, 0>(P, grid, bytes, s);
+  if (BN == 64) return st ? launch_i3<64, 1>(P, grid, bytes, s) : launch_i3<64, 0>(P, grid, bytes, s);
+  return st ? launch_i3<32, 1>(P, grid, bytes, s) : launch_i3<32, 0>(P, grid, bytes, s);
 }
 
 // ---- CIN = 16 variant: w = bsed_pack_weight3s table; persistent grid of G workgroups per 32 output channels;
@@ -736,17 +701,10 @@ extern "C" int bsed_pack_weight3s(const float* src, void* dst, int ntaps, int K,
   return BSED_OK;
 }
 
-extern "C" int bsed_igemm3s_auto_g(void) {
-  const char* v = getenv("BSED_IGEMM3S_G");   // A/B knob
-  return v && atoi(v) > 0 ? atoi(v) : 1024;
-}
+extern "C" int bsed_igemm3s_auto_g(void) { return 1024; }
 // per shape: the 32 -> 16 channel data gradient (half-width weight table, 52 KB of LDS) runs three workgroups per CU:
 // 768 / 1024 / 1536 workgroups 0.380 / 0.452 / 0.384 ms; the 16 -> 32 forward four: 0.406 / 0.365 / 0.409
-extern "C" int bsed_igemm3s_auto_g2(int CIN, int N) {
-  const char* v = getenv("BSED_IGEMM3S_G");
-  if (v && atoi(v) > 0) return atoi(v);
-  return (CIN == 32 && N <= 16) ? 768 : 1024;
-}
+extern "C" int bsed_igemm3s_auto_g2(int CIN, int N) { return (CIN == 32 && N <= 16) ? 768 : 1024; }
 
 extern "C" int bsed_igemm3s(const BsedIgemmDesc* desc, int G, void* stream) {
   BSED_CHECK_ARG(desc, "bsed_igemm3s: null descriptor");

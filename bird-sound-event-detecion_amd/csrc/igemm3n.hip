@@ -36,21 +36,6 @@ struct Igemm3nParams {
   int PW, PH, PP, lgTW, b_off, pw_magic, prio;
 };
 
-// Diagnostic build (-DI3N_STAMP, tools/build_variant.sh): s_memtime stamps of one wave's phases go to the buffer passed
-// in desc.e_src ([tile][wave][20] uint64, 16 / 17 = s_memrealtime at start / end, 18 / 19 = HW_ID / XCC_ID; no output value depends on them)
-#ifdef I3N_STAMP
-#define I3N_T(i)                                                                                         \
-  do {                                                                                                   \
-    __builtin_amdgcn_sched_barrier(0);                                                                   \
-    unsigned long long t__;                                                                              \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t__)::"memory");                          \
-    __builtin_amdgcn_sched_barrier(0);                                                                   \
-    if (lane == 0) stampbuf[i] = t__;                                                                    \
-  } while (0)
-#else
-#define I3N_T(i)
-#endif
-
 __device__ __forceinline__ int crow3n(int r, int lh) { return (r & 3) + 8 * (r >> 2) + 4 * lh; }
 
 // NWN = waves along N (each 32 channels): 4 -> BN = 128, a wave covers all four 32-row blocks of the tile;
@@ -90,19 +75,6 @@ void igemm3n_kernel(const Igemm3nParams P) {
     const int nt = gridDim.x, bid = blockIdx.x, q = nt >> 3, r = nt & 7, x = bid & 7;
     tile = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
   }
-#ifdef I3N_STAMP
-  unsigned long long* stampbuf = (unsigned long long*)p.e_src + ((size_t)tile * 4 + wave) * 20;
-#endif
-  I3N_T(0);
-#ifdef I3N_STAMP
-  if (lane == 0) stampbuf[16] = __builtin_amdgcn_s_memrealtime();
-  {
-    unsigned hwid, xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    if (lane == 0) { stampbuf[18] = hwid; stampbuf[19] = xcc; }
-  }
-#endif
   const int tw_i = tile % p.tilesW; tile /= p.tilesW;
   const int th_i = tile % p.tilesH;
   const int nb = tile / p.tilesH;
@@ -204,7 +176,6 @@ void igemm3n_kernel(const Igemm3nParams P) {
   // own iteration.  Either way: ONE barrier per chunk.  Buffer (ch + 1) & 1 was last read during chunk ch - 1, and
   // every wave has passed the barrier at the top of chunk ch since.
   constexpr bool EARLYW = NT9 != 0;
-  I3N_T(1);
   if (EARLYW) {
 #pragma unroll
     for (int u = 0; u < PV; ++u) write_piece(u, smem3n);
@@ -217,9 +188,7 @@ void igemm3n_kernel(const Igemm3nParams P) {
 #pragma unroll
       for (int u = 0; u < PV; ++u) write_piece(u, As);
     }
-    if (ch < 4) I3N_T(2 + 3 * ch);
     __syncthreads();   // the ONE barrier of the chunk: patch visible; everyone is out of chunk ch - 1
-    if (ch < 4) I3N_T(3 + 3 * ch);
     if (PRIO && ch == 0) __builtin_amdgcn_s_setprio(0);
     if (!EARLYW && more) {
 #pragma unroll
@@ -302,7 +271,6 @@ void igemm3n_kernel(const Igemm3nParams P) {
     } else {
       for (int tap = 0; tap < ntaps; ++tap) step(tap);
     }
-    if (ch < 4) I3N_T(4 + 3 * ch);
   };
   for (int ch = 0; ch < nchunks - 1; ++ch) chunk(ch, std::true_type{});
   chunk(nchunks - 1, std::false_type{});
@@ -407,25 +375,15 @@ void igemm3n_kernel(const Igemm3nParams P) {
       p.stats[(row * 2 + 1) * p.N + n] = b;
     }
   }
-  I3N_T(14);
-#ifdef I3N_STAMP
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  I3N_T(15);
-  if (lane == 0) stampbuf[17] = __builtin_amdgcn_s_memrealtime();
-#endif
 }
 
-// MFMA shape of the nine-tap instances (and of the two-wave BN = 128 builds of the 1 - 4 tap forms): 16 = 16 x 16 x 32 (default with fp32 activations: 8-16 % faster per layer,
-// tools/conv_ab.py), 32 = 32 x 32 x 16 (default with bf16 activations, where the 16 form's extra registers spill at
-// three waves per SIMD and the step is not matrix-bound).  BSED_IGEMM3N_SHAPE=16 / 32 forces one (A/B knob).
-static std::atomic<int> i3n_forced_shape{-1};
+// MFMA shape of the nine-tap instances (and of the two-wave BN = 128 builds of the 1 - 4 tap forms): 16 = 16 x 16 x 32 (default with fp32 activations: 8-16 % faster per layer),
+// 32 = 32 x 32 x 16 (default with bf16 activations, where the 16 form's extra registers spill at
+// three waves per SIMD and the step is not matrix-bound).  bsed_igemm3n_set_shape(16 / 32) forces one (tests).
+static std::atomic<int> i3n_forced_shape{0};
 extern "C" void bsed_igemm3n_set_shape(int shape) { i3n_forced_shape.store(shape == 16 || shape == 32 ? shape : 0); }
 static int i3n_shape16(int abf) {
-  int v = i3n_forced_shape.load();
-  if (v < 0) {
-    v = getenv("BSED_IGEMM3N_SHAPE") ? atoi(getenv("BSED_IGEMM3N_SHAPE")) : 0;
-    i3n_forced_shape.store(v);
-  }
+  const int v = i3n_forced_shape.load();
   return v ? v == 16 : !abf;
 }
 template <int NWN, int MW, int STATS, int PV, int NT9, int WPE, int ABF = 0>
@@ -446,18 +404,11 @@ static int launch_i3n6(const Igemm3nParams& P, dim3 grid, size_t smem, hipStream
   return BSED_OK;
 }
 
-// A/B knob (bsed_igemm3n_set_wpe, BSED_IGEMM3N_WPE): 2 / 3 = the BN = 128 build for that many waves per SIMD (256 / 168
-// registers) whatever the shape; + 8 = no raised priority outside the loop; 0 = default
-static std::atomic<int> i3n_forced_wpe{-1};
+// bsed_igemm3n_set_wpe (tests): 2 / 3 = the BN = 128 build for that many waves per SIMD (256 / 168 registers) whatever
+// the shape; + 8 = no raised priority outside the loop; 0 = default
+static std::atomic<int> i3n_forced_wpe{0};
 extern "C" void bsed_igemm3n_set_wpe(int wpe) { i3n_forced_wpe.store(wpe); }
-static int i3n_knob() {
-  int forced = i3n_forced_wpe.load();
-  if (forced < 0) {
-    forced = getenv("BSED_IGEMM3N_WPE") ? atoi(getenv("BSED_IGEMM3N_WPE")) : 0;
-    i3n_forced_wpe.store(forced);
-  }
-  return forced;
-}
+static int i3n_knob() { return i3n_forced_wpe.load(); }
 
 // which build runs a (BN, patch size, taps) combination (PV = 0: unsupported patch size)
 struct I3nPlan { int NWN, MW, PV, WPE; };
@@ -474,7 +425,7 @@ static I3nPlan i3n_plan(int NP, int PP, int ntaps, int abf) {
   pl.PV = need <= 6 ? 6 : (need <= 9 ? 9 : 0);
   // BN = 128: three waves per SIMD (168 registers) only for the shape that fits them without spilling in the loop
   // (nine taps, patch of <= 192 positions): 339 vs 359 us on the 216 x 8 layer; two otherwise (PV = 9: 173 vs 192 us
-  // on the 216 x 4 layer).  tools/conv_ab.py
+  // on the 216 x 4 layer).
   // (the 16 x 16 x 32 form needs ~185 registers at BN = 128: two waves per SIMD, where it is 8-12 % faster than the
   //  32 x 32 x 16 form at three)
   if (NWN == 4) pl.WPE = wpe == 2 || wpe == 3 ? wpe : ((pl.PV == 6 && ntaps == 9 && !i3n_shape16(abf)) ? 3 : 2);

@@ -33,15 +33,9 @@
 
 #define NFFT 2048
 #define NC 1024        // complex points
-#ifndef SM_WAVES
 #define SM_WAVES 4     // waves per workgroup (independent of each other until the final partial-sum hand-off)
-#endif
-#ifndef SM_FPW
 #define SM_FPW 8       // consecutive frames per wave
-#endif
-#ifndef SM_WPE
 #define SM_WPE 2       // waves per SIMD the register budget is held to
-#endif
 #define SM_PITCH 68    // exchange tile: row pitch in complex elements (16 rows x 64 + 4 pad)
 #define SM_TILE_FLOATS (2 * 16 * SM_PITCH)   // 8704 B per wave: exchange tile / Z image (1024 + 12 pad) / 1028 magnitudes
 #define SM_MAX_NIT 24  // float4 filterbank steps per lane (both bands)
@@ -172,25 +166,14 @@ __global__ __launch_bounds__(MEL_THREADS, SM_WPE) void stft_mel_kernel(const SmP
     const float2 ww = *reinterpret_cast<const float2*>(P.window + 2 * i);
     wins[i] = c32{ww.x, ww.y};
   }
-  // per-lane constants (registers for the whole kernel).  Twiddle k = 4a + b is held as the two factors
-  // W^(lane 4a) and W^(lane b) (6 complex numbers instead of 15 per pass; one extra multiply for a, b != 0)
-#if SM_WPE <= 2
-  // 256-register budget: all 15 + 15 twiddles of the two passes stay in registers
+  // per-lane constants (registers for the whole kernel).  256-register budget: all 15 + 15 twiddles of the two passes
+  // stay in registers
   c32 tw1[15], tw2[15];
 #pragma unroll
   for (int k = 0; k < 15; ++k) {
     const float2 a = P.tw1[k * 64 + lane], c = P.tw2[k * 64 + lane];
     tw1[k] = c32{a.x, a.y}; tw2[k] = c32{c.x, c.y};
   }
-#else
-  c32 t1a[3], t1b[3], t2a[3], t2b[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const float2 a1 = P.tw1[(4 * (i + 1) - 1) * 64 + lane], b1 = P.tw1[i * 64 + lane];
-    const float2 a2 = P.tw2[(4 * (i + 1) - 1) * 64 + lane], b2 = P.tw2[i * 64 + lane];
-    t1a[i] = c32{a1.x, a1.y}; t1b[i] = c32{b1.x, b1.y}; t2a[i] = c32{a2.x, a2.y}; t2b[i] = c32{b2.x, b2.y};
-  }
-#endif
   const float2 wl2 = P.wl[lane];
   const c32 wl = c32{wl2.x, wl2.y};
   const int4 mi = P.melidx[lane];
@@ -246,30 +229,14 @@ __global__ __launch_bounds__(MEL_THREADS, SM_WPE) void stft_mel_kernel(const SmP
     const int t = t_begin + f;
     if (t >= P.T) break;                             // wave-uniform
     asm volatile("" : "+v"(opq));
-#if SM_WPE <= 2
     const c32 wlo = wl;                              // the eight W2048^k of the unpack are hoisted into registers too
-#else
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {                    // the nine twiddle products below are recomputed per frame, not hoisted
-      asm volatile("" : "+v"(t1a[i].x), "+v"(t1a[i].y));
-      asm volatile("" : "+v"(t2a[i].x), "+v"(t2a[i].y));
-    }
-    c32 wlo = wl;                                    // likewise the eight W2048^k of the unpack
-    asm volatile("" : "+v"(wlo.x), "+v"(wlo.y));
-#endif
 #pragma unroll
     for (int j = 0; j < 16; ++j) v[j] *= wins[opq + lane + 64 * j];   // window from LDS (read per frame: 32 registers saved)
     // ---- pass 1: 16-point DFT over j of z[l + 64 j], twiddle W1024^(l k1)
     dft16(v);
 #pragma unroll
     for (int k = 1; k < 16; ++k) {
-#if SM_WPE <= 2
       v[k] = cmulw(v[k], tw1[k - 1]);
-#else
-      const int a = k >> 2, bb = k & 3;
-      const c32 tw = a == 0 ? t1b[bb - 1] : (bb == 0 ? t1a[a - 1] : cmulw(t1a[a - 1], t1b[bb - 1]));
-      v[k] = cmulw(v[k], tw);
-#endif
     }
     SM_FENCE();
 #pragma unroll
@@ -282,13 +249,7 @@ __global__ __launch_bounds__(MEL_THREADS, SM_WPE) void stft_mel_kernel(const SmP
     dft16(v);
 #pragma unroll
     for (int k = 1; k < 16; ++k) {
-#if SM_WPE <= 2
       v[k] = cmulw(v[k], tw2[k - 1]);
-#else
-      const int a = k >> 2, bb = k & 3;
-      const c32 tw = a == 0 ? t2b[bb - 1] : (bb == 0 ? t2a[a - 1] : cmulw(t2a[a - 1], t2b[bb - 1]));
-      v[k] = cmulw(v[k], tw);
-#endif
     }
     // ---- pass 3: 4-point DFT across the quad's lanes; lane m ends with output q(m): k = g + 16 k2' + 256 q
 #pragma unroll
@@ -398,34 +359,9 @@ __global__ __launch_bounds__(MEL_THREADS, SM_WPE) void stft_mel_kernel(const SmP
 // ---------------------------------------------------------------------------------------------
 #define S2_WAVES 8
 #define S2_THREADS (64 * S2_WAVES)
-#ifndef S2_FPW
 #define S2_FPW 16             // consecutive frames per wave (pairs: S2_FPW / 2)
-#endif
 #define S2_TILE_ELEMS 1088    // float4 elements per wave (16 exchange rows of pitch 68)
-#ifndef S2_FB_UNROLL
 #define S2_FB_UNROLL 4
-#endif
-#ifndef S2_TIMING
-#define S2_TIMING 0     // 1: one wave prints the cycles it spent in each phase of a frame pair (tools/mel_pair_ab.py prof)
-#endif
-#if S2_TIMING
-#define S2_STAMP(i) do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); const unsigned long long now_ = __builtin_amdgcn_s_memtime(); \
-                         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); ph[i] += (unsigned)(now_ - last_); last_ = now_; } while (0)
-#else
-#define S2_STAMP(i) do {} while (0)
-#endif
-#ifndef S2_EARLY_PREFETCH
-#define S2_EARLY_PREFETCH 1
-#endif
-#ifndef S2_STAGGER
-#define S2_STAGGER 0
-#endif
-#ifndef S2_DFT_SB
-#define S2_DFT_SB 1
-#endif
-#ifndef S2_TW1_FACTORED
-#define S2_TW1_FACTORED 1
-#endif
 #define S2_ROW(k) ((k) * 68)
 
 typedef float p2 __attribute__((ext_vector_type(2)));   // one quantity of frames (t, t+1)
@@ -445,11 +381,7 @@ __device__ __forceinline__ cp mul_w8_3(cp a, p2 R) { return cp{(a.im - a.re) * R
 __device__ __forceinline__ f4 pack4(cp a) { return f4{a.re.x, a.re.y, a.im.x, a.im.y}; }
 __device__ __forceinline__ cp unpack4(f4 a) { return cp{p2{a.x, a.y}, p2{a.z, a.w}}; }
 
-#if S2_DFT_SB
 #define S2_SB() __builtin_amdgcn_sched_barrier(0)   // one radix-4 column at a time: bounds the live temporaries
-#else
-#define S2_SB() do {} while (0)
-#endif
 // dft16 of stft_mel_kernel on frame pairs (same operation order per frame)
 __device__ __forceinline__ void dft16(cp (&v)[16]) {
   const float C1 = 0.92387953251128674f, S1 = 0.38268343236508977f;
@@ -504,7 +436,6 @@ __global__ __launch_bounds__(S2_THREADS, 2) void stft_mel2_kernel(const SmParams
   // padded filterbank steps (zero weights) may read any word of the tile: none may hold a NaN pattern
   for (int i = lane; i < S2_TILE_ELEMS; i += 64) xt[i] = f4{0.f, 0.f, 0.f, 0.f};
   // W1024^(lane k) in registers; W64^((lane & 3) k) depends on the lane's place in its quad only: a 15 x 4 LDS table
-#if S2_TW1_FACTORED
   // twiddle k = 4 a + b as the two factors W^(lane 4 a), W^(lane b): 6 complex numbers instead of 15 (the nine products
   // are recomputed per pair: 36 scalar operations against 24 registers)
   c32 t1a[3], t1b[3];
@@ -513,14 +444,6 @@ __global__ __launch_bounds__(S2_THREADS, 2) void stft_mel2_kernel(const SmParams
     const float2 a1 = P.tw1[(4 * (i + 1) - 1) * 64 + lane], b1 = P.tw1[i * 64 + lane];
     t1a[i] = c32{a1.x, a1.y}; t1b[i] = c32{b1.x, b1.y};
   }
-#else
-  c32 tw1[15];
-#pragma unroll
-  for (int k = 0; k < 15; ++k) {
-    const float2 a = P.tw1[k * 64 + lane];
-    tw1[k] = c32{a.x, a.y};
-  }
-#endif
   if (tid < 60) {
     const float2 c = P.tw2[(tid >> 2) * 64 + (tid & 3)];
     tw2s[tid] = c32{c.x, c.y};
@@ -583,16 +506,6 @@ __global__ __launch_bounds__(S2_THREADS, 2) void stft_mel2_kernel(const SmParams
     if (interior(ta) && interior(tb)) load_fast(ta, tb); else load_edge(ta, tb);
   };
   if (t_begin < P.T) load_pair(t_begin);
-#if S2_STAGGER
-  // the eight waves of a workgroup start together and would run every phase (VALU / LDS / loads) in step, queueing on
-  // one resource while the others idle: start wave w  w * S2_STAGGER cycles late
-  for (int i = 0; i < wv * (S2_STAGGER / 64); ++i) __builtin_amdgcn_s_sleep(1);
-#endif
-#if S2_TIMING
-  unsigned ph[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long last_ = __builtin_amdgcn_s_memtime();
-  const unsigned long long first_ = last_;
-#endif
 #pragma unroll 1
   for (int f = 0; f < S2_FPW; f += 2) {
     const int t = t_begin + f;
@@ -601,10 +514,8 @@ __global__ __launch_bounds__(S2_THREADS, 2) void stft_mel2_kernel(const SmParams
     asm volatile("" : "+v"(opq));
     c32 wlo = wl;                                    // the eight W2048^k of the unpack are recomputed per pair, not hoisted
     asm volatile("" : "+v"(wlo.x), "+v"(wlo.y));
-#if S2_TW1_FACTORED
 #pragma unroll
     for (int i = 0; i < 3; ++i) asm volatile("" : "+v"(t1a[i].x), "+v"(t1a[i].y));   // likewise the nine twiddle products
-#endif
     cp v[16];
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
@@ -615,30 +526,15 @@ __global__ __launch_bounds__(S2_THREADS, 2) void stft_mel2_kernel(const SmParams
       asm("v_swap_b32 %0, %1" : "+v"(xa[j].y), "+v"(xb[j].x));             // -> (even_t, even_t+1), (odd_t, odd_t+1)
       v[j] = cp{xa[j], xb[j]};
     }
-#if S2_TIMING
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-    for (int j = 0; j < 16; ++j) asm volatile("" :: "v"(v[j].re), "v"(v[j].im));
-#endif
-    S2_STAMP(0);
     // ---- pass 1
     dft16(v);
 #pragma unroll
     for (int k = 1; k < 16; ++k) {
-#if S2_TW1_FACTORED
       const int a = k >> 2, bb = k & 3;
       const c32 tw = a == 0 ? t1b[bb - 1] : (bb == 0 ? t1a[a - 1] : cmulw(t1a[a - 1], t1b[bb - 1]));
       v[k] = cmulw(v[k], tw);
-#else
-      v[k] = cmulw(v[k], tw1[k - 1]);
-#endif
     }
     SM_FENCE();
-#if S2_TIMING
-#pragma unroll
-    for (int j = 0; j < 16; ++j) asm volatile("" :: "v"(v[j].re), "v"(v[j].im));
-#endif
-    S2_STAMP(1);
 #pragma unroll
     for (int k = 0; k < 16; ++k) xt[S2_ROW(k) + lane] = pack4(v[k]);
     SM_FENCE();
@@ -649,16 +545,9 @@ __global__ __launch_bounds__(S2_THREADS, 2) void stft_mel2_kernel(const SmParams
       for (int j = 0; j < 16; ++j) v[j] = unpack4(row[4 * j]);
     }
     SM_FENCE();
-    S2_STAMP(2);
     dft16(v);
 #pragma unroll
     for (int k = 1; k < 16; ++k) v[k] = cmulw(v[k], tw2s[opq + 4 * (k - 1) + m]);
-#if S2_TIMING
-#pragma unroll
-    for (int j = 0; j < 16; ++j) asm volatile("" :: "v"(v[j].re), "v"(v[j].im));
-    __builtin_amdgcn_sched_barrier(0);
-#endif
-    S2_STAMP(3);
     // ---- pass 3: 4-point DFT across the quad's lanes
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
@@ -668,16 +557,7 @@ __global__ __launch_bounds__(S2_THREADS, 2) void stft_mel2_kernel(const SmParams
       r.re = m3 ? rr.re : r.re; r.im = m3 ? rr.im : r.im;
       o = cp{quad_dpp2<0xB1>(r.re), quad_dpp2<0xB1>(r.im)};                        // lane ^ 1
       v[k] = cp{r.re * sgn1 + o.re, r.im * sgn1 + o.im};
-#ifdef S2_SB_DPP
-      if ((k & (S2_SB_DPP - 1)) == S2_SB_DPP - 1) __builtin_amdgcn_sched_barrier(0);   // bounds the live temporaries of the stage
-#endif
     }
-#if S2_TIMING
-#pragma unroll
-    for (int j = 0; j < 16; ++j) asm volatile("" :: "v"(v[j].re), "v"(v[j].im));
-    __builtin_amdgcn_sched_barrier(0);
-#endif
-    S2_STAMP(4);
     // ---- Z image: element k at k + 4 (k >> 8)
 #pragma unroll
     for (int k = 0; k < 16; ++k) xt[g + 16 * k + 260 * q] = pack4(v[k]);
@@ -688,9 +568,7 @@ __global__ __launch_bounds__(S2_THREADS, 2) void stft_mel2_kernel(const SmParams
     const bool more = f + 2 < S2_FPW && t + 2 < P.T;
     const int tn = t + 2, tnb = t + 3 < P.T ? t + 3 : t + 2;
     const bool fast = more && interior(tn) && interior(tnb);
-#if S2_EARLY_PREFETCH
     if (fast) load_fast(tn, tnb);
-#endif
     // ---- real-FFT unpack on pairs (k, 1024 - k), k = lane + 64 i
     p2 mg_lo[8], mg_hi[8];
     const f4* xt_rev = xt + (1036 - (64 * 7 + 4)) - lane;
@@ -712,12 +590,6 @@ __global__ __launch_bounds__(S2_THREADS, 2) void stft_mel2_kernel(const SmParams
     const p2 s512 = z512.re * z512.re + z512.im * z512.im;
     const p2 mg512 = p2{__builtin_amdgcn_sqrtf(s512.x), __builtin_amdgcn_sqrtf(s512.y)};
     SM_FENCE();
-#if S2_TIMING
-#pragma unroll
-    for (int i = 0; i < 8; ++i) asm volatile("" :: "v"(mg_lo[i]), "v"(mg_hi[i]));
-    __builtin_amdgcn_sched_barrier(0);
-#endif
-    S2_STAMP(5);
     // ---- magnitudes over the tile, (t, t+1) pairs per bin (1025 + 3 zero pad)
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
@@ -727,10 +599,6 @@ __global__ __launch_bounds__(S2_THREADS, 2) void stft_mel2_kernel(const SmParams
     if (lane == 0) mg2[512] = mg512;
     if (lane >= 1 && lane <= 3) mg2[NC + lane] = bc(0.f);
     SM_FENCE();
-    S2_STAMP(6);
-#if !S2_EARLY_PREFETCH
-    if (fast) load_fast(tn, tnb);                    // next pair's samples travel while the filterbank runs
-#endif
     // ---- sparse filterbank: two bands per lane, four bins of both frames per step
     p2 acc0 = bc(0.f), acc1 = bc(0.f);
     const f4* m0 = reinterpret_cast<const f4*>(mg2 + mi.x);
@@ -751,11 +619,6 @@ __global__ __launch_bounds__(S2_THREADS, 2) void stft_mel2_kernel(const SmParams
       acc1 = bc(ww.x) * p2{ma.x, ma.y} + (bc(ww.y) * p2{ma.z, ma.w} + (bc(ww.z) * p2{mb.x, mb.y} + (bc(ww.w) * p2{mb.z, mb.w} + acc1)));
     }
     SM_FENCE();
-#if S2_TIMING
-    asm volatile("" :: "v"(acc0), "v"(acc1));
-    __builtin_amdgcn_sched_barrier(0);
-#endif
-    S2_STAMP(7);
     float* out = P.mel_out + ((size_t)b * P.T + t) * P.n_mels;
     if (has0) {
       out[band0] = acc0.x; run_max = fmaxf(run_max, acc0.x);
@@ -768,13 +631,7 @@ __global__ __launch_bounds__(S2_THREADS, 2) void stft_mel2_kernel(const SmParams
       sq1 = acc1 * acc1 + sq1;
     }
     if (more && !fast) load_edge(tn, tnb);
-    S2_STAMP(8);
   }
-#if S2_TIMING
-  if (lane == 0 && blockIdx.y == 77 && (blockIdx.x == 2 || blockIdx.x == 5) && (wv == 1 || wv == 6))
-    printf("wave (%d,%d,%d): total %u | load+window %u dft1 %u exch %u dft2 %u dpp %u zwrite+unpack %u mags %u filterbank %u store %u\n",
-           blockIdx.x, blockIdx.y, wv, (unsigned)(last_ - first_), ph[0], ph[1], ph[2], ph[3], ph[4], ph[5], ph[6], ph[7], ph[8]);
-#endif
   const float wm = wave_max(run_max);
   if (lane == 0 && t_begin < P.T) atomicMax(reinterpret_cast<int*>(P.clip_max + b), __float_as_int(wm));
   SM_FENCE();
@@ -994,7 +851,7 @@ extern "C" int bsed_mel_plan_destroy(void* plan) {
 extern "C" int bsed_mel_plan_nnz(const void* plan) { return plan ? ((const MelPlan*)plan)->nnz : -1; }
 
 // two frames per wave (stft_mel2_kernel) whenever its tiles fit the CU's LDS and its padded filterbank steps stay
-// inside a wave's tile; BSED_MEL_PAIR=0 keeps the one-frame-per-wave kernel (A/B runs)
+// inside a wave's tile; BSED_MEL_PAIR=0 keeps the one-frame-per-wave kernel (tests)
 static size_t mel_pair_smem(const MelPlan* p) {
   return (size_t)p->nit * 64 * sizeof(float4) + (NC / 2 + 64) * sizeof(float2) + (size_t)S2_WAVES * S2_TILE_ELEMS * sizeof(f4);
 }

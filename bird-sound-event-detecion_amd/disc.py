@@ -102,8 +102,7 @@ class Clip_Discriminator(_FlatModule):
         # The mask sensitivity is a property of the FORWARD contractions only (the masks are functions of the forward
         # pre-activations): the data-gradient GEMMs of the backward pass contract given operands, where split-fp32 costs
         # its usual 2^-16 and nothing is amplified.  They therefore run on the bf16 cores by default (the weight
-        # gradients always did): -2 ms per adversarial step at B = 128 + 128.  BSED_DISC_BWD_MODE=fp32 for A/B runs.
-        self.bwd_mode = os.environ.get("BSED_DISC_BWD_MODE", "bf16x3")
+        # gradients always did): -2 ms per adversarial step at B = 128 + 128.
         self.nbt = torch.zeros(5, device=device, dtype=torch.int64)
         for k in range(1, 6):
             self.P(f"bn_{k}").register_buffer("num_batches_tracked", self.nbt[k - 1])
@@ -270,21 +269,17 @@ class Clip_Discriminator(_FlatModule):
                 # the BatchNorm-backward map is affine: it left non-zero values on the grid's non-output row / column
                 dy[:, l["Ho"]:, :, :] = 0
                 dy[:, :, l["Wo"]:, :] = 0
-                part, G, KP, NP = ops.wgrad(l["xp"], dy, N, Hp, Wp, K, co, taps=TAPS2x2)
+                part, G, KP, NP = ops.wgrad(l["xp"], dy, N, Hp, Wp, K, co, taps=TAPS2x2, mode="bf16x3")
                 tmp = torch.empty((4, K, co), device=dy.device, dtype=torch.float32)
                 ops.reduce_partials(part, G, 4, KP, NP, K, co, tmp, K * co, co, 1, accumulate=False, defer=False)
                 w.grad.add_(tmp.view(16, cin, co)[_S2D_SLOT].permute(2, 1, 0).reshape(co, cin, 3, 3))
                 flipped = [(-a, -b) for a, b in TAPS2x2]
-                if self.conv_mode == "bf16x3" or self.bwd_mode == "bf16x3":
-                    wd3 = ops.pack_weight3(l["wfull"], 4, co, K, K * co, 1, co)
-                    dxp, _ = ops.igemm3(dy, wd3, K, N, Hp, Wp, co, flipped)
-                else:
-                    wd = ops.pack_weight(l["wfull"], 4, co, K, K * co, 1, co)
-                    dxp, _ = ops.igemm(dy, wd, K, N, Hp, Wp, co, taps=flipped)
+                wd3 = ops.pack_weight3(l["wfull"], 4, co, K, K * co, 1, co)
+                dxp, _ = ops.igemm3(dy, wd3, K, N, Hp, Wp, co, flipped)
                 g, stats = _s2d_bwd(dxp, p["y"], p["scale"], p["shift"], N, l["Ha_in"], l["Wa_in"], l["Hi"], l["Wi"], cin)
                 continue
             dy = g.view(l["M"], co)
-            part, G, KP, NP = ops.wgrad(l["col"], dy, 1, l["M"], 1, l["K"], co)
+            part, G, KP, NP = ops.wgrad(l["col"], dy, 1, l["M"], 1, l["K"], co, mode="bf16x3")
             if cin == 1:
                 ops.reduce_partials(part, G, 1, KP, NP, 9, co, w.grad, 0, 1, 9)
             else:
@@ -295,7 +290,7 @@ class Clip_Discriminator(_FlatModule):
                 dyp = torch.zeros((l["M"], cop), device=dy.device, dtype=torch.float32)
                 dyp[:, :co] = dy
                 dy = dyp
-            if (self.conv_mode == "bf16x3" or self.bwd_mode == "bf16x3") and cop % 32 == 0:
+            if cop % 32 == 0:
                 w3 = ops.pack_weight3(wT, 1, cop, K, 0, wT.shape[2], 1)
                 dcol, _ = ops.igemm3(dy, w3, K, 1, l["M"], 1, cop, ((0, 0),))
             else:
@@ -362,7 +357,7 @@ class Frame_Discriminator(_FlatModule):
         """accumulates dW, db of y = x W^T + b; returns dL/dx (M,K)"""
         w, b = self.P(name + ".weight"), self.P(name + ".bias")
         ops.colsum(dy, M, N, N, b.grad)
-        part, G, KP, NP = ops.wgrad(x, dy, 1, M, 1, K, N)
+        part, G, KP, NP = ops.wgrad(x, dy, 1, M, 1, K, N, mode="bf16x3")
         ops.reduce_partials(part, G, 1, KP, NP, K, N, w.grad, 0, 1, K)
         if self.conv_mode == "bf16x3":
             return ops.igemm3(dy, ops.pack_weight3(w, 1, N, K, 0, K, 1), K, 1, M, 1, N, ((0, 0),))[0]

@@ -18,7 +18,6 @@ the optimizer kernel.
 """
 import numpy as np
 import ctypes
-import os
 
 import torch
 
@@ -227,14 +226,13 @@ class SEDTrainer:
         self.pg = process_group
         self._prefetched, self._feat_stream = {}, None   # train_step(..., next_waves=...): features one step ahead
         self._uploaded, self._copy_stream, self._slots = {}, None, {}   # host waveforms: uploads one step ahead
-        # mean teacher: the EMA pair's forward on its own stream beside the student's passes (BSED_TEACHER_OVERLAP=0: inline)
-        self.teacher_overlap = os.environ.get("BSED_TEACHER_OVERLAP", "1") != "0"
+        # mean teacher: the EMA pair's forward on its own stream beside the student's passes (False: inline)
+        self.teacher_overlap = True
         self._teacher_stream = None
-        self.step_priority = os.environ.get("BSED_STEP_PRIORITY", "1") != "0"
         self._step_stream = None
         # the packed weight copies a step needs, made in ONE launch at its start from the second step on
-        # (ops.PackPlan; BSED_PACK_PLAN=0: one launch per weight at first use, the pre-plan behaviour)
-        self._pack_plans = {} if os.environ.get("BSED_PACK_PLAN", "1") != "0" else None
+        # (ops.PackPlan; None: one launch per weight at first use, the pre-plan behaviour)
+        self._pack_plans = {}
         self.world = 1
         self.rank = 0
         if process_group is not None or (torch.distributed.is_available() and torch.distributed.is_initialized()):
@@ -360,12 +358,12 @@ class SEDTrainer:
         """One iteration (see ``_train_step`` for the arguments).  With the EMA teacher on its own stream the step itself
         runs on a HIGH-PRIORITY stream of the trainer: the teacher's forward (normal priority) then fills the CUs the
         student's passes leave idle instead of taking turns with them -- 17.23 -> 16.96 ms per mean-teacher step at
-        B = 128 + 128, same kernels in the same per-stream order: same bits.  The caller's stream waits for the step
-        (``BSED_STEP_PRIORITY=0``: run on the caller's stream; torch offers no priority BELOW the default one, so the
-        side streams cannot be lowered instead).  Without a teacher stream the step stays on the caller's stream
+        B = 128 + 128 (against the caller's stream), same kernels in the same per-stream order: same bits.  The caller's
+        stream waits for the step (torch offers no priority BELOW the default one, so the side streams cannot be
+        lowered instead).  Without a teacher stream the step stays on the caller's stream
         (measured: no gain for the plain step, 13.48-13.50 vs 13.52-13.53 ms)."""
         mt = self.ema_crnn is not None and real_x is not None
-        if not (mt and self.teacher_overlap and self.step_priority):
+        if not (mt and self.teacher_overlap):
             return self._train_step(syn_x, syn_y, real_x, real_y_weak, real_x_ema, consistency_cost, from_wave, next_waves)
         caller = torch.cuda.current_stream()
         if self._step_stream is None:

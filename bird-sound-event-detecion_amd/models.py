@@ -171,7 +171,6 @@ class CRNN(_FlatModule):
         self.n_hidden = n_RNN_cell
         self.seed = 0
         self.fused_glu_bwd = True  # False = the unfused 4-launch chain (kept as a cross-check in the tests)
-        self.glu3 = os.environ.get("BSED_GLU3", "1") != "0"  # split-fp32 GLU kernels (csrc/glu3.hip)
         # GRU weight gradients of layer l on a side stream, beside the (latency-bound, half-chip) recurrence of layer
         # l-1: -0.26 ms per step at B = 256 (14.07 -> 13.81 ms), bitwise identical results (tests/test_fullsize_gpu.py).
         # The overlapped 1-tap weight gradients are stretched by the recurrence they share the chip with (0.076 ->
@@ -180,7 +179,7 @@ class CRNN(_FlatModule):
         self.overlap_rnn = os.environ.get("BSED_RNN_OVERLAP", "1") != "0"
         # first block without its conv output / gradient tensors in HBM (csrc/block0.hip); 0 = the four-kernel form
         # (conv0_fwd, glu16_fwd, glu16_bwd, conv0_wgrad), kept as the cross-check of the tests
-        self.block0_fused = os.environ.get("BSED_BLOCK0_FUSED", "1") != "0"
+        self.block0_fused = True
         self._side_stream = None
         self.rnn_hook = None
         # eval-mode forwards (get_predictions, the CNN-only tagger): the packed weight copies of a forward in one launch
@@ -285,7 +284,7 @@ class CRNN(_FlatModule):
         return torch.bfloat16 if self.conv_mode == "bf16" else torch.float32
 
     def _check_bf16_mode(self):
-        if self.conv_mode == "bf16" and not (ops.igemm3_nsplit() and self.glu3 and self.block0_fused and self.fused_glu_bwd
+        if self.conv_mode == "bf16" and not (ops.igemm3_nsplit() and self.block0_fused and self.fused_glu_bwd
                                              and not any(c.__name__ == "CRNN_fpn" for c in type(self).__mro__)
                                              and self.nb_filters[0] == 16 and all(f >= 32 for f in self.nb_filters[1:])):
             raise L.BsedError("conv_mode='bf16' is built for the plain CRNN / CRNN_pred path (fused first block with 16 "
@@ -364,7 +363,7 @@ class CRNN(_FlatModule):
             # 4 FLOP/B: HBM-bound streaming kernel instead of the MFMA tile kernel (csrc/glu_small.hip)
             pooled = ops.glu16_fwd(y, scale, shift, glu.weight, glu.bias, B, Hh, Ww, (ph, pw), drop, rng_stream,
                                    self.seed)
-        elif self._mfma3 and self.glu3 and ops.glu_fwd3_supported(Ww, co, (ph, pw)):
+        elif self._mfma3 and ops.glu_fwd3_supported(Ww, co, (ph, pw)):
             pooled = ops.glu_fwd3(y, scale, shift, glu.weight, glu.bias, B, Hh, Ww, co, (ph, pw), drop, rng_stream,
                                   self.seed)
         else:
@@ -444,11 +443,12 @@ class CRNN(_FlatModule):
         else:
             ops.colsum(dxp, B * T, 768, 768, g_bih)
             ops.colsum(dgh, B * T, 768, 768, g_bhh)
-        part, G, KP, NP = ops.wgrad(lay["inp"], dxp, 1, B * T, 1, nin, 768)
+        part, G, KP, NP = ops.wgrad(lay["inp"], dxp, 1, B * T, 1, nin, 768, mode=self.conv_mode)
         ops.reduce_partials(part, G, 1, KP, NP, nin, 768, g_wih, 0, 1, nin)
         for dr in range(2):
             part, G, KP, NP = ops.wgrad(lay["out"], dgh, B, T, 1, 128, 384, taps=((-1 if dr == 0 else 1, 0),),
-                                        in_pitch=256, dy_pitch=768, in_offset=dr * 128, dy_offset=dr * 384)
+                                        in_pitch=256, dy_pitch=768, in_offset=dr * 128, dy_offset=dr * 384,
+                                        mode=self.conv_mode)
             ops.reduce_partials(part, G, 1, KP, NP, 128, 384, g_whh, 0, 1, 128, dst_offset=dr * 384 * 128)
 
     def _gru_backward(self, layers, d, B, T, prefix):
@@ -505,18 +505,19 @@ class CRNN(_FlatModule):
                                                 dpool.contiguous(), B, Hh, Ww, (ph, pw), drop_b, rng, seed)
             ops.reduce_partials(pdw, G, 1, 16, 16, 16, 16, glu.weight.grad, 0, 16, 1)
             ops.stats_to_grad(pdb, co, 0, glu.bias.grad)
-        elif co in (32, 64) and self.fused_glu_bwd and self._mfma3 and self.glu3:
+        elif co in (32, 64) and self.fused_glu_bwd and self._mfma3:
             # all three contractions on the bf16 cores, operands fetched in MFMA register layout (csrc/glu3.hip)
             g, pdw, pdb, st2, G, slabs = ops.glu_bwd3(y, blk["scale"], blk["shift"], glu.weight, glu.bias,
                                                       dpool.contiguous(), B, Hh, Ww, co, (ph, pw), drop_b, rng, seed)
             ops.reduce_partials(pdw, G * slabs, 1, co, co, co, co, glu.weight.grad, 0, co, 1)
             ops.stats_to_grad(pdb, co, 0, glu.bias.grad)
-        elif co == 128 and self.fused_glu_bwd and self._mfma3 and self.glu3:
+        elif co == 128 and self.fused_glu_bwd and self._mfma3:
             # lin recompute + g on the bf16 cores; d_lin goes through HBM to a 1-tap weight-gradient contraction
             g, dlin, pdb, st2, G = ops.glu_bwd3n(y, blk["scale"], blk["shift"], glu.weight, glu.bias,
                                                  dpool.contiguous(), B, Hh, Ww, co, (ph, pw), drop_b, rng, seed)
             ops.stats_to_grad(pdb, co, 0, glu.bias.grad)
-            part, Gw, KP, NP = ops.wgrad(y, dlin, B, Hh, Ww, co, co, a_scale=blk["scale"], a_shift=blk["shift"])
+            part, Gw, KP, NP = ops.wgrad(y, dlin, B, Hh, Ww, co, co, a_scale=blk["scale"], a_shift=blk["shift"],
+                                         mode=self.conv_mode)
             ops.reduce_partials(part, Gw, 1, KP, NP, co, co, glu.weight.grad, 0, 1, co)
             del dlin
         elif co in (32, 64, 128) and self.fused_glu_bwd:
@@ -537,7 +538,8 @@ class CRNN(_FlatModule):
                                  rng_stream=rng, seed=seed)
             ops.stats_to_grad(st, co, 0, glu.bias.grad)
             # (2) dW_glu = d_lin^T @ bn(y)
-            part, G, KP, NP = ops.wgrad(y, dlin, B, Hh, Ww, co, co, a_scale=blk["scale"], a_shift=blk["shift"])
+            part, G, KP, NP = ops.wgrad(y, dlin, B, Hh, Ww, co, co, a_scale=blk["scale"], a_shift=blk["shift"],
+                                         mode=self.conv_mode)
             ops.reduce_partials(part, G, 1, KP, NP, co, co, glu.weight.grad, 0, 1, co)
             # (3) g = d_lin @ W_glu + gate term  (gradient w.r.t. the BatchNorm output), with BN-backward sums
             wgT = ops.pack_weight(glu.weight, 1, co, co, 0, co, 1)
@@ -559,14 +561,14 @@ class CRNN(_FlatModule):
             coef = ops.bn_bwd(st2, co, float(B * Hh * Ww), bn.weight, blk["mean"], blk["invstd"], bn.weight.grad,
                               bn.bias.grad, g, y, apply=False)
             dy = torch.empty_like(g) if need_dgrad else None
-            part, G, KP, NP = ops.wgrad(blk["inp"], g, B, Hh, Ww, cin, co, taps=taps, bn_y=y, bn_coef=coef,
-                                        bn_mean=blk["mean"], dy_out=dy)
+            part, G, KP, NP = ops.wgrad(blk["inp"], g, B, Hh, Ww, cin, co, taps=taps, mode=self.conv_mode, bn_y=y,
+                                        bn_coef=coef, bn_mean=blk["mean"], dy_out=dy)
         else:
             # (4) BatchNorm backward -> d_y in place
             ops.bn_bwd(st2, co, float(B * Hh * Ww), bn.weight, blk["mean"], blk["invstd"], bn.weight.grad,
                        bn.bias.grad, g, y)
             dy = g
-            part, G, KP, NP = ops.wgrad(blk["inp"], dy, B, Hh, Ww, cin, co, taps=taps)
+            part, G, KP, NP = ops.wgrad(blk["inp"], dy, B, Hh, Ww, cin, co, taps=taps, mode=self.conv_mode)
         ops.reduce_partials(part, G, len(taps), KP, NP, cin, co, cw.grad, s_tap, 9, cin * 9,
                             dst_offset=0 if Ww > 1 else 1)
         if not need_dgrad:
@@ -742,7 +744,7 @@ class CRNN_fpn(CRNN):
         """accumulates dW, db of the 1x1 convolution; returns dL/d(cat) (B,T,512)"""
         w, b = self.P(name + ".weight"), self.P(name + ".bias")
         ops.colsum(d_out, B * T, 256, 256, b.grad)
-        part, G, KP, NP = ops.wgrad(cat, d_out, 1, B * T, 1, 512, 256)
+        part, G, KP, NP = ops.wgrad(cat, d_out, 1, B * T, 1, 512, 256, mode=self.conv_mode)
         ops.reduce_partials(part, G, 1, KP, NP, 512, 256, w.grad, 0, 1, 512)
         if self.conv_mode == "bf16x3":
             w3 = ops.pack_weight3(w, 1, 256, 512, 0, 512, 1)

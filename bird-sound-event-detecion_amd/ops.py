@@ -234,9 +234,6 @@ def igemm(inp, wpk, N, NB, H, W, CIN, taps=((0, 0),), bias=None, out=None, epilo
     return out, stats
 
 
-IGEMM3_RB = {"rb": 1}  # 2 = 256-position tiles where they fit (measured no faster than 1: kept for A-B measurements)
-
-
 _pack_memo = None   # {(kind, data_ptr, args): packed tensor} while an ops.pack_cache() block is open
 _pack_plan = None   # the PackPlan of the open outermost block, if it was given one
 
@@ -349,9 +346,9 @@ def _pack_store(key, dst, src, kind, ntaps, K, N, s_tap, s_k, s_n):
 def igemm3_nsplit():
     """True: ops.igemm3 runs the round-3 kernel (csrc/igemm3n.hip: a wave owns 32 output channels, weight fragments
     straight from global memory, one barrier per 32-channel chunk) and pack_weight3 emits its fragment-order table;
-    BSED_IGEMM3N=0 (or 256-position tiles, IGEMM3_RB) = the slab kernel of rounds 1-2 (csrc/igemm3.hip)."""
+    BSED_IGEMM3N=0 = the slab kernel of rounds 1-2 (csrc/igemm3.hip)."""
     import os
-    return os.environ.get("BSED_IGEMM3N", "1") != "0" and IGEMM3_RB["rb"] != 2
+    return os.environ.get("BSED_IGEMM3N", "1") != "0"
 
 
 def pack_weight3(src, ntaps, K, N, s_tap, s_k, s_n):
@@ -434,14 +431,6 @@ def igemm3(inp, w3, N, NB, H, W, CIN, taps, bias=None, epilogue=EPI_PLAIN, valid
     TH, TW = tile_for(W)
     NP = w3.shape[2]
     bn = 128 if NP % 128 == 0 else (64 if NP % 64 == 0 else 32)
-    import os
-    if os.environ.get("BSED_IGEMM3_BN") in ("64", "32"):   # A/B knob (csrc/igemm3.hip): labels follow the launch
-        bn = min(bn, int(os.environ["BSED_IGEMM3_BN"]))
-    # 256-position tiles (two row blocks per wave: half the LDS reads and weight-slab stagings per MFMA) when they
-    # still fill the chip: 128 output channels per workgroup and at least ~4 workgroups per CU
-    rb = 2 if (IGEMM3_RB["rb"] == 2 and bn == 128 and H >= 2 * TH and (2 * TH + 2) * (TW + 2) <= 384 and
-               NB * ((H + 2 * TH - 1) // (2 * TH)) * (W // TW) * (NP // 128) >= 1024) else 1
-    TH *= rb
     dev = inp.device
     out = (torch.zeros if valid else torch.empty)((NB, H, W, N), device=dev, dtype=torch.float32)
     if valid:
@@ -459,13 +448,10 @@ def igemm3(inp, w3, N, NB, H, W, CIN, taps, bias=None, epilogue=EPI_PLAIN, valid
     d.ph = d.pw = 1; d.Hp, d.Wp = H, W
     d.epilogue = epilogue
     need = ((TH + 2 * d.hh) * (TW + 2 * d.hw) * 8 + 255) // 256        # float4 patch elements per thread (launch_i3)
-    pv = 12 if rb == 2 or need > 9 else (9 if need > 6 else 6)
-    _launch((f"igemm3_kernel<{bn}, {1 if epilogue == EPI_STATS else 0}, {rb}, {pv}>", len(taps), CIN, N, H, W),
+    pv = 12 if need > 9 else (9 if need > 6 else 6)
+    _launch((f"igemm3_kernel<{bn}, {1 if epilogue == EPI_STATS else 0}, 1, {pv}>", len(taps), CIN, N, H, W),
             2.0 * NB * H * W * len(taps) * CIN * N, lambda: L.call("bsed_igemm3", ctypes.byref(d), L.stream()))
     return out, stats
-
-
-IGEMM3N_WPE = {"wpe": None}   # A/B knob (set_igemm3n_wpe)
 
 
 def set_igemm3n_shape(shape):
@@ -476,7 +462,6 @@ def set_igemm3n_shape(shape):
 def set_igemm3n_wpe(wpe):
     """A/B knob of the BN = 128 build: 2 / 3 = built for that many waves per SIMD whatever the shape; + 8 = no raised
     wave priority outside the MFMA loop; 0 / None = default"""
-    IGEMM3N_WPE["wpe"] = wpe
     L.lib().bsed_igemm3n_set_wpe(_i(wpe or 0))
 
 
@@ -502,8 +487,6 @@ def _igemm3n(inp, wtab, N, NB, H, W, CIN, taps, bias, epilogue, valid):
         d.dh[i], d.dw[i] = a, b
     d.ph = d.pw = 1; d.Hp, d.Wp = H, W
     d.epilogue = epilogue
-    if IGEMM3N_WPE.get("stamp") is not None:   # diagnostic builds only (tools/conv_stamp.py, -DI3N_STAMP)
-        d.e_src = IGEMM3N_WPE["stamp"].data_ptr()
     d.in_ = _dp(inp); d.w = wtab.data_ptr(); d.bias = _p(bias); d.out = out.data_ptr()
     rows = L.lib().bsed_igemm3n_stats_rows(ctypes.byref(d))
     var = L.lib().bsed_igemm3n_variant(ctypes.byref(d))
@@ -517,16 +500,14 @@ def _igemm3n(inp, wtab, N, NB, H, W, CIN, taps, bias, epilogue, valid):
     return out, stats
 
 
-WGRAD_MODE = {"mode": None}  # None = follow BSED_CONV_MODE; "fp32" / "bf16x3" force one
-
-
 def wgrad(inp, dy, NB, H, W, CIN, N, taps=((0, 0),), in_pitch=None, dy_pitch=None, a_scale=None, a_shift=None,
-          in_offset=0, dy_offset=0, mode=None, bn_y=None, bn_coef=None, bn_mean=None, dy_out=None):
-    """Partial slabs of dW; returns (part, G, CINP, NP).  mode "bf16x3" = split-fp32 operands on the bf16 cores.
+          in_offset=0, dy_offset=0, *, mode, bn_y=None, bn_coef=None, bn_mean=None, dy_out=None):
+    """Partial slabs of dW; returns (part, G, CINP, NP).  mode: the caller's conv_mode -- "fp32" = the fp32-core
+    kernels, "bf16x3" / "bf16" = split-fp32 operands on the bf16 cores.
     bn_y / bn_coef / bn_mean: `dy` is dL/d(BatchNorm output) and BatchNorm's backward is applied on load (bf16x3 only);
     dy_out then receives d_y for the data-gradient convolution."""
-    import os
-    mode = mode or WGRAD_MODE["mode"] or os.environ.get("BSED_CONV_MODE", "bf16x3")
+    if mode not in ("fp32", "bf16x3", "bf16"):
+        raise L.BsedError(f"wgrad: unknown mode {mode!r}")
     sfx = "3" if mode in ("bf16x3", "bf16") else ""
     d = WgradDesc()
     TH, TW = tile_for(W)
@@ -706,8 +687,7 @@ def glu16_bwd(y, scale, shift, wg, bg, dpool, B, H, W, pool, drop_p, rng_stream,
 
 def block0_stats(x, cw, cb, NB, H, W):
     """train-mode statistics of the first block from x alone: returns (stats (G,2,16) for bn_finalize, xr64 (54,) fp64)"""
-    import os
-    G = int(min(int(os.environ.get("BSED_B0_STATS_G", "2048")), max(1, (NB * H * W) // 256)))   # (A/B knob)
+    G = int(min(2048, max(1, (NB * H * W) // 256)))
     dev = x.device
     stats = torch.empty((G, 2, 16), device=dev, dtype=torch.float32)
     xr_part = torch.empty((G, 54), device=dev, dtype=torch.float32)
@@ -736,8 +716,7 @@ def block0_bwd(x, cw, cb, scale, shift, wg, bg, dpool, B, H, W, pool, drop_p, rn
     """returns (part_dw (G,16,16), part_db (G,2,16), part_st (G,2,16), part_gx (G,9,16), G)"""
     ph, pw = pool
     dev = x.device
-    import os
-    G = int(min(int(os.environ.get("BSED_B0_BWD_G", "8192")), B * (H // ph)))   # 2048 / 4096 / 8192 workgroups: 0.983 / 0.966 / 0.957 ms
+    G = int(min(8192, B * (H // ph)))   # 2048 / 4096 / 8192 workgroups: 0.983 / 0.966 / 0.957 ms
     part_dw = torch.empty((G, 16, 16), device=dev, dtype=torch.float32)
     part_db = torch.empty((G, 2, 16), device=dev, dtype=torch.float32)
     part_st = torch.empty((G, 2, 16), device=dev, dtype=torch.float32)

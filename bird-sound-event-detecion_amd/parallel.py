@@ -2,7 +2,6 @@
 ROCm, "gloo" in the CPU tests).  The reference has no distributed code: this is the MI355X-side design of
 SURVEY.md section 8(e) -- shard clips by rank, keep BatchNorm statistics per rank, exchange ONE flat gradient
 buffer per module per step, fold 1/world into the optimizer."""
-import os
 
 import torch
 import torch.distributed as dist
@@ -33,14 +32,12 @@ class GradArena:
     Sums only: the 1/world factor is folded into the optimizer kernel.  With world size 1 both are no-ops (and the
     arena still makes zero_grad one memset).  SURVEY.md section 8(e); the reference has no distributed code."""
 
-    def __init__(self, modules, tail_floats=0, group=None, exchange_single_rank=None):
+    def __init__(self, modules, tail_floats=0, group=None, exchange_single_rank=False):
         """exchange_single_rank: run the two all-reduces even in a group of ONE rank (identity on the data, but they
         execute on the backend's stream with the real dependencies) -- the one way a single-GPU box can put
-        begin_early / finish through RCCL (tests/test_dp_gpu.py); default from BSED_DP_SINGLE_RANK_EXCHANGE."""
+        begin_early / finish through RCCL (tests/test_dp_gpu.py)."""
         self.modules = [m for m in modules if m is not None]
         self.group = group
-        if exchange_single_rank is None:
-            exchange_single_rank = os.environ.get("BSED_DP_SINGLE_RANK_EXCHANGE", "0") == "1"
         self.exchange_single_rank = bool(exchange_single_rank)
         sizes = [m.flat_grad.numel() for m in self.modules]
         dev = self.modules[0].flat_grad.device

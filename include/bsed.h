@@ -150,11 +150,11 @@ int bsed_igemm3s(const BsedIgemmDesc* desc, int G, void* stream);
 int bsed_igemm3n(const BsedIgemmDesc* desc /*host*/, void* stream);
 int bsed_igemm3n_stats_rows(const BsedIgemmDesc* desc /*host: NB, H, W, TH, TW, NP*/);
 int bsed_igemm3n_variant(const BsedIgemmDesc* desc);   /* NWN | MW << 4 | PV << 8 | WPE << 12 of the build */
-void bsed_igemm3n_set_wpe(int knob);  /* A/B knob: 2 / 3 = the BN = 128 build for that many waves per SIMD whatever the
+void bsed_igemm3n_set_wpe(int knob);  /* test hook: 2 / 3 = the BN = 128 build for that many waves per SIMD whatever the
                                        * shape, + 8 = no raised wave priority outside the MFMA loop, 0 = default */
-void bsed_igemm3n_set_shape(int shape); /* A/B knob: MFMA shape of the nine-tap instances, 16 = v_mfma_f32_16x16x32_bf16 (default with
+void bsed_igemm3n_set_shape(int shape); /* test hook: MFMA shape of the nine-tap instances, 16 = v_mfma_f32_16x16x32_bf16 (default with
                                          * fp32 activations), 32 = v_mfma_f32_32x32x16_bf16 (default with bf16 activations, and
-                                         * bit-identical to bsed_igemm3); 0 = defaults / BSED_IGEMM3N_SHAPE */
+                                         * bit-identical to bsed_igemm3); 0 = defaults */
 int bsed_igemm3s_auto_g(void);
 int bsed_igemm3s_auto_g2(int CIN, int N);   /* per shape (resident workgroups differ with the LDS footprint) */
 
@@ -192,7 +192,7 @@ int bsed_wgrad_variant(const BsedWgradDesc* desc /*host*/);
  * shapes whose two tile buffers fit in LDS run the producer/consumer kernel (wgrad3p_kernel).  Same descriptor, same
  * partial-slab layout; G must come from bsed_wgrad3_auto_g (it differs between the two kernels).
  * bsed_wgrad3_variant: MAXS*16 + NW, NW == 1 meaning wgrad3p_kernel<MAXS>; bit 12 = the BS template argument of
- * wgrad3_kernel<MAXS, NW, BS> (labels only).  BSED_WGRAD3_NOPIPE=1 in the environment forces wgrad3_kernel (A/B runs). */
+ * wgrad3_kernel<MAXS, NW, BS> (labels only).  BSED_WGRAD3_NOPIPE=1 in the environment forces wgrad3_kernel (tests). */
 int bsed_wgrad3(const BsedWgradDesc* desc /*host*/, void* stream);
 int bsed_wgrad3_auto_g(const BsedWgradDesc* desc /*host*/);
 int bsed_wgrad3_variant(const BsedWgradDesc* desc /*host*/);

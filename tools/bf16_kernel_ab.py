@@ -44,8 +44,8 @@ for dt in (torch.float32, torch.bfloat16):
         "conv fwd": timed(lambda: ops.igemm3(x, w3, C, B, H, W, C, ops.TAPS3x3, bias=bias, epilogue=ops.EPI_STATS)),
         "glu fwd": timed(lambda: ops.glu_fwd3(y, sc, sh, wl, bias, B, H, W, C, (1, 2), 0.5, 101, 7)),
         "glu bwd": timed(lambda: (ops.glu_bwd3n if C == 128 else ops.glu_bwd3)(y, sc, sh, wl, bias, dp, B, H, W, C, (1, 2), 0.5, 101, 7)),
-        "wgrad9+bn": timed(lambda: ops.wgrad(x, gg, B, H, W, C, C, taps=ops.TAPS3x3, bn_y=y, bn_coef=coef, bn_mean=mean, dy_out=dy)),
-        "wgrad9": timed(lambda: ops.wgrad(x, gg, B, H, W, C, C, taps=ops.TAPS3x3)),
-        "wgrad1": timed(lambda: ops.wgrad(y, gg, B, H, W, C, C, a_scale=sc, a_shift=sh)),
+        "wgrad9+bn": timed(lambda: ops.wgrad(x, gg, B, H, W, C, C, taps=ops.TAPS3x3, mode="bf16x3", bn_y=y, bn_coef=coef, bn_mean=mean, dy_out=dy)),
+        "wgrad9": timed(lambda: ops.wgrad(x, gg, B, H, W, C, C, taps=ops.TAPS3x3, mode="bf16x3")),
+        "wgrad1": timed(lambda: ops.wgrad(y, gg, B, H, W, C, C, a_scale=sc, a_shift=sh, mode="bf16x3")),
     }
     print(f"W={W} C={C} {str(dt):15s}: " + "  ".join(f"{k} {v:7.1f} us" for k, v in res.items()), flush=True)
