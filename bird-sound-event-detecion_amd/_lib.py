@@ -4,6 +4,7 @@ The library is built in-tree by ``csrc/build.sh`` (``__graft_entry__.build()``) 
 compute path: ``lib()`` raises if it is missing -- there is no eager/PyTorch fallback.
 """
 import ctypes
+import keyword
 import os
 import re
 
@@ -43,16 +44,97 @@ class BsedError(RuntimeError):
     pass
 
 
-class MelCfg(ctypes.Structure):
-    _fields_ = [("sr", ctypes.c_int), ("n_fft", ctypes.c_int), ("hop", ctypes.c_int),
-                ("n_mels", ctypes.c_int), ("fmin", ctypes.c_float), ("fmax", ctypes.c_float)]
+# include/bsed.h is the one statement of the C ABI: the prototypes (-> argtypes / restype), the descriptor structs (->
+# ctypes.Structure classes) and the integer constants are read from it, never restated in Python, so a change there
+# reaches every caller or fails loudly.  The grammar is the header's own -- prototypes, `typedef struct X {...} X;`,
+# enums and `#define NAME <int>` -- over the scalar types below and pointers (void*); anything else raises with the
+# offending text.
+_SCALARS = {"int": ctypes.c_int, "long": ctypes.c_long, "long long": ctypes.c_longlong, "size_t": ctypes.c_size_t,
+            "float": ctypes.c_float, "double": ctypes.c_double,
+            "uint32_t": ctypes.c_uint32, "uint64_t": ctypes.c_uint64}
+_ITEM = re.compile(r"""(?: typedef\s+struct\s+\w+\s*\{(?P<fields>[^{}]*)\}\s*(?P<struct>\w+)\s*;
+                        | enum\s*\{(?P<enum>[^{}]*)\}\s*;
+                        | (?P<ret>[\w\s*]+?)\s*\b(?P<fn>\w+)\s*\((?P<params>[^()]*)\)\s*; )\s*""", re.X)
+
+
+def _unparsed(text):
+    return BsedError(f"include/bsed.h: cannot bind {' '.join(text.split())!r}")
+
+
+def _ctype(base, stars, text):
+    if stars:
+        return ctypes.c_void_p
+    base = " ".join(w for w in base.split() if w != "const")
+    if base not in _SCALARS:
+        raise _unparsed(text)
+    return _SCALARS[base]
+
+
+def _declaration(text):
+    """'const float *a, *b' / 'int dh[9]' -> [(name, ctype, array length or 0), ...]"""
+    head, *more = text.split(",")
+    m = re.fullmatch(r"\s*([\w\s]+?)(\s*\**\s*\w+\s*(?:\[\d+\])?\s*)", head)
+    out = []
+    for d in [m and m[2]] + more:
+        dm = d and re.fullmatch(r"\s*(\**)\s*(\w+)\s*(?:\[(\d+)\])?\s*", d)
+        if not dm:
+            raise _unparsed(text)
+        out.append((dm[2], _ctype(m[1], dm[1], text), int(dm[3] or 0)))
+    return out
+
+
+def _param(text):
+    (_, t, n), = _declaration(text)
+    if n:
+        raise _unparsed(text)
+    return t
+
+
+def parse_header(path=None):
+    """include/bsed.h -> (functions {name: (restype, [argtypes])}, structs {name: Structure}, constants {name: int})"""
+    txt = re.sub(r"/\*.*?\*/|//[^\n]*", " ", open(path or HEADER_PATH).read(), flags=re.S)
+    txt = re.sub(r"#ifdef __cplusplus.*?#endif", " ", txt, flags=re.S)     # the extern "C" guard
+    functions, structs, constants = {}, {}, {}
+    for line in re.findall(r"^[ \t]*#.*", txt, flags=re.M):
+        d = re.fullmatch(r"\s*#\s*define\s+(\w+)(?:\s+(-?\d+))?\s*", line)
+        if d and d[2]:
+            constants[d[1]] = int(d[2])
+        elif not (d or re.fullmatch(r"\s*#\s*(ifndef|endif|include)\b.*", line)):
+            raise _unparsed(line)
+    txt = re.sub(r"^[ \t]*#.*", " ", txt, flags=re.M).strip()
+    pos = 0
+    while pos < len(txt):
+        m = _ITEM.match(txt, pos)
+        if not m:
+            raise _unparsed(txt[pos:pos + 120])
+        pos = m.end()
+        if m["struct"]:
+            fields = [f for decl in m["fields"].split(";") if decl.strip() for f in _declaration(decl)]
+            structs[m["struct"]] = type(m["struct"], (ctypes.Structure,), {"_fields_": [
+                (n + "_" if keyword.iskeyword(n) else n, t * k if k else t) for n, t, k in fields]})
+        elif m["enum"] is not None:
+            v = -1
+            for e in filter(str.strip, m["enum"].split(",")):
+                em = re.fullmatch(r"\s*(\w+)\s*(?:=\s*(-?\d+)\s*)?", e)
+                if not em:
+                    raise _unparsed(e)
+                v = constants[em[1]] = int(em[2]) if em[2] else v + 1
+        else:
+            ret = re.sub(r"\s*\*", "*", " ".join(m["ret"].split()))
+            restype = {"void": None, "const char*": ctypes.c_char_p}.get(ret, False)
+            if restype is False:
+                restype = _ctype(ret.rstrip("*"), ret.count("*"), m[0])
+            params = m["params"].strip()
+            functions[m["fn"]] = (restype, [] if params == "void" else [_param(p) for p in params.split(",")])
+    return functions, structs, constants
+
+
+FUNCTIONS, STRUCTS, CONSTANTS = parse_header()
 
 
 def header_symbols():
     """Every function name declared in include/bsed.h."""
-    txt = open(HEADER_PATH).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(bsed_[a-z0-9_]+)\s*\(", txt)))
+    return sorted(FUNCTIONS)
 
 
 def lib():
@@ -62,12 +144,9 @@ def lib():
             raise BsedError(f"{LIB_PATH} is missing: build it with csrc/build.sh "
                             "(python -c 'import __graft_entry__ as g; g.build()'); there is no CPU fallback")
         L = ctypes.CDLL(LIB_PATH)
-        L.bsed_last_error.restype = ctypes.c_char_p
-        L.bsed_build_info.restype = ctypes.c_char_p
-        for name in header_symbols():
+        for name, (restype, argtypes) in FUNCTIONS.items():
             fn = getattr(L, name)  # AttributeError = header/library mismatch: fail loudly
-            if name not in ("bsed_last_error", "bsed_build_info"):
-                fn.restype = ctypes.c_int
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = L
     return _lib
 
@@ -126,7 +205,7 @@ pending = None
 
 
 def call(name, *args):
-    """Call an int-returning entry point; ints/floats are passed with explicit ctypes."""
+    """Call an int-returning entry point and raise on a nonzero return; the header's argtypes convert the arguments."""
     global pending
     fn = getattr(lib(), name)
     if timer is None:
@@ -139,6 +218,3 @@ def call(name, *args):
 
 c_int = ctypes.c_int
 c_float = ctypes.c_float
-c_u64 = ctypes.c_uint64
-c_void_p = ctypes.c_void_p
-c_size_t = ctypes.c_size_t

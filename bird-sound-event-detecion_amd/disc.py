@@ -8,7 +8,6 @@ Layers 2 and 3 (98 % of the multiply-adds) run directly on the implicit-GEMM ker
 re-layout (a 3x3 / stride-2 convolution is a 2x2 / stride-1 one over 4C channels); layers 1, 4 and 5 (1, 32, 16 input
 channels) keep the im2col lowering (csrc/disc.hip, csrc/igemm.hip, csrc/igemm3.hip).
 """
-import ctypes
 import math
 
 import numpy as np
@@ -23,10 +22,6 @@ D_EPS, D_MOM = 1e-5, 0.1
 D_CH = [1, 128, 64, 32, 16, 8]
 
 
-def _i(v):
-    return ctypes.c_int(v)
-
-
 def grl_coeff(iter_num, alpha=1.0, lo=0.0, hi=1.0, max_iters=1000.0):
     """WarmStartGradientReverseLayer coefficient at call ``iter_num`` (reference src/DA/grl.py:62-67)"""
     return float(2.0 * (hi - lo) / (1.0 + np.exp(-alpha * iter_num / max_iters)) - (hi - lo) + lo)
@@ -36,8 +31,7 @@ def _im2col(act, scale, shift, N, Hi, Wi, C, CP):
     Ho, Wo = (Hi - 3) // 2 + 1, (Wi - 3) // 2 + 1
     K = 16 if C == 1 else 9 * CP
     col = torch.empty((N * Ho * Wo, K), device=act.device, dtype=torch.float32)
-    L.call("bsed_im2col_s2", L.ptr(act), L.ptr(scale), L.ptr(shift), L.ptr(col), _i(N), _i(Hi), _i(Wi), _i(C), _i(CP),
-           L.stream())
+    L.call("bsed_im2col_s2", L.ptr(act), L.ptr(scale), L.ptr(shift), L.ptr(col), N, Hi, Wi, C, CP, L.stream())
     return col, Ho, Wo, K
 
 
@@ -48,8 +42,8 @@ def _col2im(dcol, y, scale, shift, N, Hi, Wi, C, CP, out_scale=1.0):
     if C > 1:
         nb = L.lib().bsed_col2im_s2_num_blocks(N, Hi, Wi, C)
         stats = torch.empty((nb, 2, C), device=dev, dtype=torch.float32)
-    L.call("bsed_col2im_s2", L.ptr(dcol), L.ptr(y), L.ptr(scale), L.ptr(shift), L.ptr(out), L.ptr(stats), _i(N), _i(Hi),
-           _i(Wi), _i(C), _i(CP), ctypes.c_float(out_scale), L.stream())
+    L.call("bsed_col2im_s2", L.ptr(dcol), L.ptr(y), L.ptr(scale), L.ptr(shift), L.ptr(out), L.ptr(stats), N, Hi, Wi,
+           C, CP, out_scale, L.stream())
     return out, stats
 
 
@@ -64,8 +58,7 @@ def _s2d_fwd(y, scale, shift, N, Ha, Wa, Hi, Wi, C):
     Hp, Wp = (Hi + 1) // 2, (Wi + 1) // 2
     xp = torch.empty((N, Hp, Wp, 4 * C), device=y.device, dtype=torch.float32)
     ops._note("s2d_fwd_kernel", f"{Hi}x{Wi}x{C}", 3.0 * xp.numel(), 4.0 * (N * Hi * Wi * C + xp.numel()))
-    L.call("bsed_s2d_fwd", L.ptr(y), L.ptr(scale), L.ptr(shift), L.ptr(xp), _i(N), _i(Ha), _i(Wa), _i(Hi), _i(Wi), _i(C),
-           L.stream())
+    L.call("bsed_s2d_fwd", L.ptr(y), L.ptr(scale), L.ptr(shift), L.ptr(xp), N, Ha, Wa, Hi, Wi, C, L.stream())
     return xp, Hp, Wp
 
 
@@ -74,8 +67,8 @@ def _s2d_bwd(dxp, y, scale, shift, N, Ha, Wa, Hi, Wi, C):
     nb = L.lib().bsed_s2d_num_blocks(N, Ha, Wa, C)
     stats = torch.empty((nb, 2, C), device=y.device, dtype=torch.float32)
     ops._note("s2d_bwd_kernel", f"{Hi}x{Wi}x{C}", 4.0 * g.numel(), 4.0 * (N * Hi * Wi * C + 2 * g.numel()))
-    L.call("bsed_s2d_bwd", L.ptr(dxp), L.ptr(y), L.ptr(scale), L.ptr(shift), L.ptr(g), L.ptr(stats), _i(N), _i(Ha), _i(Wa),
-           _i(Hi), _i(Wi), _i(C), L.stream())
+    L.call("bsed_s2d_bwd", L.ptr(dxp), L.ptr(y), L.ptr(scale), L.ptr(shift), L.ptr(g), L.ptr(stats), N, Ha, Wa, Hi,
+           Wi, C, L.stream())
     return g, stats
 
 
@@ -234,10 +227,9 @@ class Clip_Discriminator(_FlatModule):
             dbl = torch.empty((N, 2, 1), device=dev, dtype=torch.float32)
             lossp = torch.empty((N, 2, 1), device=dev, dtype=torch.float32)
         dense = self.P("dense_d")
-        L.call("bsed_disc_head", L.ptr(act), L.ptr(scale), L.ptr(shift), ctypes.c_void_p(dense.weight.data_ptr()),
-               ctypes.c_void_p(dense.bias.data_ptr()), _i(N), _i(n_source or 0), _i(Hi), _i(Wi), _i(8),
-               _i(1 if do_loss else 0), L.ptr(d), L.ptr(g5), L.ptr(stats5), L.ptr(dwl), L.ptr(dbl), L.ptr(lossp),
-               L.stream())
+        L.call("bsed_disc_head", L.ptr(act), L.ptr(scale), L.ptr(shift), dense.weight.data_ptr(),
+               dense.bias.data_ptr(), N, n_source or 0, Hi, Wi, 8, 1 if do_loss else 0, L.ptr(d), L.ptr(g5),
+               L.ptr(stats5), L.ptr(dwl), L.ptr(dbl), L.ptr(lossp), L.stream())
         ctx = dict(N=N, T=T, F=F, layers=layers, g5=g5, stats5=stats5, dwl=dwl, dbl=dbl, lossp=lossp) if save else None
         return d, ctx
 
@@ -365,14 +357,14 @@ class Frame_Discriminator(_FlatModule):
 
     def _act(self, a, stream_id, drop):
         out = torch.empty_like(a)
-        L.call("bsed_leaky_dropout_fwd", L.ptr(a), L.ptr(out), ctypes.c_long(a.numel()), ctypes.c_float(self.SLOPE),
-               ctypes.c_float(drop), ctypes.c_uint32(stream_id), ctypes.c_uint64(self.seed), L.stream())
+        L.call("bsed_leaky_dropout_fwd", L.ptr(a), L.ptr(out), a.numel(), self.SLOPE, drop, stream_id,
+               self.seed, L.stream())
         return out
 
     def _act_bwd(self, d_out, a, stream_id, drop, seed):
         d_a = torch.empty_like(a)
-        L.call("bsed_leaky_dropout_bwd", L.ptr(d_out), L.ptr(a), L.ptr(d_a), ctypes.c_long(a.numel()),
-               ctypes.c_float(self.SLOPE), ctypes.c_float(drop), ctypes.c_uint32(stream_id), ctypes.c_uint64(seed), L.stream())
+        L.call("bsed_leaky_dropout_bwd", L.ptr(d_out), L.ptr(a), L.ptr(d_a), a.numel(), self.SLOPE, drop,
+               stream_id, seed, L.stream())
         return d_a
 
     def run_forward(self, x, save=True):
@@ -389,8 +381,8 @@ class Frame_Discriminator(_FlatModule):
         h2 = self._act(a2, 402, drop)
         d = torch.empty((M,), device=x.device, dtype=torch.float32)
         w3, b3 = self.P("dense_d_3.weight"), self.P("dense_d_3.bias")
-        L.call("bsed_frame_head_fwd", L.ptr(h2), ctypes.c_void_p(w3.data_ptr()), ctypes.c_void_p(b3.data_ptr()), L.ptr(d),
-               ctypes.c_long(M), _i(32), L.stream())
+        L.call("bsed_frame_head_fwd", L.ptr(h2), w3.data_ptr(), b3.data_ptr(), L.ptr(d), M, 32,
+               L.stream())
         ctx = dict(x=x2d, a1=a1, h1=h1, a2=a2, h2=h2, d=d, M=M, drop=drop, seed=self.seed, shape=(N, T)) if save else None
         return d.view(N, T, 1), ctx
 
@@ -401,8 +393,8 @@ class Frame_Discriminator(_FlatModule):
         G = int(min(1024, max(1, M // 256)))
         dh2 = torch.empty((M, 32), device=d_out.device, dtype=torch.float32)
         part = torch.empty((G, 2, 32), device=d_out.device, dtype=torch.float32)
-        L.call("bsed_frame_head_bwd", L.ptr(ctx["h2"]), ctypes.c_void_p(w3.data_ptr()), L.ptr(ctx["d"]),
-               L.ptr(d_out.contiguous().view(M)), L.ptr(dh2), L.ptr(part), _i(G), ctypes.c_long(M), _i(32), L.stream())
+        L.call("bsed_frame_head_bwd", L.ptr(ctx["h2"]), w3.data_ptr(), L.ptr(ctx["d"]),
+               L.ptr(d_out.contiguous().view(M)), L.ptr(dh2), L.ptr(part), G, M, 32, L.stream())
         ops.stats_to_grad(part, 32, 0, w3.grad)
         tmp = torch.zeros(32, device=d_out.device, dtype=torch.float32)
         ops.stats_to_grad(part, 32, 1, tmp)

@@ -17,7 +17,6 @@ but the first two CNN blocks' has been enqueued, and overlaps the rest of it; th
 the optimizer kernel.
 """
 import numpy as np
-import ctypes
 
 import torch
 
@@ -515,18 +514,16 @@ class SEDTrainer:
             self._train_step(self._g_x, self._g_y, from_wave=from_wave)
         # device-resident step state: zero addends now, the baked scalars are those of THIS step
         self._g_state = torch.zeros(4, device=dev, dtype=torch.int64)     # [0] seed addend (uint64), [1] step addend (int32)
-        L.check(L.lib().bsed_set_step_state(ctypes.c_void_p(self._g_state[0:1].data_ptr()),
-                                            ctypes.c_void_p(self._g_state[1:2].data_ptr())), "bsed_set_step_state")
+        L.check(L.lib().bsed_set_step_state(self._g_state[0:1].data_ptr(), self._g_state[1:2].data_ptr()),
+                "bsed_set_step_state")
         self._g_base_step = self.global_step
         torch.cuda.synchronize()
         self._graph = torch.cuda.CUDAGraph()
         seed_inc = (parallel.rank_seed(self.seed, 1, self.rank) - parallel.rank_seed(self.seed, 0, self.rank)) * 4
         with torch.cuda.graph(self._graph):
             out = self._train_step(self._g_x, self._g_y, from_wave=from_wave)
-            L.check(L.lib().bsed_step_state_advance(ctypes.c_void_p(self._g_state[0:1].data_ptr()),
-                                                    ctypes.c_void_p(self._g_state[1:2].data_ptr()),
-                                                    ctypes.c_uint64(seed_inc), ctypes.c_int(1), L.stream()),
-                    "bsed_step_state_advance")
+            L.check(L.lib().bsed_step_state_advance(self._g_state[0:1].data_ptr(), self._g_state[1:2].data_ptr(),
+                                                    seed_inc, 1, L.stream()), "bsed_step_state_advance")
         self._g_out = out
         # the capture ran no kernel: undo its host-side bookkeeping (the first replay IS that step)
         self.global_step = self._g_base_step

@@ -11,7 +11,6 @@ Everything per frame runs on the GPU for the whole batch: forward (HIP), thresho
 ``bsed_decode_write``).  Only the event list (a few rows per clip) travels to the host, where the DataFrames are
 assembled without a per-clip Python loop.  Metric values (sed_eval / psds_eval) stay external.
 """
-import ctypes
 import os
 
 import numpy as np
@@ -38,8 +37,7 @@ def binarize_median_gpu(pred_strong, threshold=0.5, median_window=1):
     x = pred_strong.contiguous()
     B, T, C = x.shape
     out = torch.empty_like(x)
-    L.call("bsed_binarize_median", L.ptr(x), L.ptr(out), L.c_int(B), L.c_int(T), L.c_int(C), ctypes.c_float(threshold),
-           L.c_int(median_window), L.stream())
+    L.call("bsed_binarize_median", L.ptr(x), L.ptr(out), B, T, C, threshold, median_window, L.stream())
     return out
 
 
@@ -52,7 +50,7 @@ def decode_regions_gpu(mask, scale, max_len_seconds):
     if B * C == 0 or T == 0:                            # an empty batch decodes to an empty event list
         return (np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros((0, 2), np.int32), np.zeros((0, 2), np.float64))
     counts = torch.empty(B * C, device=mask.device, dtype=torch.int32)
-    L.call("bsed_decode_count", L.ptr(mask), L.c_int(B), L.c_int(T), L.c_int(C), L.ptr(counts, torch.int32), L.stream())
+    L.call("bsed_decode_count", L.ptr(mask), B, T, C, L.ptr(counts, torch.int32), L.stream())
     csum = torch.cumsum(counts, 0, dtype=torch.int32)
     offsets = (csum - counts).contiguous()
     E = int(csum[-1])                                   # the one host sync of the decode: the list length
@@ -61,9 +59,9 @@ def decode_regions_gpu(mask, scale, max_len_seconds):
     ev_frames = torch.empty((max(E, 1), 2), device=mask.device, dtype=torch.int32)
     ev_seconds = torch.empty((max(E, 1), 2), device=mask.device, dtype=torch.float64)
     if E:
-        L.call("bsed_decode_write", L.ptr(mask), L.ptr(offsets, torch.int32), L.c_int(B), L.c_int(T), L.c_int(C),
-               ctypes.c_double(scale), ctypes.c_double(max_len_seconds), L.ptr(ev_clip, torch.int32),
-               L.ptr(ev_class, torch.int32), L.ptr(ev_frames, torch.int32), L.ptr(ev_seconds, torch.float64), L.stream())
+        L.call("bsed_decode_write", L.ptr(mask), L.ptr(offsets, torch.int32), B, T, C, scale,
+               max_len_seconds, L.ptr(ev_clip, torch.int32), L.ptr(ev_class, torch.int32), L.ptr(ev_frames, torch.int32),
+               L.ptr(ev_seconds, torch.float64), L.stream())
     return (ev_clip[:E].cpu().numpy(), ev_class[:E].cpu().numpy(), ev_frames[:E].cpu().numpy(),
             ev_seconds[:E].cpu().numpy())
 

@@ -36,8 +36,8 @@ class MelFrontEnd:
     def __init__(self, cfg=None):
         L._require_gpu()
         self.cfg = cfg or MelConfig()
-        c = L.MelCfg(self.cfg.sr, self.cfg.n_window, self.cfg.hop_size, self.cfg.n_mels,
-                     self.cfg.mel_f_min, self.cfg.mel_f_max)
+        c = L.STRUCTS["BsedMelCfg"](self.cfg.sr, self.cfg.n_window, self.cfg.hop_size, self.cfg.n_mels,
+                                    self.cfg.mel_f_min, self.cfg.mel_f_max)
         self._plan = ctypes.c_void_p()
         L.call("bsed_mel_plan_create", ctypes.byref(c), ctypes.byref(self._plan))
         self.nnz = int(L.lib().bsed_mel_plan_nnz(self._plan))
@@ -68,11 +68,9 @@ class MelFrontEnd:
         ops._note("stft_mel2_kernel" if self.frames_per_wave == 2 else "stft_mel_kernel", f"T{T}",
                   B * T * (2.5 * 2048 * 11 + 4.0 * 1025 + 2.0 * self.nnz),
                   4.0 * B * (n + T * self.cfg.n_mels))
-        fn = L.lib().bsed_mel_scratch_floats
-        fn.restype = ctypes.c_long
-        scratch = torch.empty(fn(self._plan, L.c_int(B), L.c_int(n)), device=wav.device, dtype=torch.float32)
-        L.call("bsed_mel_linear", self._plan, L.ptr(wav), L.c_int(B), L.c_int(n), L.ptr(mel), L.ptr(cmax),
-               L.ptr(sumsq), L.ptr(scratch), L.stream())
+        scratch = torch.empty(L.lib().bsed_mel_scratch_floats(self._plan, B, n), device=wav.device, dtype=torch.float32)
+        L.call("bsed_mel_linear", self._plan, L.ptr(wav), B, n, L.ptr(mel), L.ptr(cmax), L.ptr(sumsq), L.ptr(scratch),
+               L.stream())
         return mel, cmax, sumsq
 
     def stats(self, mel_lin):
@@ -80,8 +78,7 @@ class MelFrontEnd:
         B, T, M = mel_lin.shape
         cmax = torch.empty((B,), device=mel_lin.device, dtype=torch.float32)
         sumsq = torch.empty((B, M), device=mel_lin.device, dtype=torch.float32)
-        L.call("bsed_mel_stats", L.ptr(mel_lin), L.c_int(B), L.c_int(T), L.c_int(M), L.ptr(cmax), L.ptr(sumsq),
-               L.stream())
+        L.call("bsed_mel_stats", L.ptr(mel_lin), B, T, M, L.ptr(cmax), L.ptr(sumsq), L.stream())
         return cmax, sumsq
 
     def to_db(self, mel_lin, clip_max, max_frames=None):
@@ -89,8 +86,8 @@ class MelFrontEnd:
         T_out = T if max_frames is None else max_frames
         out = torch.empty((B, 1, T_out, M), device=mel_lin.device, dtype=torch.float32)
         ops._note("mel_db_kernel", f"T{T_out}", 4.0 * B * T_out * M, 4.0 * B * M * (T + T_out))
-        L.call("bsed_mel_db", L.ptr(mel_lin), L.ptr(clip_max), L.c_int(B), L.c_int(T), L.c_int(T_out),
-               L.c_int(M), L.c_float(self.cfg.top_db), L.ptr(out), L.stream())
+        L.call("bsed_mel_db", L.ptr(mel_lin), L.ptr(clip_max), B, T, T_out, M, self.cfg.top_db,
+               L.ptr(out), L.stream())
         return out
 
     def add_noise(self, mel_lin, bin_sumsq, seed=0, unit_noise=None):
@@ -98,8 +95,8 @@ class MelFrontEnd:
         noisy = torch.empty_like(mel_lin)
         cmax = torch.empty((B,), device=mel_lin.device, dtype=torch.float32)
         ops._note("mel_noise_kernel", f"T{T}", 30.0 * B * T * M, 8.0 * B * T * M)
-        L.call("bsed_mel_noise", L.ptr(mel_lin), L.ptr(bin_sumsq), L.ptr(unit_noise), L.c_int(B), L.c_int(T),
-               L.c_int(M), L.c_float(self.cfg.noise_snr), L.c_u64(seed), L.ptr(noisy), L.ptr(cmax), L.stream())
+        L.call("bsed_mel_noise", L.ptr(mel_lin), L.ptr(bin_sumsq), L.ptr(unit_noise), B, T, M,
+               self.cfg.noise_snr, seed, L.ptr(noisy), L.ptr(cmax), L.stream())
         return noisy, cmax
 
     def transform(self, wav, max_frames=None, noisy=False, seed=0, unit_noise=None):

@@ -593,7 +593,7 @@ class CRNN(_FlatModule):
         drop = self.dropout_p if train else 0.0
         a, cin = x, 1
         bn_pre = None
-        if not train and len(self.nb_filters) <= 16:
+        if not train and len(self.nb_filters) <= ops.BN_EVAL_MAX_JOBS:
             # eval mode: the running-statistics scale / shift of all blocks in one launch
             bns = [self.P(f"cnn.batchnorm{i}") for i in range(len(self.nb_filters))]
             bn_pre = ops.bn_eval_batch([(co, bn.weight, bn.bias, bn.running_mean, bn.running_var)

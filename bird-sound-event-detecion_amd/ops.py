@@ -7,39 +7,14 @@ import torch
 
 from . import _lib as L
 
-EPI_PLAIN, EPI_STATS, EPI_GLU_POOL, EPI_GLU_BWD, EPI_ADD_STATS2 = range(5)
-
-_fp = ctypes.c_void_p
-_i = ctypes.c_int
-
-
-class IgemmDesc(ctypes.Structure):
-    _fields_ = ([(n, _fp) for n in ("in_", "w", "bias", "out", "out2", "stats", "a_scale", "a_shift", "e_src",
-                                    "e_scale", "e_shift", "e_dpool")]
-                + [(n, _i) for n in ("in_pitch", "out_pitch", "e_pitch", "NB", "H", "W", "CIN", "N", "NP", "TH", "TW",
-                                     "tilesH", "tilesW", "hh", "hw", "ntaps")]
-                + [("dh", _i * 9), ("dw", _i * 9)]
-                + [(n, _i) for n in ("ph", "pw", "Hp", "Wp", "epilogue")]
-                + [("drop_p", ctypes.c_float), ("rng_stream", ctypes.c_uint32), ("seed", ctypes.c_uint64)]
-                + [("valid_h", _i), ("valid_w", _i), ("act_bf16", _i)])
-
-
-class WgradDesc(ctypes.Structure):
-    _fields_ = ([(n, _fp) for n in ("in_", "dy", "part", "a_scale", "a_shift")]
-                + [(n, _i) for n in ("in_pitch", "dy_pitch", "NB", "H", "W", "CIN", "CINP", "N", "NP", "G", "TH", "TW",
-                                     "tilesH", "tilesW", "hh", "hw", "ntaps")]
-                + [("dh", _i * 9), ("dw", _i * 9)]
-                + [(n, _fp) for n in ("bn_y", "bn_coef", "bn_mean", "dy_out")] + [("act_bf16", _i)])
-
-
-class HeadBwdDesc(ctypes.Structure):
-    _fields_ = ([(n, _fp) for n in ("x", "w", "strong", "sof_raw", "weak", "den", "y_strong", "y_weak", "ema_strong",
-                                    "ema_weak", "ema_strong2", "g_strong_ext", "g_weak_ext")]
-                + [(n, ctypes.c_float) for n in ("w_strong", "w_weak", "w_cons_s", "w_cons_w", "w_cons_s2",
-                                                 "inv_n_strong", "inv_n_weak")]
-                + [(n, _fp) for n in ("dx", "dw_part", "db_part", "loss_part")]
-                + [(n, _i) for n in ("B", "T", "K", "C", "attention")])
-
+# epilogue ids and job limits of include/bsed.h; the descriptor and job structs come from the same parse (_lib.py)
+EPI_PLAIN, EPI_STATS, EPI_GLU_POOL, EPI_GLU_BWD, EPI_ADD_STATS2 = (
+    L.CONSTANTS["BSED_EPI_" + n] for n in ("PLAIN", "STATS", "GLU_POOL", "GLU_BWD", "ADD_STATS2"))
+PACK_MAX_JOBS = L.CONSTANTS["BSED_PACK_MAX_JOBS"]
+REDUCE_MAX_JOBS = L.CONSTANTS["BSED_REDUCE_MAX_JOBS"]
+BN_EVAL_MAX_JOBS = L.CONSTANTS["BSED_BN_EVAL_MAX_JOBS"]
+IgemmDesc, WgradDesc, HeadBwdDesc, PackJob, ReduceJob, BnEvalJob = (L.STRUCTS["Bsed" + n] for n in (
+    "IgemmDesc", "WgradDesc", "HeadBwdDesc", "PackJob", "ReduceJob", "BnEvalJob"))
 
 TAPS3x3 = [(kh - 1, kw - 1) for kh in range(3) for kw in range(3)]
 
@@ -187,8 +162,7 @@ def pack_weight(src, ntaps, K, N, s_tap, s_k, s_n, src_offset=0):
     NP = round_up(N, 32)
     dst = torch.empty((ntaps, K, NP), device=src.device, dtype=torch.float32)
     _note("pack_weight_kernel", "", 0.0, 4.0 * dst.numel())
-    L.call("bsed_pack_weight", _fp(_dp(src, src_offset)), L.ptr(dst), _i(ntaps), _i(K), _i(N), _i(NP),
-           ctypes.c_long(s_tap), ctypes.c_long(s_k), ctypes.c_long(s_n), L.stream())
+    L.call("bsed_pack_weight", _dp(src, src_offset), L.ptr(dst), ntaps, K, N, NP, s_tap, s_k, s_n, L.stream())
     return dst
 
 
@@ -238,15 +212,6 @@ _pack_memo = None   # {(kind, data_ptr, args): packed tensor} while an ops.pack_
 _pack_plan = None   # the PackPlan of the open outermost block, if it was given one
 
 
-class BsedPackJob(ctypes.Structure):
-    _fields_ = ([("src", _fp), ("dst", ctypes.c_void_p)]
-                + [(n, _i) for n in ("kind", "ntaps", "K", "N", "NP")]
-                + [(n, ctypes.c_long) for n in ("s_tap", "s_k", "s_n")])
-
-
-PACK_MAX_JOBS = 32   # BSED_PACK_MAX_JOBS
-
-
 class PackPlan:
     """Which packed weight copies a recurring ``pack_cache`` block asked for last time.  The next block given the same
     plan makes ALL of them in one launch on entry (``bsed_pack_weights_batch``) instead of one 5-7 us launch per weight
@@ -284,12 +249,12 @@ class PackPlan:
             jobs.append((src.data_ptr(), dst.data_ptr(), kind, ntaps, K, N, NP, s_tap, s_k, s_n))
         for j0 in range(0, len(jobs), PACK_MAX_JOBS):
             part = jobs[j0:j0 + PACK_MAX_JOBS]
-            arr = (BsedPackJob * len(part))()
+            arr = (PackJob * len(part))()
             for a, (sp, dp, kind, ntaps, K, N, NP, s_tap, s_k, s_n) in zip(arr, part):
                 a.src = sp; a.dst = dp
                 a.kind, a.ntaps, a.K, a.N, a.NP = kind, ntaps, K, N, NP
                 a.s_tap, a.s_k, a.s_n = s_tap, s_k, s_n
-            L.call("bsed_pack_weights_batch", arr, _i(len(part)), stream)
+            L.call("bsed_pack_weights_batch", arr, len(part), stream)
 
     def close(self):
         stream = L.stream().value
@@ -363,8 +328,7 @@ def pack_weight3(src, ntaps, K, N, s_tap, s_k, s_n):
     NP = round_up(N, 32)
     dst = torch.empty((ntaps, K // 32, NP, 64), device=src.device, dtype=torch.int16)
     _note("pack_weight3_kernel", "", 0.0, 4.0 * dst.numel())
-    L.call("bsed_pack_weight3", _fp(_dp(src)), ctypes.c_void_p(dst.data_ptr()), _i(ntaps), _i(K), _i(N), _i(NP),
-           ctypes.c_long(s_tap), ctypes.c_long(s_k), ctypes.c_long(s_n), L.stream())
+    L.call("bsed_pack_weight3", _dp(src), dst.data_ptr(), ntaps, K, N, NP, s_tap, s_k, s_n, L.stream())
     _pack_store(key, dst, src, 0, ntaps, K, N, s_tap, s_k, s_n)
     return dst
 
@@ -378,8 +342,7 @@ def pack_weight3s(src, ntaps, N, s_tap, s_k, s_n, K=16):
     NP = round_up(N, 32)
     dst = torch.empty((NP // 32, ntaps, K // 16, 2, 64, 8), device=src.device, dtype=torch.int16)
     _note("pack_weight3s_kernel", "", 0.0, 4.0 * dst.numel())
-    L.call("bsed_pack_weight3s", _fp(_dp(src)), ctypes.c_void_p(dst.data_ptr()), _i(ntaps), _i(K), _i(N), _i(NP),
-           ctypes.c_long(s_tap), ctypes.c_long(s_k), ctypes.c_long(s_n), L.stream())
+    L.call("bsed_pack_weight3s", _dp(src), dst.data_ptr(), ntaps, K, N, NP, s_tap, s_k, s_n, L.stream())
     _pack_store(key, dst, src, 1, ntaps, K, N, s_tap, s_k, s_n)
     return dst
 
@@ -399,7 +362,7 @@ def igemm3s(inp, wtab, N, NB, H, W, taps, bias=None, epilogue=EPI_PLAIN):
     dev = inp.device
     out = torch.empty((NB, H, W, N), device=dev, dtype=inp.dtype)
     ntiles = NB * ((H + TH - 1) // TH) * (W // TW)
-    G = int(min(ntiles, L.lib().bsed_igemm3s_auto_g2(_i(inp.shape[-1]), _i(N))))
+    G = int(min(ntiles, L.lib().bsed_igemm3s_auto_g2(inp.shape[-1], N)))
     stats = torch.empty((G, 2, N), device=dev, dtype=torch.float32) if epilogue == EPI_STATS else None
     d.act_bf16 = _abf(inp)
     d.in_ = _dp(inp); d.w = wtab.data_ptr(); d.bias = _p(bias); d.out = out.data_ptr(); d.stats = _p(stats)
@@ -415,7 +378,7 @@ def igemm3s(inp, wtab, N, NB, H, W, taps, bias=None, epilogue=EPI_PLAIN):
     d.epilogue = epilogue
     nv = 16 if N <= 16 and N % 4 == 0 else 32                      # transposed epilogue (bsed_igemm3s)
     _launch((f"igemm3s_kernel<{1 if epilogue == EPI_STATS else 0}, {len(taps)}, {CIN // 16}, {nv}, {d.act_bf16}>", len(taps), CIN, N, H, W),
-            2.0 * NB * H * W * len(taps) * CIN * N, lambda: L.call("bsed_igemm3s", ctypes.byref(d), _i(G), L.stream()),
+            2.0 * NB * H * W * len(taps) * CIN * N, lambda: L.call("bsed_igemm3s", ctypes.byref(d), G, L.stream()),
             _esz(inp) * NB * H * W * (CIN + N))
     return out, stats
 
@@ -456,13 +419,13 @@ def igemm3(inp, w3, N, NB, H, W, CIN, taps, bias=None, epilogue=EPI_PLAIN, valid
 
 def set_igemm3n_shape(shape):
     """A/B knob: MFMA shape of the nine-tap N-split instances: 16 (16 x 16 x 32), 32 (32 x 32 x 16), 0 / None = default"""
-    L.lib().bsed_igemm3n_set_shape(_i(shape or 0))
+    L.lib().bsed_igemm3n_set_shape(shape or 0)
 
 
 def set_igemm3n_wpe(wpe):
     """A/B knob of the BN = 128 build: 2 / 3 = built for that many waves per SIMD whatever the shape; + 8 = no raised
     wave priority outside the MFMA loop; 0 / None = default"""
-    L.lib().bsed_igemm3n_set_wpe(_i(wpe or 0))
+    L.lib().bsed_igemm3n_set_wpe(wpe or 0)
 
 
 def _igemm3n(inp, wtab, N, NB, H, W, CIN, taps, bias, epilogue, valid):
@@ -552,13 +515,6 @@ def wgrad(inp, dy, NB, H, W, CIN, N, taps=((0, 0),), in_pitch=None, dy_pitch=Non
     return part, G, CINP, NP
 
 
-class ReduceJob(ctypes.Structure):
-    _fields_ = ([("part", _fp), ("dst", _fp)]
-                + [(n, _i) for n in ("G", "ntaps", "KP", "NP", "K", "N", "accumulate")]
-                + [(n, ctypes.c_long) for n in ("s_tap", "s_k", "s_n")])
-
-
-REDUCE_MAX_JOBS = 40
 _rq = None   # the active queue of deferred reductions: dict(stream=..., jobs=[(ReduceJob fields..., keepalive)])
 
 
@@ -607,7 +563,7 @@ def flush_reductions():
             arr[i].accumulate, arr[i].s_tap, arr[i].s_k, arr[i].s_n = acc, s_tap, s_k, s_n
             nel += part.numel()
         _note("reduce_partials_batch_kernel", f"jobs{len(batch)}", float(nel), 4.0 * nel)
-        L.call("bsed_reduce_partials_batch", arr, _i(len(batch)), L.stream())
+        L.call("bsed_reduce_partials_batch", arr, len(batch), L.stream())
         pending = rest
 
 
@@ -617,9 +573,8 @@ def reduce_partials(part, G, ntaps, KP, NP, K, N, dst, s_tap, s_k, s_n, accumula
         _rq["jobs"].append((part, _dp(dst, dst_offset), G, ntaps, KP, NP, K, N, s_tap, s_k, s_n, 1 if accumulate else 0))
         return
     _note("reduce_partials_kernel", f"G{G}", float(part.numel()), 4.0 * part.numel())
-    L.call("bsed_reduce_partials", L.ptr(part), _i(G), _i(ntaps), _i(KP), _i(NP), _i(K), _i(N),
-           _fp(_dp(dst, dst_offset)), ctypes.c_long(s_tap), ctypes.c_long(s_k), ctypes.c_long(s_n),
-           _i(1 if accumulate else 0), L.stream())
+    L.call("bsed_reduce_partials", L.ptr(part), G, ntaps, KP, NP, K, N, _dp(dst, dst_offset), s_tap, s_k, s_n,
+           1 if accumulate else 0, L.stream())
 
 
 _scratch = {}
@@ -629,9 +584,8 @@ def stats_scratch(C, device):
     key = (C, str(device), L.stream().value)   # one scratch per stream: launches of different streams may overlap
     s = _scratch.get(key)
     if s is None:
-        n = L.lib().bsed_stats_scratch_bytes
-        n.restype = ctypes.c_size_t
-        s = _scratch[key] = torch.empty((n(_i(C)) + 7) // 8, device=device, dtype=torch.float64)
+        s = _scratch[key] = torch.empty((L.lib().bsed_stats_scratch_bytes(C) + 7) // 8, device=device,
+                                        dtype=torch.float64)
     return s
 
 
@@ -642,8 +596,7 @@ def conv0_fwd(x, w, bias, NB, H, W, CO, want_stats):
     if want_stats:
         stats = torch.empty((nt, 2, CO), device=x.device, dtype=torch.float32)
     _note(f"conv0_fwd_kernel<{CO}>", f"{H}x{W}", 2.0 * 9 * CO * NB * H * W, 4.0 * NB * H * W * (1 + CO))
-    L.call("bsed_conv0_fwd", L.ptr(x), _fp(_dp(w)), _fp(_dp(bias)), L.ptr(y), _fp(_p(stats)), _i(NB), _i(H), _i(W),
-           _i(CO), L.stream())
+    L.call("bsed_conv0_fwd", L.ptr(x), _dp(w), _dp(bias), L.ptr(y), _p(stats), NB, H, W, CO, L.stream())
     return y, stats
 
 
@@ -654,8 +607,8 @@ def conv0_wgrad(x, dy, NB, H, W, CO, y=None, coef=None, mean=None):
     # x, dy (= g) and, with the fused BatchNorm backward, y: each read once
     _note(f"conv0_wgrad_kernel<{CO}, {'true' if y is not None else 'false'}>", f"{H}x{W}",
           2.0 * 9 * CO * NB * H * W, 4.0 * NB * H * W * (1 + CO * (2 if y is not None else 1)))
-    L.call("bsed_conv0_wgrad", L.ptr(x), L.ptr(dy), _fp(_p(y)), _fp(_p(coef)), _fp(_p(mean)), L.ptr(part), _i(G),
-           _i(NB), _i(H), _i(W), _i(CO), L.stream())
+    L.call("bsed_conv0_wgrad", L.ptr(x), L.ptr(dy), _p(y), _p(coef), _p(mean), L.ptr(part), G, NB, H, W, CO,
+           L.stream())
     return part, G
 
 
@@ -663,9 +616,8 @@ def glu16_fwd(y, scale, shift, wg, bg, B, H, W, pool, drop_p, rng_stream, seed):
     ph, pw = pool
     out = torch.empty((B, H // ph, W // pw, 16), device=y.device, dtype=torch.float32)
     _note("glu16_fwd_kernel", f"{H}x{W}", 2.0 * B * H * W * 256, 4.0 * B * H * W * 16 * (1.0 + 1.0 / (ph * pw)))
-    L.call("bsed_glu16_fwd", L.ptr(y), L.ptr(scale), L.ptr(shift), _fp(_dp(wg)), _fp(_dp(bg)), L.ptr(out), _i(B), _i(H),
-           _i(W), _i(16), _i(ph), _i(pw), ctypes.c_float(drop_p), ctypes.c_uint32(rng_stream), ctypes.c_uint64(seed),
-           L.stream())
+    L.call("bsed_glu16_fwd", L.ptr(y), L.ptr(scale), L.ptr(shift), _dp(wg), _dp(bg), L.ptr(out), B, H, W, 16,
+           ph, pw, drop_p, rng_stream, seed, L.stream())
     return out
 
 
@@ -679,9 +631,8 @@ def glu16_bwd(y, scale, shift, wg, bg, dpool, B, H, W, pool, drop_p, rng_stream,
     part_db = torch.empty((G, 2, 16), device=dev, dtype=torch.float32)
     part_st = torch.empty((G, 2, 16), device=dev, dtype=torch.float32)
     _note("glu16_bwd_kernel", f"{H}x{W}", 3 * 2.0 * B * H * W * 256, 4.0 * B * H * W * 16 * (2.0 + 1.0 / (ph * pw)))
-    L.call("bsed_glu16_bwd", L.ptr(y), L.ptr(scale), L.ptr(shift), _fp(_dp(wg)), _fp(_dp(bg)), L.ptr(dpool), L.ptr(g),
-           L.ptr(part_dw), L.ptr(part_db), L.ptr(part_st), _i(G), _i(B), _i(H), _i(W), _i(16), _i(ph), _i(pw),
-           ctypes.c_float(drop_p), ctypes.c_uint32(rng_stream), ctypes.c_uint64(seed), L.stream())
+    L.call("bsed_glu16_bwd", L.ptr(y), L.ptr(scale), L.ptr(shift), _dp(wg), _dp(bg), L.ptr(dpool), L.ptr(g),
+           L.ptr(part_dw), L.ptr(part_db), L.ptr(part_st), G, B, H, W, 16, ph, pw, drop_p, rng_stream, seed, L.stream())
     return g, part_dw, part_db, part_st, G
 
 
@@ -694,8 +645,8 @@ def block0_stats(x, cw, cb, NB, H, W):
     xr64 = torch.empty(54, device=dev, dtype=torch.float64)
     _note("b0_stats_kernel", f"{H}x{W}", 2.0 * NB * H * W * (9 * 16 + 16 + 54), 4.0 * NB * H * W)
     cwt = cw.detach().reshape(16, 9).t().contiguous()   # [tap][channel]: channel pairs become packed scalar operands
-    L.call("bsed_block0_stats", L.ptr(x), L.ptr(cwt), _fp(_dp(cb)), L.ptr(stats), L.ptr(xr_part),
-           L.ptr(xr64, torch.float64), _i(G), _i(NB), _i(H), _i(W), _i(16), L.stream())
+    L.call("bsed_block0_stats", L.ptr(x), L.ptr(cwt), _dp(cb), L.ptr(stats), L.ptr(xr_part),
+           L.ptr(xr64, torch.float64), G, NB, H, W, 16, L.stream())
     return stats, xr64
 
 
@@ -706,9 +657,8 @@ def block0_fwd(x, cw, cb, scale, shift, wg, bg, B, H, W, pool, drop_p, rng_strea
     small = "false" if ab else ("true" if B * H * W < (1 << 28) else "false")
     _note(f"b0_fwd_kernel<{ph}, {small}, {ab}>", f"{H}x{W}", 2.0 * B * H * W * (9 * 16 + 256),
           B * H * W * (4.0 + _esz(out) * 16.0 / (ph * pw)))
-    L.call("bsed_block0_fwd", L.ptr(x), _fp(_dp(cw)), _fp(_dp(cb)), L.ptr(scale), L.ptr(shift), _fp(_dp(wg)),
-           _fp(_dp(bg)), _pa(out), _i(B), _i(H), _i(W), _i(16), _i(ph), _i(pw), ctypes.c_float(drop_p),
-           ctypes.c_uint32(rng_stream), ctypes.c_uint64(seed), _i(ab), L.stream())
+    L.call("bsed_block0_fwd", L.ptr(x), _dp(cw), _dp(cb), L.ptr(scale), L.ptr(shift), _dp(wg), _dp(bg), _pa(out), B,
+           H, W, 16, ph, pw, drop_p, rng_stream, seed, ab, L.stream())
     return out
 
 
@@ -724,17 +674,16 @@ def block0_bwd(x, cw, cb, scale, shift, wg, bg, dpool, B, H, W, pool, drop_p, rn
     ab = _abf(dpool)
     _note(f"b0_bwd_kernel<{ph}, {'true' if B * H * W < (1 << 28) else 'false'}, {ab}>", f"{H}x{W}", 2.0 * B * H * W * (2 * 9 * 16 + 3 * 256),
           B * H * W * (4.0 + _esz(dpool) * 16.0 / (ph * pw)))
-    L.call("bsed_block0_bwd", L.ptr(x), _fp(_dp(cw)), _fp(_dp(cb)), L.ptr(scale), L.ptr(shift), _fp(_dp(wg)),
-           _fp(_dp(bg)), _pa(dpool), L.ptr(part_dw), L.ptr(part_db), L.ptr(part_st), L.ptr(part_gx), _i(G), _i(B),
-           _i(H), _i(W), _i(16), _i(ph), _i(pw), ctypes.c_float(drop_p), ctypes.c_uint32(rng_stream),
-           ctypes.c_uint64(seed), _i(ab), L.stream())
+    L.call("bsed_block0_bwd", L.ptr(x), _dp(cw), _dp(cb), L.ptr(scale), L.ptr(shift), _dp(wg), _dp(bg), _pa(dpool),
+           L.ptr(part_dw), L.ptr(part_db), L.ptr(part_st), L.ptr(part_gx), G, B, H, W, 16, ph, pw, drop_p, rng_stream,
+           seed, ab, L.stream())
     return part_dw, part_db, part_st, part_gx, G
 
 
 def block0_wgrad_finish(part_gx, G, xr64, coef, mean, cw, cb, dst, accumulate=True):
     _note("b0_wgrad_finish_kernel", f"G{G}", float(part_gx.numel()), 4.0 * part_gx.numel())
-    L.call("bsed_block0_wgrad_finish", L.ptr(part_gx), _i(G), L.ptr(xr64, torch.float64), L.ptr(coef), L.ptr(mean),
-           _fp(_dp(cw)), _fp(_dp(cb)), _fp(_dp(dst)), _i(1 if accumulate else 0), _i(16), L.stream())
+    L.call("bsed_block0_wgrad_finish", L.ptr(part_gx), G, L.ptr(xr64, torch.float64), L.ptr(coef), L.ptr(mean),
+           _dp(cw), _dp(cb), _dp(dst), 1 if accumulate else 0, 16, L.stream())
 
 
 def glu_bwd_fused(y, scale, shift, wfwd, w, bias, dpool, B, H, W, C, pool, drop_p, rng_stream, seed):
@@ -752,10 +701,9 @@ def glu_bwd_fused(y, scale, shift, wfwd, w, bias, dpool, B, H, W, C, pool, drop_
     flops = 3 * 2.0 * B * H * W * C * C
     nbytes = 4.0 * B * H * W * C * (2.0 + 1.0 / (ph * pw))  # y, g, d_pooled
     _launch((f"glu_bwd_fused_kernel<{C}, {8 if C == 128 else 4}>", 1, C, C, H, W), flops,
-            lambda: L.call("bsed_glu_bwd_fused", L.ptr(y), L.ptr(scale), L.ptr(shift), L.ptr(wfwd), _fp(_dp(w)),
-                           _fp(_dp(bias)), L.ptr(dpool), L.ptr(g), L.ptr(part_dw), L.ptr(part_db), L.ptr(part_st),
-                           _i(G), _i(B), _i(H), _i(W), _i(C), _i(TH), _i(TW), _i(ph), _i(pw), ctypes.c_float(drop_p),
-                           ctypes.c_uint32(rng_stream), ctypes.c_uint64(seed), L.stream()), nbytes)
+            lambda: L.call("bsed_glu_bwd_fused", L.ptr(y), L.ptr(scale), L.ptr(shift), L.ptr(wfwd), _dp(w),
+                           _dp(bias), L.ptr(dpool), L.ptr(g), L.ptr(part_dw), L.ptr(part_db), L.ptr(part_st),
+                           G, B, H, W, C, TH, TW, ph, pw, drop_p, rng_stream, seed, L.stream()), nbytes)
     return g, part_dw, part_db, part_st, G, slabs
 
 
@@ -774,9 +722,8 @@ def glu_fwd3(y, scale, shift, w, bias, B, H, W, C, pool, drop_p, rng_stream, see
     out = torch.empty((B, H // ph, W // pw, C), device=y.device, dtype=y.dtype)
     ab = _abf(y)
     _launch((f"glu_fwd3_kernel<{C}, {4 if TW == 16 else -1}, {ab}>", 1, C, C, H, W), 2.0 * B * H * W * C * C,
-            lambda: L.call("bsed_glu_fwd3", _pa(y), L.ptr(scale), L.ptr(shift), _fp(_dp(w)), _fp(_dp(bias)),
-                           _pa(out), _i(G), _i(B), _i(H), _i(W), _i(C), _i(TH), _i(TW), _i(ph), _i(pw),
-                           ctypes.c_float(drop_p), ctypes.c_uint32(rng_stream), ctypes.c_uint64(seed), _i(ab), L.stream()),
+            lambda: L.call("bsed_glu_fwd3", _pa(y), L.ptr(scale), L.ptr(shift), _dp(w), _dp(bias),
+                           _pa(out), G, B, H, W, C, TH, TW, ph, pw, drop_p, rng_stream, seed, ab, L.stream()),
             _esz(y) * B * H * W * C * (1.0 + 1.0 / (ph * pw)))  # y, pooled
     return out
 
@@ -796,10 +743,9 @@ def glu_bwd3(y, scale, shift, w, bias, dpool, B, H, W, C, pool, drop_p, rng_stre
     flops = 3 * 2.0 * B * H * W * C * C
     ab = _abf(y, dpool)
     _launch((f"glu_bwd3_kernel<{C}, {4 if TW == 16 else -1}, {ab}>", 1, C, C, H, W), flops,
-            lambda: L.call("bsed_glu_bwd3", _pa(y), L.ptr(scale), L.ptr(shift), _fp(_dp(w)), _fp(_dp(bias)),
-                           _pa(dpool), _pa(g), L.ptr(part_dw), L.ptr(part_db), L.ptr(part_st), _i(G), _i(B), _i(H),
-                           _i(W), _i(C), _i(TH), _i(TW), _i(ph), _i(pw), ctypes.c_float(drop_p),
-                           ctypes.c_uint32(rng_stream), ctypes.c_uint64(seed), _i(ab), L.stream()),
+            lambda: L.call("bsed_glu_bwd3", _pa(y), L.ptr(scale), L.ptr(shift), _dp(w), _dp(bias),
+                           _pa(dpool), _pa(g), L.ptr(part_dw), L.ptr(part_db), L.ptr(part_st), G, B, H,
+                           W, C, TH, TW, ph, pw, drop_p, rng_stream, seed, ab, L.stream()),
             _esz(y) * B * H * W * C * (2.0 + 1.0 / (ph * pw)))  # y, g, d_pooled
     return g, part_dw, part_db, part_st, G, slabs
 
@@ -816,20 +762,16 @@ def glu_bwd3n(y, scale, shift, w, bias, dpool, B, H, W, C, pool, drop_p, rng_str
     G = int(min((ntiles + 1) // 2, 256))  # 8-wave workgroups take two tiles at a time
     tb = _frag_tables.get(str(dev))
     if tb is None:
-        fn = L.lib().bsed_glu_bwd3n_table_bytes
-        fn.restype = ctypes.c_size_t
-        tb = _frag_tables[str(dev)] = torch.empty(fn(), device=dev, dtype=torch.uint8)
+        tb = _frag_tables[str(dev)] = torch.empty(L.lib().bsed_glu_bwd3n_table_bytes(), device=dev, dtype=torch.uint8)
     g = torch.empty_like(y)
     dlin = torch.empty_like(y)
     part_db = torch.empty((G, 2, C), device=dev, dtype=torch.float32)
     part_st = torch.empty((G, 2, C), device=dev, dtype=torch.float32)
     ab = _abf(y, dpool)
     _launch((f"glu_bwd3n_kernel<{ab}>", 1, C, C, H, W), 2 * 2.0 * B * H * W * C * C,
-            lambda: L.call("bsed_glu_bwd3n", _pa(y), L.ptr(scale), L.ptr(shift), _fp(_dp(w)), _fp(_dp(bias)),
+            lambda: L.call("bsed_glu_bwd3n", _pa(y), L.ptr(scale), L.ptr(shift), _dp(w), _dp(bias),
                            _pa(dpool), _pa(g), _pa(dlin), L.ptr(part_db), L.ptr(part_st),
-                           ctypes.c_void_p(tb.data_ptr()), _i(G), _i(B), _i(H), _i(W), _i(C), _i(TH), _i(TW), _i(ph),
-                           _i(pw), ctypes.c_float(drop_p), ctypes.c_uint32(rng_stream), ctypes.c_uint64(seed),
-                           _i(ab), L.stream()),
+                           tb.data_ptr(), G, B, H, W, C, TH, TW, ph, pw, drop_p, rng_stream, seed, ab, L.stream()),
             _esz(y) * B * H * W * C * (3.0 + 1.0 / (ph * pw)))  # y, g, d_lin, d_pooled
     return g, dlin, part_db, part_st, G
 
@@ -838,9 +780,8 @@ def bn_finalize(stats, C, count, eps, momentum, gamma, beta, rmean, rvar, nbt):
     dev = stats.device
     mean, invstd, scale, shift = (torch.empty(C, device=dev, dtype=torch.float32) for _ in range(4))
     _note("stats_chunk_kernel+stats_finish_kernel", f"C{C}", 0.0, 4.0 * stats.numel())
-    L.call("bsed_bn_finalize", L.ptr(stats), ctypes.c_long(stats.shape[0]), _i(C), ctypes.c_double(count),
-           ctypes.c_float(eps), ctypes.c_float(momentum), _fp(_dp(gamma)), _fp(_dp(beta)), _fp(_dp(rmean)),
-           _fp(_dp(rvar)), _fp(None if nbt is None else nbt.data_ptr()), L.ptr(mean), L.ptr(invstd), L.ptr(scale),
+    L.call("bsed_bn_finalize", L.ptr(stats), stats.shape[0], C, count, eps, momentum, _dp(gamma), _dp(beta), _dp(rmean),
+           _dp(rvar), _dp(nbt), L.ptr(mean), L.ptr(invstd), L.ptr(scale),
            L.ptr(shift), L.ptr(stats_scratch(C, dev), torch.float64), L.stream())
     return mean, invstd, scale, shift
 
@@ -848,20 +789,16 @@ def bn_finalize(stats, C, count, eps, momentum, gamma, beta, rmean, rvar, nbt):
 def bn_eval(C, eps, gamma, beta, rmean, rvar):
     dev = gamma.device
     scale, shift = (torch.empty(C, device=dev, dtype=torch.float32) for _ in range(2))
-    L.call("bsed_bn_eval", _i(C), ctypes.c_float(eps), _fp(_dp(gamma)), _fp(_dp(beta)), _fp(_dp(rmean)),
-           _fp(_dp(rvar)), L.ptr(scale), L.ptr(shift), L.stream())
+    L.call("bsed_bn_eval", C, eps, _dp(gamma), _dp(beta), _dp(rmean), _dp(rvar), L.ptr(scale), L.ptr(shift),
+           L.stream())
     return scale, shift
-
-
-class BsedBnEvalJob(ctypes.Structure):
-    _fields_ = [(n, _fp) for n in ("gamma", "beta", "running_mean", "running_var", "scale", "shift")] + [("C", _i)]
 
 
 def bn_eval_batch(layers, eps):
     """[(C, gamma, beta, running_mean, running_var), ...] -> [(scale, shift), ...] in one launch (eval-mode forward)"""
     dev = layers[0][1].device
     out = torch.empty(2 * sum(l[0] for l in layers), device=dev, dtype=torch.float32)
-    arr = (BsedBnEvalJob * len(layers))()
+    arr = (BnEvalJob * len(layers))()
     res, off = [], 0
     for a, (C, gamma, beta, rmean, rvar) in zip(arr, layers):
         scale, shift = out[off:off + C], out[off + C:off + 2 * C]
@@ -870,7 +807,7 @@ def bn_eval_batch(layers, eps):
         a.scale, a.shift, a.C = scale.data_ptr(), shift.data_ptr(), C
         res.append((scale, shift))
     _note("bn_eval_batch_kernel", "", 0.0, 4.0 * 3 * out.numel())
-    L.call("bsed_bn_eval_batch", arr, _i(len(layers)), ctypes.c_float(eps), L.stream())
+    L.call("bsed_bn_eval_batch", arr, len(layers), eps, L.stream())
     return res
 
 
@@ -881,10 +818,10 @@ def bn_bwd(stats, C, count, gamma, mean, invstd, dgamma, dbeta, g_inout, y, appl
     coef = torch.empty((3, C), device=dev, dtype=torch.float32)
     _note("bn_bwd_apply_kernel" if apply else "stats_chunk_kernel+stats_finish_kernel", f"C{C}", 3.0 * y.numel() if apply else 0.0,
           12.0 * y.numel() if apply else 4.0 * stats.numel())
-    L.call("bsed_bn_bwd", L.ptr(stats), ctypes.c_long(stats.shape[0]), _i(C), ctypes.c_double(count), _fp(_dp(gamma)),
-           L.ptr(mean), L.ptr(invstd), _fp(_dp(dgamma)), _fp(_dp(dbeta)), _i(1),
+    L.call("bsed_bn_bwd", L.ptr(stats), stats.shape[0], C, count, _dp(gamma), L.ptr(mean), L.ptr(invstd), _dp(dgamma),
+           _dp(dbeta), 1,
            L.ptr(g_inout) if apply else None, L.ptr(y) if apply else None,
-           ctypes.c_long(y.numel() if apply else C), L.ptr(coef), L.ptr(stats_scratch(C, dev), torch.float64),
+           y.numel() if apply else C, L.ptr(coef), L.ptr(stats_scratch(C, dev), torch.float64),
            L.stream())
     return coef
 
@@ -895,7 +832,7 @@ def stats_to_grad(stats, C, which, dst):
         _rq["jobs"].append((stats, _dp(dst), stats.shape[0], 1, 2, C, 1, C, 0, 0, 1, 1))
         return
     _note("stats_chunk_kernel+stats_finish_kernel", f"C{C}", 0.0, 4.0 * stats.numel())
-    L.call("bsed_stats_to_grad", L.ptr(stats), ctypes.c_long(stats.shape[0]), _i(C), _i(which), _fp(_dp(dst)), _i(1),
+    L.call("bsed_stats_to_grad", L.ptr(stats), stats.shape[0], C, which, _dp(dst), 1,
            L.ptr(stats_scratch(C, stats.device), torch.float64), L.stream())
 
 
@@ -904,19 +841,18 @@ def colsum(inp, M, C, pitch, dst, accumulate=True, in_offset=0):
     part = torch.empty((G, 2, C), device=inp.device, dtype=torch.float32)
     _note("colsum_kernel", f"C{C}", float(M) * C, 4.0 * M * C)
     if _rq is not None and _rq["stream"] == L.stream().value:
-        L.call("bsed_colsum_part", _fp(_dp(inp, in_offset)), ctypes.c_long(M), _i(C), _i(pitch), L.ptr(part), _i(G),
+        L.call("bsed_colsum_part", _dp(inp, in_offset), M, C, pitch, L.ptr(part), G,
                L.stream())
         _rq["jobs"].append((part, _dp(dst), G, 1, 2, C, 1, C, 0, 0, 1, 1 if accumulate else 0))
         return
-    L.call("bsed_colsum", _fp(_dp(inp, in_offset)), ctypes.c_long(M), _i(C), _i(pitch), L.ptr(part), _i(G),
-           _fp(_dp(dst)), _i(1 if accumulate else 0), L.ptr(stats_scratch(C, inp.device), torch.float64), L.stream())
+    L.call("bsed_colsum", _dp(inp, in_offset), M, C, pitch, L.ptr(part), G,
+           _dp(dst), 1 if accumulate else 0, L.ptr(stats_scratch(C, inp.device), torch.float64), L.stream())
 
 
 def dropout(x, p, rng_stream, seed):
     out = torch.empty_like(x)
     _note("dropout_kernel", "", float(x.numel()), 8.0 * x.numel())
-    L.call("bsed_dropout", L.ptr(x), L.ptr(out), ctypes.c_long(x.numel()), ctypes.c_float(p),
-           ctypes.c_uint32(rng_stream), ctypes.c_uint64(seed), L.stream())
+    L.call("bsed_dropout", L.ptr(x), L.ptr(out), x.numel(), p, rng_stream, seed, L.stream())
     return out
 
 
@@ -931,11 +867,11 @@ def gru_fwd(xp, w_hh, b_hh, B, T, save_gates, mode="fp32"):
     _note("gru_fwd_mfma_kernel<true>" if mode == "bf16x3" else "gru_fwd_kernel", f"T{T}", 2.0 * B * T * 2 * 128 * 384,
           4.0 * B * T * (768 + 256 + (1024 if save_gates else 0)))
     if mode == "bf16x3":  # matrix-core recurrence, split-fp32 operands
-        L.call("bsed_gru_fwd3", L.ptr(xp), _fp(_dp(w_hh)), _fp(_dp(b_hh)), L.ptr(out), _fp(_p(gates)), _i(B), _i(T),
+        L.call("bsed_gru_fwd3", L.ptr(xp), _dp(w_hh), _dp(b_hh), L.ptr(out), _p(gates), B, T,
                L.stream())
     else:
-        L.call("bsed_gru_fwd", L.ptr(xp), _fp(_dp(w_hh)), _fp(_dp(b_hh)), L.ptr(out), _fp(_p(gates)), _i(B), _i(T),
-               _i(gru_rows(B)), L.stream())
+        L.call("bsed_gru_fwd", L.ptr(xp), _dp(w_hh), _dp(b_hh), L.ptr(out), _p(gates), B, T, gru_rows(B),
+               L.stream())
     return out, gates
 
 
@@ -948,12 +884,12 @@ def gru_bwd(dout, out, gates, w_hh, B, T, mode="fp32"):
         rows = L.lib().bsed_gru_bwd3_rows(B)
         pih = torch.empty((rows, 768), device=dout.device, dtype=torch.float32)
         phh = torch.empty((rows, 768), device=dout.device, dtype=torch.float32)
-        L.call("bsed_gru_bwd3", L.ptr(dout), L.ptr(out), L.ptr(gates), _fp(_dp(w_hh)), L.ptr(dxp), L.ptr(dgh),
-               L.ptr(pih), L.ptr(phh), _i(B), _i(T), L.stream())
+        L.call("bsed_gru_bwd3", L.ptr(dout), L.ptr(out), L.ptr(gates), _dp(w_hh), L.ptr(dxp), L.ptr(dgh),
+               L.ptr(pih), L.ptr(phh), B, T, L.stream())
         return dxp, dgh, pih, phh
     else:
-        L.call("bsed_gru_bwd", L.ptr(dout), L.ptr(out), L.ptr(gates), _fp(_dp(w_hh)), L.ptr(dxp), L.ptr(dgh), _i(B),
-               _i(T), _i(gru_rows(B)), L.stream())
+        L.call("bsed_gru_bwd", L.ptr(dout), L.ptr(out), L.ptr(gates), _dp(w_hh), L.ptr(dxp), L.ptr(dgh), B, T,
+               gru_rows(B), L.stream())
     return dxp, dgh, None, None
 
 
@@ -963,7 +899,7 @@ def max_over_time(y):
     B, T, C = y.shape
     out = torch.empty((B, C), device=y.device, dtype=torch.float32)
     _note("max_over_time_kernel", f"T{T}", 0.0, 4.0 * (y.numel() + out.numel()))
-    L.call("bsed_max_over_time", L.ptr(y), L.ptr(out), _i(B), _i(T), _i(C), L.stream())
+    L.call("bsed_max_over_time", L.ptr(y), L.ptr(out), B, T, C, L.stream())
     return out
 
 
@@ -976,8 +912,8 @@ def head_fwd(x, w, b, B, T, K, C, attention):
     S = L.lib().bsed_head_splits(B, T)
     part = torch.empty((B, S, 2, C), device=dev, dtype=torch.float32) if S > 1 else None
     _note(f"head_fwd_kernel<{C}>", f"T{T}", 2.0 * B * T * K * 2 * C, 4.0 * B * T * (K + 2 * C))
-    L.call("bsed_head_fwd", L.ptr(x), _fp(_dp(w)), _fp(_dp(b)), L.ptr(strong), L.ptr(sof), L.ptr(weak), L.ptr(den),
-           L.ptr(part), _i(B), _i(T), _i(K), _i(C), _i(1 if attention else 0), L.stream())
+    L.call("bsed_head_fwd", L.ptr(x), _dp(w), _dp(b), L.ptr(strong), L.ptr(sof), L.ptr(weak), L.ptr(den), L.ptr(part),
+           B, T, K, C, 1 if attention else 0, L.stream())
     return strong, sof, weak, den
 
 
@@ -1014,49 +950,45 @@ def tag_head_fwd(x, logits):
     weak = torch.empty((B, C), device=x.device, dtype=torch.float32)
     part = torch.empty((B, S, 2, C), device=x.device, dtype=torch.float32)
     _note("tag_pool_kernel", f"T{T}", 12.0 * B * T * C, 12.0 * B * T * C)
-    L.call("bsed_tag_head_fwd", L.ptr(x), L.ptr(logits), L.ptr(strong), L.ptr(weak), L.ptr(part), _i(B), _i(T), _i(C),
-           L.stream())
+    L.call("bsed_tag_head_fwd", L.ptr(x), L.ptr(logits), L.ptr(strong), L.ptr(weak), L.ptr(part), B, T, C, L.stream())
     return strong, weak
 
 
 def adam_step(p, g, m, v, lr, step, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_scale=1.0):
     _note("adam_kernel", "", 12.0 * p.numel(), 28.0 * p.numel())
-    L.call("bsed_adam_step", L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), ctypes.c_long(p.numel()), ctypes.c_float(lr),
-           ctypes.c_float(betas[0]), ctypes.c_float(betas[1]), ctypes.c_float(eps), ctypes.c_float(weight_decay),
-           ctypes.c_long(step), ctypes.c_float(grad_scale), L.stream())
+    L.call("bsed_adam_step", L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), p.numel(), lr, betas[0], betas[1], eps,
+           weight_decay, step, grad_scale, L.stream())
 
 
 def sgd_step(p, g, buf, lr, momentum, weight_decay, first_step, nesterov=True, grad_scale=1.0):
     _note("sgd_kernel", "", 6.0 * p.numel(), 20.0 * p.numel())
-    L.call("bsed_sgd_step", L.ptr(p), L.ptr(g), L.ptr(buf), ctypes.c_long(p.numel()), ctypes.c_float(lr),
-           ctypes.c_float(momentum), ctypes.c_float(weight_decay), _i(1 if first_step else 0),
-           _i(1 if nesterov else 0), ctypes.c_float(grad_scale), L.stream())
+    L.call("bsed_sgd_step", L.ptr(p), L.ptr(g), L.ptr(buf), p.numel(), lr, momentum, weight_decay,
+           1 if first_step else 0, 1 if nesterov else 0, grad_scale, L.stream())
 
 
 def roll(x, B, H, W, sh=None, sw=None):
     """per-sample torch.roll of a contiguous (B,H,W[,..]) tensor viewed as (B,H,W); sh/sw: int32 device tensors (B)"""
     out = torch.empty_like(x)
     _note("roll_kernel", "", 0.0, 8.0 * x.numel())
-    L.call("bsed_roll", L.ptr(x), L.ptr(out), _i(B), _i(H), _i(W), L.ptr(sh, torch.int32), L.ptr(sw, torch.int32),
-           L.stream())
+    L.call("bsed_roll", L.ptr(x), L.ptr(out), B, H, W, L.ptr(sh, torch.int32), L.ptr(sw, torch.int32), L.stream())
     return out
 
 
 def axpy(y, x, a=1.0):
     """y += a * x in place (contiguous fp32 tensors of equal size)"""
     _note("axpy_kernel", "", 2.0 * y.numel(), 12.0 * y.numel())
-    L.call("bsed_axpy", L.ptr(y), L.ptr(x.contiguous()), ctypes.c_long(y.numel()), ctypes.c_float(a), L.stream())
+    L.call("bsed_axpy", L.ptr(y), L.ptr(x.contiguous()), y.numel(), a, L.stream())
     return y
 
 
 def ema_update(ema, p, alpha):
     _note("ema_kernel", "", 3.0 * p.numel(), 12.0 * p.numel())
-    L.call("bsed_ema_update", L.ptr(ema), L.ptr(p), ctypes.c_long(p.numel()), ctypes.c_float(alpha), L.stream())
+    L.call("bsed_ema_update", L.ptr(ema), L.ptr(p), p.numel(), alpha, L.stream())
 
 
 def ema_update_i64(ema, p, alpha):
-    L.call("bsed_ema_update_i64", L.ptr(ema, torch.int64), L.ptr(p, torch.int64), _i(p.numel()),
-           ctypes.c_float(alpha), L.stream())
+    L.call("bsed_ema_update_i64", L.ptr(ema, torch.int64), L.ptr(p, torch.int64), p.numel(), alpha,
+           L.stream())
 
 
 def upsample_time(inp, T_out, out=None, out_offset=0):
@@ -1065,8 +997,8 @@ def upsample_time(inp, T_out, out=None, out_offset=0):
     B, T_in, C = inp.shape
     if out is None:
         out = torch.empty((B, T_out, C), device=inp.device, dtype=torch.float32)
-    L.call("bsed_upsample_time_fwd", L.ptr(inp), _fp(_dp(out, out_offset)), _i(B), _i(T_in), _i(T_out), _i(C),
-           _i(inp.shape[2]), _i(out.shape[2]), L.stream())
+    L.call("bsed_upsample_time_fwd", L.ptr(inp), _dp(out, out_offset), B, T_in, T_out, C, inp.shape[2], out.shape[2],
+           L.stream())
     return out
 
 
@@ -1074,6 +1006,5 @@ def upsample_time_bwd(dout, T_in, C, in_offset=0):
     """adjoint of upsample_time: dout (B,T_out,P) columns in_offset..in_offset+C -> (B,T_in,C)"""
     B, T_out, P = dout.shape
     din = torch.empty((B, T_in, C), device=dout.device, dtype=torch.float32)
-    L.call("bsed_upsample_time_bwd", _fp(_dp(dout, in_offset)), L.ptr(din), _i(B), _i(T_in), _i(T_out), _i(C), _i(P),
-           _i(C), L.stream())
+    L.call("bsed_upsample_time_bwd", _dp(dout, in_offset), L.ptr(din), B, T_in, T_out, C, P, C, L.stream())
     return din

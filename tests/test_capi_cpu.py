@@ -1,7 +1,12 @@
 """CPU-side checks of the drop-in boundary: the shared library builds, loads and exports every
-symbol include/bsed.h declares.  No compute call is made here (no GPU in this tier)."""
+symbol include/bsed.h declares, and the binding _lib.py derives from the header agrees with it (argument and return
+types, struct layouts and constants as the C compiler sees them).  No compute call is made here (no GPU in this tier)."""
 import ctypes
+import keyword
 import os
+import re
+import shutil
+import subprocess
 
 import pytest
 
@@ -38,3 +43,70 @@ def test_no_cpu_fallback():
     from bsed_amd.features import MelFrontEnd
     with pytest.raises(L.BsedError):
         MelFrontEnd()
+
+
+def _prototypes():
+    """(name, return type text, [parameter texts]) of every prototype in include/bsed.h, by a scan of its own"""
+    txt = re.sub(r"/\*.*?\*/", " ", open(L.HEADER_PATH).read(), flags=re.S)
+    out = []
+    for ret, name, params in re.findall(r"([\w *]+?)\s*\b(bsed_\w+)\s*\(([^()]*)\)\s*;", txt):
+        params = " ".join(params.split())
+        out.append((name, re.sub(r"\s*\*", "*", " ".join(ret.split())), [] if params == "void" else params.split(",")))
+    return out
+
+
+def test_every_prototype_is_bound_from_the_header():
+    scalars = {"int": ctypes.c_int, "long": ctypes.c_long, "long long": ctypes.c_longlong, "size_t": ctypes.c_size_t,
+               "float": ctypes.c_float, "double": ctypes.c_double, "uint32_t": ctypes.c_uint32,
+               "uint64_t": ctypes.c_uint64}
+    protos = _prototypes()
+    assert sorted(n for n, _, _ in protos) == L.header_symbols() and len(protos) > 90
+    lib = L.lib()
+    for name, ret, params in protos:
+        fn = getattr(lib, name)
+        want_ret = None if ret == "void" else ctypes.c_char_p if ret == "const char*" else scalars[ret]
+        assert fn.restype is want_ret, (name, ret, fn.restype)
+        want = [ctypes.c_void_p if "*" in p else scalars[" ".join(p.split()[:-1])] for p in params]
+        assert fn.argtypes == want, (name, params, fn.argtypes)
+
+
+@pytest.mark.skipif(not (shutil.which("cc") or shutil.which("gcc")), reason="no host C compiler")
+def test_struct_layouts_and_constants_match_the_c_compiler(tmp_path):
+    assert set(L.STRUCTS) == {"BsedMelCfg", "BsedIgemmDesc", "BsedPackJob", "BsedWgradDesc", "BsedReduceJob",
+                              "BsedBnEvalJob", "BsedHeadBwdDesc"}
+    assert {"BSED_EPI_PLAIN", "BSED_EPI_STATS", "BSED_EPI_GLU_POOL", "BSED_EPI_GLU_BWD", "BSED_EPI_ADD_STATS2",
+            "BSED_PACK_MAX_JOBS", "BSED_REDUCE_MAX_JOBS", "BSED_BN_EVAL_MAX_JOBS"} <= set(L.CONSTANTS)
+    lines, want = [], []
+    for sname, S in L.STRUCTS.items():
+        lines.append(f'printf("S {sname} %zu\\n", sizeof({sname}));')
+        want.append(f"S {sname} {ctypes.sizeof(S)}")
+        for fname, _ in S._fields_:
+            c = fname[:-1] if fname.endswith("_") and keyword.iskeyword(fname[:-1]) else fname
+            lines.append(f'printf("F {sname}.{fname} %zu %zu\\n", offsetof({sname}, {c}), sizeof((({sname}*)0)->{c}));')
+            f = getattr(S, fname)
+            want.append(f"F {sname}.{fname} {f.offset} {f.size}")
+    for k, v in L.CONSTANTS.items():
+        lines.append(f'printf("K {k} %lld\\n", (long long)({k}));')
+        want.append(f"K {k} {v}")
+    src = tmp_path / "layout.c"
+    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "bsed.h"\nint main(void) {\n  '
+                   + "\n  ".join(lines) + "\n  return 0;\n}\n")
+    exe = str(tmp_path / "layout")
+    cc = shutil.which("cc") or shutil.which("gcc")
+    subprocess.run([cc, "-std=c11", "-I", os.path.dirname(L.HEADER_PATH), str(src), "-o", exe], check=True, timeout=120)
+    got = subprocess.run([exe], check=True, capture_output=True, text=True, timeout=60).stdout.splitlines()
+    assert got == want
+
+
+def test_wrong_argument_type_fails_before_the_library():
+    with pytest.raises(ctypes.ArgumentError):
+        L.lib().bsed_mel_linear(None, None, 1.5, 32000, None, None, None, None, None)   # float for `int B`
+
+
+def test_header_parser_refuses_what_it_does_not_know(tmp_path):
+    for decl in ("int bsed_f(short n);", "typedef struct BsedX { unsigned n; } BsedX;", "int (*bsed_g)(int);",
+                 "#define BSED_NAME \"text\""):
+        h = tmp_path / "h.h"
+        h.write_text(decl + "\n")
+        with pytest.raises(L.BsedError):
+            L.parse_header(str(h))
