@@ -138,6 +138,47 @@ template <int ABF> __device__ __forceinline__ void act_st4(float* base, size_t i
 
 static inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 
+// log2 of a power of two, -1 for anything else
+static inline int ilog2_exact(int v) {
+  int l = 0;
+  while ((1 << l) < v) ++l;
+  return (1 << l) == v ? l : -1;
+}
+
+// Host side of every tiled contraction (bsed_igemm, bsed_igemm3, bsed_igemm3s, bsed_igemm3n, bsed_wgrad*): checks the
+// shape, tile, tap, input-pitch and padding fields that BsedIgemmDesc and BsedWgradDesc share (P.d, already copied
+// from the caller's descriptor) and fills the geometry the kernels derive their addresses from: P.lgTW, d.tilesH,
+// d.tilesW, P.PW / PH / PP (the tile plus its halo) and P.pw_magic (pos / PW == (pos * pw_magic) >> 20 for every
+// position of the patch, verified here).  `who` = the entry point, for the messages; cin_mult = what CIN must be a
+// multiple of; pitch_align = what in_pitch must be a multiple of (elements).  Returns the number of position tiles
+// (below 2^31) or BSED_ERR_ARG; makes no HIP call.
+template <class Params>
+static int bsed_tile_geometry(Params& P, const char* who, int cin_mult, int pitch_align) {
+  auto& d = P.d;
+  BSED_CHECK_ARG(d.NB > 0 && d.H > 0 && d.W > 0 && d.CIN > 0 && d.N > 0, "%s: bad shape", who);
+  BSED_CHECK_ARG(d.CIN % cin_mult == 0, "%s: CIN must be a multiple of %d", who, cin_mult);
+  BSED_CHECK_ARG(d.TH * d.TW == 128, "%s: TH*TW must be 128 (got %dx%d)", who, d.TH, d.TW);
+  P.lgTW = ilog2_exact(d.TW);
+  BSED_CHECK_ARG(P.lgTW >= 0, "%s: TW must be a power of two", who);
+  BSED_CHECK_ARG(d.W % d.TW == 0, "%s: TW must divide W", who);
+  BSED_CHECK_ARG(d.ntaps >= 1 && d.ntaps <= 9, "%s: ntaps must be in 1..9", who);
+  for (int t = 0; t < d.ntaps; ++t)
+    BSED_CHECK_ARG(abs(d.dh[t]) <= d.hh && abs(d.dw[t]) <= d.hw, "%s: tap %d outside the halo", who, t);
+  BSED_CHECK_ARG(d.in_pitch >= d.CIN && d.in_pitch % pitch_align == 0, "%s: bad pitch", who);
+  BSED_CHECK_ARG(d.NP % 32 == 0 && d.NP >= d.N, "%s: NP must be N rounded up to 32", who);
+  d.tilesH = ceil_div(d.H, d.TH);
+  d.tilesW = d.W / d.TW;
+  P.PW = d.TW + 2 * d.hw;
+  P.PH = d.TH + 2 * d.hh;
+  P.PP = P.PW * P.PH;
+  P.pw_magic = ((1 << 20) + P.PW - 1) / P.PW;
+  for (int pos = 0; pos < P.PP; ++pos)
+    BSED_CHECK_ARG(((pos * P.pw_magic) >> 20) == pos / P.PW, "%s: internal: magic division fails for PW=%d", who, P.PW);
+  const long ntiles = (long)d.NB * d.tilesH * d.tilesW;
+  BSED_CHECK_ARG(ntiles < (1L << 31), "%s: too many tiles", who);
+  return (int)ntiles;
+}
+
 #if defined(__HIPCC__)
 // ----------------------------------------------------------------------------------------------
 // Philox4x32-10 counter RNG: stateless, keyed on (seed, stream) with a 64-bit element counter, so

@@ -10,8 +10,7 @@ objs=()
 for f in *.hip; do
   o=obj/${f%.hip}.o
   objs+=("$o")
-  if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ bsed_common.h -nt "$o" ] || [ ../../include/bsed.h -nt "$o" ] \
-     || { [ -f igemm_core.h ] && [ igemm_core.h -nt "$o" ]; }; then
+  if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ bsed_common.h -nt "$o" ] || [ ../../include/bsed.h -nt "$o" ]; then
     # mel.hip: the SLP vectorizer packs the FFT's scalar fp32 arithmetic into v_pk_* with op_sel swizzles, whose
     # destination-forwarding hazards cost ~90 s_nop per frame: 0.635 -> 0.599 ms without it (A/B on MI355X).
     # The GCN register-pressure trackers let the scheduler see stft_mel2_kernel's real pressure: without them the

@@ -900,9 +900,8 @@ static int fill_params(Glu3Params& P, int NB, int H, int W, int C, int TH, int T
   BSED_CHECK_ARG(NB > 0 && H > 0 && W > 0 && TH * TW == G3_M && W % TW == 0, "%s: bad shape", who);
   BSED_CHECK_ARG((ph == 1 || ph == 2) && (pw == 1 || pw == 2), "%s: pooling windows must be 1 or 2", who);
   P.NB = NB; P.H = H; P.W = W; P.TH = TH; P.TW = TW;
-  P.lgTW = 0;
-  while ((1 << P.lgTW) < TW) ++P.lgTW;
-  BSED_CHECK_ARG((1 << P.lgTW) == TW, "%s: TW must be a power of two", who);
+  P.lgTW = ilog2_exact(TW);
+  BSED_CHECK_ARG(P.lgTW >= 0, "%s: TW must be a power of two", who);
   P.tilesH = ceil_div(H, TH); P.tilesW = W / TW;
   const long ntiles = (long)NB * P.tilesH * P.tilesW;
   BSED_CHECK_ARG(ntiles < (1L << 31) && (long)NB * H * W * C < (1L << 32),

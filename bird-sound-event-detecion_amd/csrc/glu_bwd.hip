@@ -311,9 +311,8 @@ extern "C" int bsed_glu_bwd_fused(const float* y, const float* scale, const floa
   P.y = y; P.scale = scale; P.shift = shift; P.wfwd = wfwd; P.wbwd = wbwd; P.bias = bias; P.dpool = dpool;
   P.g = g; P.part_dw = part_dw; P.part_db = part_db; P.part_st = part_st;
   P.NB = NB; P.H = H; P.W = W; P.TH = TH; P.TW = TW;
-  P.lgTW = 0;
-  while ((1 << P.lgTW) < TW) ++P.lgTW;
-  BSED_CHECK_ARG((1 << P.lgTW) == TW, "bsed_glu_bwd_fused: TW must be a power of two");
+  P.lgTW = ilog2_exact(TW);
+  BSED_CHECK_ARG(P.lgTW >= 0, "bsed_glu_bwd_fused: TW must be a power of two");
   P.tilesH = ceil_div(H, TH); P.tilesW = W / TW;
   const long ntiles = (long)NB * P.tilesH * P.tilesW;
   BSED_CHECK_ARG(ntiles < (1L << 31) && G <= ntiles, "bsed_glu_bwd_fused: G must not exceed the %ld tiles", ntiles);

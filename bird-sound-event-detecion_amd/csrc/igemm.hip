@@ -1504,12 +1504,6 @@ __global__ void pack_weight_kernel(const float* __restrict__ src, float* __restr
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-static int ilog2_exact(int v) {
-  int l = 0;
-  while ((1 << l) < v) ++l;
-  return (1 << l) == v ? l : -1;
-}
-
 template <int KC, int BN>
 static int launch_igemm_epi(const IgemmParams& P, dim3 grid, size_t smem, hipStream_t s) {
   switch (P.d.epilogue) {
@@ -1545,28 +1539,12 @@ extern "C" int bsed_igemm(const BsedIgemmDesc* desc, void* stream) {
   P.d = *desc;
   BsedIgemmDesc& d = P.d;
   BSED_CHECK_ARG(d.in && d.w && d.out, "bsed_igemm: null tensor");
-  BSED_CHECK_ARG(d.NB > 0 && d.H > 0 && d.W > 0 && d.CIN > 0 && d.N > 0, "bsed_igemm: bad shape");
-  BSED_CHECK_ARG(d.TH * d.TW == IG_TILE_M, "bsed_igemm: TH*TW must be 128 (got %dx%d)", d.TH, d.TW);
-  P.lgTW = ilog2_exact(d.TW);
-  BSED_CHECK_ARG(P.lgTW >= 0, "bsed_igemm: TW must be a power of two");
-  BSED_CHECK_ARG(d.W % d.TW == 0, "bsed_igemm: W %% TW != 0");
-  BSED_CHECK_ARG(d.ntaps >= 1 && d.ntaps <= 9, "bsed_igemm: ntaps must be in 1..9");
-  for (int t = 0; t < d.ntaps; ++t)
-    BSED_CHECK_ARG(abs(d.dh[t]) <= d.hh && abs(d.dw[t]) <= d.hw, "bsed_igemm: tap %d outside the halo", t);
+  const int ntiles = bsed_tile_geometry(P, "bsed_igemm", 16, 4);
+  if (ntiles < 0) return ntiles;
+  BSED_CHECK_ARG(d.out_pitch >= d.N, "bsed_igemm: bad pitch");
   const int KC = (d.CIN % 32 == 0) ? 32 : 16;
-  BSED_CHECK_ARG(d.CIN % KC == 0, "bsed_igemm: CIN must be a multiple of 16");
-  BSED_CHECK_ARG(d.in_pitch >= d.CIN && d.in_pitch % 4 == 0 && d.out_pitch >= d.N, "bsed_igemm: bad pitch");
-  BSED_CHECK_ARG(d.NP % 32 == 0 && d.NP >= d.N, "bsed_igemm: NP must be N rounded up to 32");
   const int BN = d.NP % 128 == 0 ? 128 : (d.NP % 64 == 0 ? 64 : 32);
-  d.tilesH = ceil_div(d.H, d.TH);
-  d.tilesW = d.W / d.TW;
-  P.PW = d.TW + 2 * d.hw;
-  P.PH = d.TH + 2 * d.hh;
-  P.PP = P.PW * P.PH;
   P.b_off = (P.PP * (KC + 1) + 3) & ~3;
-  P.pw_magic = ((1 << 20) + P.PW - 1) / P.PW;
-  for (int pos = 0; pos < P.PP; ++pos)
-    BSED_CHECK_ARG(((pos * P.pw_magic) >> 20) == pos / P.PW, "bsed_igemm: internal: magic division fails for PW=%d", P.PW);
   size_t fl = (size_t)P.b_off + (size_t)KC * BN;
   if (d.epilogue == EPI_GLU_POOL) {
     BSED_CHECK_ARG((d.ph == 1 || d.ph == 2) && (d.pw == 1 || d.pw == 2) && d.TH % d.ph == 0 && d.TW % d.pw == 0,
@@ -1586,8 +1564,6 @@ extern "C" int bsed_igemm(const BsedIgemmDesc* desc, void* stream) {
   fl = std::max(fl, (size_t)8 * BN);
   const size_t smem = fl * sizeof(float);
   BSED_CHECK_ARG(smem <= 160 * 1024, "bsed_igemm: tile needs %zu B of LDS", smem);
-  const long ntiles = (long)d.NB * d.tilesH * d.tilesW;
-  BSED_CHECK_ARG(ntiles < (1L << 31), "bsed_igemm: too many tiles");
   dim3 grid((unsigned)ntiles, d.NP / BN);
   hipStream_t s = (hipStream_t)stream;
   if (KC == 32) {
@@ -1614,27 +1590,17 @@ static int wgrad_prepare(const BsedWgradDesc* desc, WgradParams& P, size_t& smem
   BSED_CHECK_ARG(desc, "bsed_wgrad: null descriptor");
   P.d = *desc;
   BsedWgradDesc& d = P.d;
-  BSED_CHECK_ARG(d.NB > 0 && d.H > 0 && d.W > 0 && d.CIN > 0 && d.N > 0, "bsed_wgrad: bad shape");
-  BSED_CHECK_ARG(d.TH * d.TW == IG_TILE_M, "bsed_wgrad: TH*TW must be 128");
-  P.lgTW = ilog2_exact(d.TW);
-  BSED_CHECK_ARG(P.lgTW >= 0 && d.W % d.TW == 0, "bsed_wgrad: TW must be a power of two dividing W");
-  BSED_CHECK_ARG(d.ntaps >= 1 && d.ntaps <= 9, "bsed_wgrad: ntaps must be in 1..9");
-  for (int t = 0; t < d.ntaps; ++t)
-    BSED_CHECK_ARG(abs(d.dh[t]) <= d.hh && abs(d.dw[t]) <= d.hw, "bsed_wgrad: tap %d outside the halo", t);
-  BSED_CHECK_ARG(d.CIN % 4 == 0 && d.N % 4 == 0, "bsed_wgrad: CIN and N must be multiples of 4");
-  BSED_CHECK_ARG(d.CINP % 32 == 0 && d.CINP >= d.CIN && d.NP % 32 == 0 && d.NP >= d.N, "bsed_wgrad: bad padding");
-  BSED_CHECK_ARG(d.in_pitch >= d.CIN && d.in_pitch % 4 == 0 && d.dy_pitch >= d.N && d.dy_pitch % 4 == 0, "bsed_wgrad: bad pitch");
+  P.ntiles = bsed_tile_geometry(P, "bsed_wgrad", 4, 4);
+  if (P.ntiles < 0) return P.ntiles;
+  BSED_CHECK_ARG(d.N % 4 == 0, "bsed_wgrad: N must be a multiple of 4");
+  BSED_CHECK_ARG(d.CINP % 32 == 0 && d.CINP >= d.CIN, "bsed_wgrad: bad padding");
+  BSED_CHECK_ARG(d.dy_pitch >= d.N && d.dy_pitch % 4 == 0, "bsed_wgrad: bad pitch");
   BSED_CHECK_ARG((d.bn_y == nullptr) == (d.bn_coef == nullptr) && (d.bn_y == nullptr) == (d.bn_mean == nullptr),
                  "bsed_wgrad: bn_y, bn_coef and bn_mean come together (BatchNorm backward applied on load) or not at all");
   BSED_CHECK_ARG(d.bn_y || !d.dy_out, "bsed_wgrad: dy_out only goes with bn_y");
   BSED_CHECK_ARG(!d.bn_y || mode3, "bsed_wgrad: BatchNorm backward on load is built into the split-fp32 kernels (bsed_wgrad3) only");
   BSED_CHECK_ARG(!d.dy_out || (d.dy_out != d.dy && d.dy_out != d.bn_y), "bsed_wgrad: dy_out must not alias dy or bn_y "
                  "(other workgroups still read them)");
-  d.tilesH = ceil_div(d.H, d.TH);
-  d.tilesW = d.W / d.TW;
-  P.PW = d.TW + 2 * d.hw;
-  P.PH = d.TH + 2 * d.hh;
-  P.PP = P.PW * P.PH;
   // input channels are contracted in chunks of CC per workgroup (grid.z): 64 for the 9-tap convolutions so that
   // two workgroups fit in a CU's LDS and one's tile load overlaps the other's MFMAs, 128 for the 1-tap forms
   const bool wide1 = d.ntaps == 1;
@@ -1648,27 +1614,23 @@ static int wgrad_prepare(const BsedWgradDesc* desc, WgradParams& P, size_t& smem
   P.nct = P.CC / 32;
   P.pack2 = (d.CIN <= 16 && d.CINP == 32 && d.ntaps > 1) ? 1 : 0;
   P.dy_off = mode3 ? P.PP * P.CC : ((P.PP * (P.CC + 1) + 3) & ~3);  // in 4-byte words
-  P.pw_magic = ((1 << 20) + P.PW - 1) / P.PW;
-  for (int pos = 0; pos < P.PP; ++pos)
-    BSED_CHECK_ARG(((pos * P.pw_magic) >> 20) == pos / P.PW, "bsed_wgrad: internal: magic division fails for PW=%d", P.PW);
   // 1-tap contractions have one MFMA per LDS pair: widen the dy tile to 128 channels so the activation tile is
   // staged once per 4 output tiles (4x fewer HBM/L2 re-reads of `in`) when it fits in LDS
   // (the 9-tap forms get 2 dy tiles when two workgroups still fit in one CU's LDS: the activation patch is then
   // staged once per 64 output channels and the per-CU load rate stops being the limiter)
   P.ntw = 1;
+  const int tap_items = P.pack2 ? (d.ntaps + 1) / 2 : d.ntaps;
   for (int cand = 4; cand >= 2; cand >>= 1) {
     const size_t need = mode3 ? (size_t)P.dy_off * 4 + (size_t)W3_DY_BYTES * cand
                               : ((size_t)P.dy_off + IG_TILE_M * 32 * cand) * sizeof(float);
     const size_t budget = wide1 ? 160 * 1024 : 80 * 1024;
-    const int tap_items = P.pack2 ? (d.ntaps + 1) / 2 : d.ntaps;
     if (d.NP % (32 * cand) == 0 && tap_items * P.nct * cand <= 36 && need <= budget) { P.ntw = cand; break; }
   }
   smem = mode3 ? (size_t)P.dy_off * 4 + (size_t)W3_DY_BYTES * P.ntw
                : ((size_t)P.dy_off + IG_TILE_M * 32 * P.ntw) * sizeof(float);
+  BSED_CHECK_ARG(tap_items * P.nct * P.ntw <= 36, "bsed_wgrad: %d work items per workgroup exceed the 36 supported",
+                 tap_items * P.nct * P.ntw);
   BSED_CHECK_ARG(smem <= 160 * 1024, "bsed_wgrad: tile needs %zu B of LDS", smem);
-  const long ntiles = (long)d.NB * d.tilesH * d.tilesW;
-  BSED_CHECK_ARG(ntiles < (1L << 31), "bsed_wgrad: too many tiles");
-  P.ntiles = (int)ntiles;
   grid_yz = dim3(1, d.NP / (32 * P.ntw), d.CINP / P.CC);
   return BSED_OK;
 }
@@ -1685,11 +1647,12 @@ extern "C" int bsed_wgrad_auto_g(const BsedWgradDesc* desc) {
   return (int)std::max<long>(1, std::min<long>(want, P.ntiles));
 }
 
-// which template instance bsed_wgrad will launch for this shape: MAXS * 16 + NW (profiling / bench labels)
+// The ONE choice of wgrad_kernel<MAXS, NW> for a shape, as MAXS * 16 + NW: bsed_wgrad launches it, bsed_wgrad_variant
+// reports it (profiling / bench labels)
 static int wgrad_variant(const WgradParams& P) {
   const BsedWgradDesc& d = P.d;
   const int nitems = (P.pack2 ? (d.ntaps + 1) / 2 : d.ntaps) * P.nct * P.ntw;
-  if (nitems >= 16 && d.ntaps == 1) {
+  if (nitems >= 16 && d.ntaps == 1) {  // 1-tap forms: 8 waves per staged tile (measured +55 %); 9-tap forms are faster with 4
     const int slots8 = ceil_div(nitems, 8);
     if (slots8 <= 2) return 2 * 16 + 8;
     if (slots8 <= 3) return 3 * 16 + 8;
@@ -1717,22 +1680,16 @@ extern "C" int bsed_wgrad(const BsedWgradDesc* desc, void* stream) {
   BsedWgradDesc& d = P.d;
   BSED_CHECK_ARG(d.in && d.dy && d.part, "bsed_wgrad: null tensor");
   BSED_CHECK_ARG(d.G > 0 && d.G <= P.ntiles, "bsed_wgrad: G (%d) must be in 1..%d tiles", d.G, P.ntiles);
-  const int nitems = (P.pack2 ? (d.ntaps + 1) / 2 : d.ntaps) * P.nct * P.ntw;
   dim3 grid((unsigned)d.G, gyz.y, gyz.z);
   hipStream_t s = (hipStream_t)stream;
-  if (nitems >= 16 && d.ntaps == 1) {  // 1-tap forms: 8 waves per staged tile (measured +55 %); 9-tap forms are faster with 4
-    const int slots8 = ceil_div(nitems, 8);
-    if (slots8 <= 2) return launch_wgrad<2, 8>(P, grid, smem, s);
-    if (slots8 <= 3) return launch_wgrad<3, 8>(P, grid, smem, s);
-    if (slots8 <= 5) return launch_wgrad<5, 8>(P, grid, smem, s);
+  switch (wgrad_variant(P)) {
+#define CASE(MAXS, NW) \
+  case MAXS * 16 + NW: return launch_wgrad<MAXS, NW>(P, grid, smem, s);
+    CASE(2, 8) CASE(3, 8) CASE(5, 8)
+    CASE(1, 4) CASE(2, 4) CASE(3, 4) CASE(5, 4) CASE(9, 4)
+#undef CASE
   }
-  const int slots = ceil_div(nitems, 4);
-  if (slots <= 1) return launch_wgrad<1, 4>(P, grid, smem, s);
-  if (slots <= 2) return launch_wgrad<2, 4>(P, grid, smem, s);
-  if (slots <= 3) return launch_wgrad<3, 4>(P, grid, smem, s);
-  if (slots <= 5) return launch_wgrad<5, 4>(P, grid, smem, s);
-  if (slots <= 9) return launch_wgrad<9, 4>(P, grid, smem, s);
-  bsed_set_error("bsed_wgrad: %d work items per workgroup exceed the 36 supported", nitems);
+  bsed_set_error("bsed_wgrad: no kernel instance for variant %d", wgrad_variant(P));
   return BSED_ERR_ARG;
 }
 

@@ -655,31 +655,14 @@ extern "C" int bsed_igemm3(const BsedIgemmDesc* desc, void* stream) {
   BSED_CHECK_ARG(d.in && d.w && d.out, "bsed_igemm3: null tensor");
   BSED_CHECK_ARG(d.epilogue == BSED_EPI_PLAIN || d.epilogue == BSED_EPI_STATS, "bsed_igemm3: PLAIN / STATS epilogues only");
   BSED_CHECK_ARG(d.epilogue != BSED_EPI_STATS || d.stats, "bsed_igemm3: STATS needs a stats buffer");
-  BSED_CHECK_ARG(d.NB > 0 && d.H > 0 && d.W > 0 && d.CIN > 0 && d.CIN % 32 == 0 && d.N > 0, "bsed_igemm3: CIN must be a multiple of 32");
-  BSED_CHECK_ARG(d.TH * d.TW == I3_M && d.W % d.TW == 0, "bsed_igemm3: TH*TW must be 128 and TW divide W");
-  P.lgTW = 0;
-  while ((1 << P.lgTW) < d.TW) ++P.lgTW;
-  BSED_CHECK_ARG((1 << P.lgTW) == d.TW, "bsed_igemm3: TW must be a power of two");
-  BSED_CHECK_ARG(d.ntaps >= 1 && d.ntaps <= 9, "bsed_igemm3: ntaps must be in 1..9");
-  for (int t = 0; t < d.ntaps; ++t)
-    BSED_CHECK_ARG(abs(d.dh[t]) <= d.hh && abs(d.dw[t]) <= d.hw, "bsed_igemm3: tap %d outside the halo", t);
-  BSED_CHECK_ARG(d.in_pitch >= d.CIN && d.in_pitch % 4 == 0 && d.out_pitch >= d.N, "bsed_igemm3: bad pitch");
-  BSED_CHECK_ARG(d.NP % 32 == 0 && d.NP >= d.N, "bsed_igemm3: NP must be N rounded up to 32");
+  const int ntiles = bsed_tile_geometry(P, "bsed_igemm3", 32, 4);
+  if (ntiles < 0) return ntiles;
+  BSED_CHECK_ARG(d.out_pitch >= d.N, "bsed_igemm3: bad pitch");
   const int BN = d.NP % 128 == 0 ? 128 : (d.NP % 64 == 0 ? 64 : 32);
-  d.tilesH = ceil_div(d.H, d.TH);
-  d.tilesW = d.W / d.TW;
-  P.PW = d.TW + 2 * d.hw;
-  P.PH = d.TH + 2 * d.hh;
-  P.PP = P.PW * P.PH;
   P.b_off = (P.PP * I3_ROW + 7) & ~7;
-  P.pw_magic = ((1 << 20) + P.PW - 1) / P.PW;
-  for (int pos = 0; pos < P.PP; ++pos)
-    BSED_CHECK_ARG(((pos * P.pw_magic) >> 20) == pos / P.PW, "bsed_igemm3: internal: magic division fails for PW=%d", P.PW);
   size_t bytes = ((size_t)P.b_off + (size_t)BN * I3_ROW) * sizeof(unsigned short);
   bytes = std::max(bytes, (size_t)8 * BN * sizeof(float));
   BSED_CHECK_ARG(bytes <= 160 * 1024, "bsed_igemm3: tile needs %zu B of LDS", bytes);
-  const long ntiles = (long)d.NB * d.tilesH * d.tilesW;
-  BSED_CHECK_ARG(ntiles < (1L << 31), "bsed_igemm3: too many tiles");
   dim3 grid((unsigned)ntiles, d.NP / BN);
   hipStream_t s = (hipStream_t)stream;
   const bool st = d.epilogue == BSED_EPI_STATS;
@@ -714,31 +697,16 @@ extern "C" int bsed_igemm3s(const BsedIgemmDesc* desc, int G, void* stream) {
   BSED_CHECK_ARG(d.in && d.w && d.out, "bsed_igemm3s: null tensor");
   BSED_CHECK_ARG(d.epilogue == BSED_EPI_PLAIN || d.epilogue == BSED_EPI_STATS, "bsed_igemm3s: PLAIN / STATS epilogues only");
   BSED_CHECK_ARG(d.epilogue != BSED_EPI_STATS || d.stats, "bsed_igemm3s: STATS needs a stats buffer");
-  BSED_CHECK_ARG(d.NB > 0 && d.H > 0 && d.W > 0 && (d.CIN == 16 || d.CIN == 32) && d.N > 0,
-                 "bsed_igemm3s: built for CIN = 16 or 32");
-  const int KS = d.CIN / 16;
-  BSED_CHECK_ARG(d.TH * d.TW == I3_M && d.W % d.TW == 0, "bsed_igemm3s: TH*TW must be 128 and TW divide W");
-  P.lgTW = 0;
-  while ((1 << P.lgTW) < d.TW) ++P.lgTW;
-  BSED_CHECK_ARG((1 << P.lgTW) == d.TW, "bsed_igemm3s: TW must be a power of two");
+  BSED_CHECK_ARG(d.CIN == 16 || d.CIN == 32, "bsed_igemm3s: built for CIN = 16 or 32");
   BSED_CHECK_ARG(d.ntaps == 9 || d.ntaps == 1, "bsed_igemm3s: 9 or 1 taps");
-  for (int t = 0; t < d.ntaps; ++t)
-    BSED_CHECK_ARG(abs(d.dh[t]) <= d.hh && abs(d.dw[t]) <= d.hw, "bsed_igemm3s: tap %d outside the halo", t);
-  BSED_CHECK_ARG(d.in_pitch >= d.CIN && d.in_pitch % (d.act_bf16 ? 8 : 4) == 0 && d.out_pitch >= d.N, "bsed_igemm3s: bad pitch");
-  BSED_CHECK_ARG(d.NP % 32 == 0 && d.NP >= d.N, "bsed_igemm3s: NP must be N rounded up to 32");
-  d.tilesH = ceil_div(d.H, d.TH);
-  d.tilesW = d.W / d.TW;
-  P.PW = d.TW + 2 * d.hw;
-  P.PH = d.TH + 2 * d.hh;
-  P.PP = P.PW * P.PH;
+  const int ntiles = bsed_tile_geometry(P, "bsed_igemm3s", 16, d.act_bf16 ? 8 : 4);
+  if (ntiles < 0) return ntiles;
+  BSED_CHECK_ARG(d.out_pitch >= d.N, "bsed_igemm3s: bad pitch");
+  const int KS = d.CIN / 16;
   BSED_CHECK_ARG(P.PP <= (KS == 1 ? 256 : 192), "bsed_igemm3s: patch of %d positions exceeds the %d supported", P.PP,
                  KS == 1 ? 256 : 192);
   P.b_off = 0;
-  P.pw_magic = ((1 << 20) + P.PW - 1) / P.PW;
-  for (int pos = 0; pos < P.PP; ++pos)
-    BSED_CHECK_ARG(((pos * P.pw_magic) >> 20) == pos / P.PW, "bsed_igemm3s: internal: magic division fails for PW=%d", P.PW);
-  const long ntiles = (long)d.NB * d.tilesH * d.tilesW;
-  BSED_CHECK_ARG(ntiles < (1L << 31) && G > 0 && G <= ntiles, "bsed_igemm3s: G must be in 1..%ld tiles", ntiles);
+  BSED_CHECK_ARG(G > 0 && G <= ntiles, "bsed_igemm3s: G must be in 1..%d tiles", ntiles);
   // N <= 16: transposed epilogue (wave-private LDS image, float4 row stores)
   const bool nv16 = d.N <= 16 && d.N % 4 == 0 && d.out_pitch % 4 == 0;
   const size_t bytes = (size_t)d.ntaps * KS * 2 * (nv16 ? 32 : 64) * 16 + (size_t)P.PP * ((d.act_bf16 ? 1 : 2) * d.CIN + 8) * 2 +

@@ -480,32 +480,15 @@ extern "C" int bsed_igemm3n(const BsedIgemmDesc* desc, void* stream) {
   BSED_CHECK_ARG(d.in && d.w && d.out, "bsed_igemm3n: null tensor");
   BSED_CHECK_ARG(d.epilogue == BSED_EPI_PLAIN || d.epilogue == BSED_EPI_STATS, "bsed_igemm3n: PLAIN / STATS epilogues only");
   BSED_CHECK_ARG(d.epilogue != BSED_EPI_STATS || d.stats, "bsed_igemm3n: STATS needs a stats buffer");
-  BSED_CHECK_ARG(d.NB > 0 && d.H > 0 && d.W > 0 && d.CIN > 0 && d.CIN % 32 == 0 && d.N > 0, "bsed_igemm3n: CIN must be a multiple of 32");
-  BSED_CHECK_ARG(d.TH * d.TW == I3N_M && d.W % d.TW == 0, "bsed_igemm3n: TH*TW must be 128 and TW divide W");
-  P.lgTW = 0;
-  while ((1 << P.lgTW) < d.TW) ++P.lgTW;
-  BSED_CHECK_ARG((1 << P.lgTW) == d.TW, "bsed_igemm3n: TW must be a power of two");
-  BSED_CHECK_ARG(d.ntaps >= 1 && d.ntaps <= 9, "bsed_igemm3n: ntaps must be in 1..9");
-  for (int t = 0; t < d.ntaps; ++t)
-    BSED_CHECK_ARG(abs(d.dh[t]) <= d.hh && abs(d.dw[t]) <= d.hw, "bsed_igemm3n: tap %d outside the halo", t);
-  BSED_CHECK_ARG(d.in_pitch >= d.CIN && d.in_pitch % (d.act_bf16 ? 8 : 4) == 0 && d.out_pitch >= d.N, "bsed_igemm3n: bad pitch");
-  BSED_CHECK_ARG(d.NP % 32 == 0 && d.NP >= d.N, "bsed_igemm3n: NP must be N rounded up to 32");
+  const int ntiles = bsed_tile_geometry(P, "bsed_igemm3n", 32, d.act_bf16 ? 8 : 4);
+  if (ntiles < 0) return ntiles;
+  BSED_CHECK_ARG(d.out_pitch >= d.N, "bsed_igemm3n: bad pitch");
   const int BN = d.NP % 128 == 0 ? 128 : (d.NP % 64 == 0 ? 64 : 32);
-  d.tilesH = ceil_div(d.H, d.TH);
-  d.tilesW = d.W / d.TW;
-  P.PW = d.TW + 2 * d.hw;
-  P.PH = d.TH + 2 * d.hh;
-  P.PP = P.PW * P.PH;
   P.b_off = (P.PP * (d.act_bf16 ? 40 : I3N_ROW) + 7) & ~7;
   P.prio = (i3n_knob() & 8) ? 0 : 1;
-  P.pw_magic = ((1 << 20) + P.PW - 1) / P.PW;
-  for (int pos = 0; pos < P.PP; ++pos)
-    BSED_CHECK_ARG(((pos * P.pw_magic) >> 20) == pos / P.PW, "bsed_igemm3n: internal: magic division fails for PW=%d", P.PW);
   // two patch buffers when the layer has more than one chunk
   const size_t bytes = (size_t)P.b_off * sizeof(unsigned short) * (d.CIN > I3N_KC ? 2 : 1);
   BSED_CHECK_ARG(bytes <= 160 * 1024, "bsed_igemm3n: tile needs %zu B of LDS", bytes);
-  const long ntiles = (long)d.NB * d.tilesH * d.tilesW;
-  BSED_CHECK_ARG(ntiles < (1L << 31), "bsed_igemm3n: too many tiles");
   BSED_CHECK_ARG((size_t)d.H * d.W * d.in_pitch < (1ull << 31), "bsed_igemm3n: an image of 2^31 elements or more");
   dim3 grid((unsigned)ntiles, d.NP / BN);
   hipStream_t s = (hipStream_t)stream;

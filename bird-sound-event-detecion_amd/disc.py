@@ -182,12 +182,8 @@ class Clip_Discriminator(_FlatModule):
                 assert (Hp - 1, Wp - 1) == (Ho, Wo)
                 wfull = self._s2d_weight(k)
                 K = 4 * cin
-                if self.conv_mode == "bf16x3":
-                    w3 = ops.pack_weight3(wfull, 4, K, co, K * co, co, 1)
-                    y, stats = ops.igemm3(xp, w3, co, N, Hp, Wp, K, TAPS2x2, bias=bias, epilogue=epi, valid=(Ho, Wo))
-                else:
-                    wpk = ops.pack_weight(wfull, 4, K, co, K * co, co, 1)
-                    y, stats = ops.igemm(xp, wpk, co, N, Hp, Wp, K, taps=TAPS2x2, bias=bias, epilogue=epi, valid=(Ho, Wo))
+                y, stats = ops.contract(xp, wfull, co, N, Hp, Wp, K, TAPS2x2, K * co, co, 1, mode=self.conv_mode,
+                                        bias=bias, epilogue=epi, valid=(Ho, Wo))
                 rec = dict(direct=True, xp=xp, wfull=wfull, Hp=Hp, Wp=Wp)
                 nHa, nWa = Hp, Wp
             else:
@@ -341,9 +337,7 @@ class Frame_Discriminator(_FlatModule):
 
     def _linear(self, x, name, M, K, N):
         w, b = self.P(name + ".weight"), self.P(name + ".bias")
-        if self.conv_mode == "bf16x3":
-            return ops.igemm3(x, ops.pack_weight3(w, 1, K, N, 0, 1, K), N, 1, M, 1, K, ((0, 0),), bias=b)[0]
-        return ops.igemm(x, ops.pack_weight(w, 1, K, N, 0, 1, K), N, 1, M, 1, K, bias=b)[0]
+        return ops.contract(x, w, N, 1, M, 1, K, ops.TAP1, 0, 1, K, mode=self.conv_mode, bias=b)[0]
 
     def _linear_bwd(self, x, dy, name, M, K, N):
         """accumulates dW, db of y = x W^T + b; returns dL/dx (M,K)"""
@@ -351,9 +345,7 @@ class Frame_Discriminator(_FlatModule):
         ops.colsum(dy, M, N, N, b.grad)
         part, G, KP, NP = ops.wgrad(x, dy, 1, M, 1, K, N, mode="bf16x3")
         ops.reduce_partials(part, G, 1, KP, NP, K, N, w.grad, 0, 1, K)
-        if self.conv_mode == "bf16x3":
-            return ops.igemm3(dy, ops.pack_weight3(w, 1, N, K, 0, K, 1), K, 1, M, 1, N, ((0, 0),))[0]
-        return ops.igemm(dy, ops.pack_weight(w, 1, N, K, 0, K, 1), K, 1, M, 1, N)[0]
+        return ops.contract(dy, w, K, 1, M, 1, N, ops.TAP1, 0, K, 1, mode=self.conv_mode)[0]
 
     def _act(self, a, stream_id, drop):
         out = torch.empty_like(a)

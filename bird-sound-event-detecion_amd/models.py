@@ -342,15 +342,8 @@ class CRNN(_FlatModule):
             y, stats = ops.conv0_fwd(a, cw, cb, B, Hh, Ww, co, want_stats=train)
         else:
             epi = ops.EPI_STATS if train else ops.EPI_PLAIN
-            if self._mfma3 and cin % 32 == 0:
-                w3 = ops.pack_weight3(wsrc, len(taps), cin, co, s_tap, 9, cin * 9)
-                y, stats = ops.igemm3(a, w3, co, B, Hh, Ww, cin, taps, bias=cb, epilogue=epi)
-            elif self._mfma3 and cin == 16 and ops.igemm3s_supported(Ww, cin):
-                w3s = ops.pack_weight3s(cw, 9, co, 1, 9, cin * 9)
-                y, stats = ops.igemm3s(a, w3s, co, B, Hh, Ww, ops.TAPS3x3, bias=cb, epilogue=epi)
-            else:
-                wpk = ops.pack_weight(wsrc, len(taps), cin, co, s_tap, 9, cin * 9)
-                y, stats = ops.igemm(a, wpk, co, B, Hh, Ww, cin, taps=taps, bias=cb, epilogue=epi)
+            y, stats = ops.contract(a, wsrc, co, B, Hh, Ww, cin, taps, s_tap, 9, cin * 9, mode=self.conv_mode, bias=cb,
+                                    epilogue=epi, resident=cin == 16 and ops.igemm3s_supported(Ww, cin))
         bn = self.P(names[1])
         if train:
             mean, invstd, scale, shift = ops.bn_finalize(stats, co, float(B * Hh * Ww), BN_EPS, BN_MOMENTUM,
@@ -407,12 +400,7 @@ class CRNN(_FlatModule):
         layers = []
         for l in range(2):
             nin, w_ih, w_hh, b_ih, b_hh = self._rnn_views(l, prefix)
-            if self._mfma3:
-                w3 = ops.pack_weight3(w_ih, 1, nin, 768, 0, 1, nin)
-                xp, _ = ops.igemm3(seq, w3, 768, 1, B * T, 1, nin, ((0, 0),), bias=b_ih)
-            else:
-                wpk = ops.pack_weight(w_ih, 1, nin, 768, 0, 1, nin)
-                xp, _ = ops.igemm(seq, wpk, 768, 1, B * T, 1, nin, bias=b_ih)
+            xp, _ = ops.contract(seq, w_ih, 768, 1, B * T, 1, nin, ops.TAP1, 0, 1, nin, mode=self.conv_mode, bias=b_ih)
             if l == 0 and self.rnn_hook is not None:
                 # one-shot: independent work for the chip's idle half while the recurrences run (SEDTrainer enqueues
                 # the next batch's mel transform on its feature stream here)
@@ -470,12 +458,7 @@ class CRNN(_FlatModule):
                         t.record_stream(side)               # the allocator must not recycle them under the side stream
             else:
                 self._gru_param_grads(lay, l, prefix, dxp, dgh, pih, phh, B, T)
-            if self._mfma3:
-                w3 = ops.pack_weight3(w_ih, 1, 768, nin, 0, nin, 1)
-                d, _ = ops.igemm3(dxp, w3, nin, 1, B * T, 1, 768, ((0, 0),))
-            else:
-                wpk = ops.pack_weight(w_ih, 1, 768, nin, 0, nin, 1)
-                d, _ = ops.igemm(dxp, wpk, nin, 1, B * T, 1, 768)
+            d, _ = ops.contract(dxp, w_ih, nin, 1, B * T, 1, 768, ops.TAP1, 0, nin, 1, mode=self.conv_mode)
             d = d.view(B, T, nin)
         return d
 
@@ -574,16 +557,9 @@ class CRNN(_FlatModule):
         if not need_dgrad:
             return None
         flipped = [(-a, -b) for a, b in taps]
-        if self._mfma3 and co == 32 and cin <= 32 and ops.igemm3s_supported(Ww, co):
-            # data gradient of a 32-channel layer: all taps' weights resident in LDS (csrc/igemm3.hip, igemm3s)
-            wds = ops.pack_weight3s(cw, 9, cin, 1, cin * 9, 9, K=co)
-            d_in, _ = ops.igemm3s(dy, wds, cin, B, Hh, Ww, flipped)
-        elif self._mfma3:
-            wd3 = ops.pack_weight3(wsrc, len(taps), co, cin, s_tap, cin * 9, 9)
-            d_in, _ = ops.igemm3(dy, wd3, cin, B, Hh, Ww, co, flipped)
-        else:
-            wd = ops.pack_weight(wsrc, len(taps), co, cin, s_tap, cin * 9, 9)
-            d_in, _ = ops.igemm(dy, wd, cin, B, Hh, Ww, co, taps=flipped)
+        # data gradient of a 32-channel layer: all taps' weights resident in LDS (csrc/igemm3.hip, igemm3s)
+        d_in, _ = ops.contract(dy, wsrc, cin, B, Hh, Ww, co, flipped, s_tap, cin * 9, 9, mode=self.conv_mode,
+                               resident=co == 32 and cin <= 32 and ops.igemm3s_supported(Ww, co))
         return d_in
 
     def _cnn_forward(self, x, ctx):
@@ -729,15 +705,15 @@ class CRNN_fpn(CRNN):
         sd = super().state_dict(*args, **kwargs)
         return OrderedDict((("cnn." + k if self._BASE_KEY.match(k) else k), v) for k, v in sd.items())
 
+    @property
+    def _fuse_mode(self):
+        """the fuse layers have no bf16-mode path (_check_bf16_mode): there they stay on the fp32-core kernel"""
+        return "fp32" if self.conv_mode == "bf16" else self.conv_mode
+
     # 1x1 convolution over channels of a (B,T,512) sequence == GEMM with the (256,512) weight
     def _fuse(self, cat, name, B, T):
         w, b = self.P(name + ".weight"), self.P(name + ".bias")
-        if self.conv_mode == "bf16x3":
-            w3 = ops.pack_weight3(w, 1, 512, 256, 0, 1, 512)
-            out, _ = ops.igemm3(cat, w3, 256, 1, B * T, 1, 512, ((0, 0),), bias=b)
-        else:
-            wpk = ops.pack_weight(w, 1, 512, 256, 0, 1, 512)
-            out, _ = ops.igemm(cat, wpk, 256, 1, B * T, 1, 512, bias=b)
+        out, _ = ops.contract(cat, w, 256, 1, B * T, 1, 512, ops.TAP1, 0, 1, 512, mode=self._fuse_mode, bias=b)
         return out.view(B, T, 256)
 
     def _fuse_backward(self, cat, d_out, name, B, T):
@@ -746,12 +722,7 @@ class CRNN_fpn(CRNN):
         ops.colsum(d_out, B * T, 256, 256, b.grad)
         part, G, KP, NP = ops.wgrad(cat, d_out, 1, B * T, 1, 512, 256, mode=self.conv_mode)
         ops.reduce_partials(part, G, 1, KP, NP, 512, 256, w.grad, 0, 1, 512)
-        if self.conv_mode == "bf16x3":
-            w3 = ops.pack_weight3(w, 1, 256, 512, 0, 512, 1)
-            d_cat, _ = ops.igemm3(d_out, w3, 512, 1, B * T, 1, 256, ((0, 0),))
-        else:
-            wpk = ops.pack_weight(w, 1, 256, 512, 0, 512, 1)
-            d_cat, _ = ops.igemm(d_out, wpk, 512, 1, B * T, 1, 256)
+        d_cat, _ = ops.contract(d_out, w, 512, 1, B * T, 1, 256, ops.TAP1, 0, 512, 1, mode=self._fuse_mode)
         return d_cat.view(B, T, 512)
 
     def run_forward(self, x, save=True):
@@ -864,12 +835,7 @@ class CRNN_pred(CRNN):
             C = self.nclass
             feats = (a if a.dtype == torch.float32 else a.float()).view(B, T, C)   # bf16 mode: the head stays fp32
             w, b = self.P("dense_softmax.weight"), self.P("dense_softmax.bias")
-            if self._mfma3:
-                w3 = ops.pack_weight3(w, 1, C, C, 0, 1, C)
-                logits, _ = ops.igemm3(feats, w3, C, 1, B * T, 1, C, ((0, 0),), bias=b)
-            else:
-                wpk = ops.pack_weight(w, 1, C, C, 0, 1, C)
-                logits, _ = ops.igemm(feats, wpk, C, 1, B * T, 1, C, bias=b)
+            logits, _ = ops.contract(feats, w, C, 1, B * T, 1, C, ops.TAP1, 0, 1, C, mode=self.conv_mode, bias=b)
         return ops.tag_head_fwd(feats, logits.view(B, T, C))
 
     def run_backward(self, ctx, d):

@@ -17,6 +17,7 @@ IgemmDesc, WgradDesc, HeadBwdDesc, PackJob, ReduceJob, BnEvalJob = (L.STRUCTS["B
     "IgemmDesc", "WgradDesc", "HeadBwdDesc", "PackJob", "ReduceJob", "BnEvalJob"))
 
 TAPS3x3 = [(kh - 1, kw - 1) for kh in range(3) for kw in range(3)]
+TAP1 = ((0, 0),)   # a plain GEMM: (positions, CIN) x (CIN, N)
 
 
 class KernelTimer:
@@ -166,40 +167,56 @@ def pack_weight(src, ntaps, K, N, s_tap, s_k, s_n, src_offset=0):
     return dst
 
 
+def _tile_taps(d, H, W, taps):
+    """Tile, taps and halo of an IgemmDesc / WgradDesc; returns the tile count of one (H, W) image."""
+    TH, TW = d.TH, d.TW = tile_for(W)
+    hh = hw = 0
+    for i, (a, b) in enumerate(taps):
+        d.dh[i], d.dw[i] = a, b
+        hh, hw = max(hh, abs(a)), max(hw, abs(b))
+    d.hh, d.hw, d.ntaps = hh, hw, len(taps)
+    return ((H + TH - 1) // TH) * (W // TW)
+
+
+def _igemm_desc(NB, H, W, CIN, N, NP, taps, epilogue, valid=None):
+    """(IgemmDesc, tile count) of a contraction without pooling, with dense rows (pitch = channel count); the
+    pointers, and whatever else differs, are the caller's."""
+    d = IgemmDesc()
+    ntiles = NB * _tile_taps(d, H, W, taps)
+    d.NB, d.H, d.W, d.CIN, d.N, d.NP = NB, H, W, CIN, N, NP
+    d.in_pitch, d.out_pitch, d.e_pitch = CIN, N, N
+    d.ph = d.pw = 1
+    d.Hp, d.Wp = H, W
+    d.epilogue = epilogue
+    if valid:
+        d.valid_h, d.valid_w = valid
+    return d, ntiles
+
+
 def igemm(inp, wpk, N, NB, H, W, CIN, taps=((0, 0),), bias=None, out=None, epilogue=EPI_PLAIN, in_pitch=None,
           out_pitch=None, a_scale=None, a_shift=None, e_src=None, e_scale=None, e_shift=None, e_dpool=None,
           out2=None, pool=(1, 1), drop_p=0.0, rng_stream=0, seed=0, in_offset=0, want_stats=False, valid=None):
     """Launch the implicit GEMM.  Returns (out, stats or None).  valid = (h, w): only output positions inside that
     extent are stored / enter the STATS sums (the rest of a freshly allocated ``out`` is zero)."""
-    d = IgemmDesc()
-    TH, TW = tile_for(W)
     NP = wpk.shape[2]
+    d, ntiles = _igemm_desc(NB, H, W, CIN, N, NP, taps, epilogue, valid)
     ph, pw = pool
     Hp, Wp = H // ph, W // pw
     dev = inp.device
     if out is None:
         shape = (NB, Hp, Wp, N) if epilogue == EPI_GLU_POOL else (NB, H, W, N)
         out = (torch.zeros if valid else torch.empty)(shape, device=dev, dtype=torch.float32)
-    if valid:
-        d.valid_h, d.valid_w = valid
-    ntiles = NB * ((H + TH - 1) // TH) * (W // TW)
     stats = None
     if epilogue in (EPI_STATS, EPI_GLU_BWD, EPI_ADD_STATS2):
         stats = torch.empty((ntiles, 2, N), device=dev, dtype=torch.float32)
     d.in_ = _dp(inp, in_offset); d.w = _p(wpk); d.bias = _p(bias); d.out = _p(out); d.out2 = _p(out2)
     d.stats = _p(stats); d.a_scale = _p(a_scale); d.a_shift = _p(a_shift); d.e_src = _p(e_src)
     d.e_scale = _p(e_scale); d.e_shift = _p(e_shift); d.e_dpool = _p(e_dpool)
-    d.in_pitch = CIN if in_pitch is None else in_pitch
-    d.out_pitch = N if out_pitch is None else out_pitch
-    d.e_pitch = N
-    d.NB, d.H, d.W, d.CIN, d.N, d.NP = NB, H, W, CIN, N, NP
-    d.TH, d.TW = TH, TW
-    d.hh = max(abs(t[0]) for t in taps); d.hw = max(abs(t[1]) for t in taps)
-    d.ntaps = len(taps)
-    for i, (a, b) in enumerate(taps):
-        d.dh[i], d.dw[i] = a, b
+    if in_pitch is not None:
+        d.in_pitch = in_pitch
+    if out_pitch is not None:
+        d.out_pitch = out_pitch
     d.ph, d.pw, d.Hp, d.Wp = ph, pw, Hp, Wp
-    d.epilogue = epilogue
     d.drop_p, d.rng_stream, d.seed = drop_p, rng_stream, seed
     kc = 32 if CIN % 32 == 0 else 16
     bn = 128 if NP % 128 == 0 else (64 if NP % 64 == 0 else 32)
@@ -356,26 +373,14 @@ def igemm3s_supported(W, CIN, ntaps=9):
 def igemm3s(inp, wtab, N, NB, H, W, taps, bias=None, epilogue=EPI_PLAIN):
     """CIN = 16 / 32 convolution on the bf16 cores (split-fp32), all taps' weights resident in LDS.
     Returns (out, stats (G,2,N) or None)."""
-    d = IgemmDesc()
-    TH, TW = tile_for(W)
-    NP = wtab.shape[0] * 32
+    CIN = 16 * wtab.shape[2]
+    d, ntiles = _igemm_desc(NB, H, W, CIN, N, wtab.shape[0] * 32, taps, epilogue)
     dev = inp.device
     out = torch.empty((NB, H, W, N), device=dev, dtype=inp.dtype)
-    ntiles = NB * ((H + TH - 1) // TH) * (W // TW)
     G = int(min(ntiles, L.lib().bsed_igemm3s_auto_g2(inp.shape[-1], N)))
     stats = torch.empty((G, 2, N), device=dev, dtype=torch.float32) if epilogue == EPI_STATS else None
     d.act_bf16 = _abf(inp)
     d.in_ = _dp(inp); d.w = wtab.data_ptr(); d.bias = _p(bias); d.out = out.data_ptr(); d.stats = _p(stats)
-    CIN = 16 * wtab.shape[2]
-    d.in_pitch, d.out_pitch, d.e_pitch = CIN, N, N
-    d.NB, d.H, d.W, d.CIN, d.N, d.NP = NB, H, W, CIN, N, NP
-    d.TH, d.TW = TH, TW
-    d.hh = max(abs(t[0]) for t in taps); d.hw = max(abs(t[1]) for t in taps)
-    d.ntaps = len(taps)
-    for i, (a, b) in enumerate(taps):
-        d.dh[i], d.dw[i] = a, b
-    d.ph = d.pw = 1; d.Hp, d.Wp = H, W
-    d.epilogue = epilogue
     nv = 16 if N <= 16 and N % 4 == 0 else 32                      # transposed epilogue (bsed_igemm3s)
     _launch((f"igemm3s_kernel<{1 if epilogue == EPI_STATS else 0}, {len(taps)}, {CIN // 16}, {nv}, {d.act_bf16}>", len(taps), CIN, N, H, W),
             2.0 * NB * H * W * len(taps) * CIN * N, lambda: L.call("bsed_igemm3s", ctypes.byref(d), G, L.stream()),
@@ -390,27 +395,14 @@ def igemm3(inp, w3, N, NB, H, W, CIN, taps, bias=None, epilogue=EPI_PLAIN, valid
         return _igemm3n(inp, w3, N, NB, H, W, CIN, taps, bias, epilogue, valid)
     if inp.dtype != torch.float32:
         raise L.BsedError("bf16 activations need the N-split kernel (BSED_IGEMM3N=1)")
-    d = IgemmDesc()
-    TH, TW = tile_for(W)
     NP = w3.shape[2]
+    d, ntiles = _igemm_desc(NB, H, W, CIN, N, NP, taps, epilogue, valid)
     bn = 128 if NP % 128 == 0 else (64 if NP % 64 == 0 else 32)
     dev = inp.device
     out = (torch.zeros if valid else torch.empty)((NB, H, W, N), device=dev, dtype=torch.float32)
-    if valid:
-        d.valid_h, d.valid_w = valid
-    ntiles = NB * ((H + TH - 1) // TH) * (W // TW)
     stats = torch.empty((ntiles, 2, N), device=dev, dtype=torch.float32) if epilogue == EPI_STATS else None
     d.in_ = _dp(inp); d.w = w3.data_ptr(); d.bias = _p(bias); d.out = _p(out); d.stats = _p(stats)
-    d.in_pitch, d.out_pitch, d.e_pitch = CIN, N, N
-    d.NB, d.H, d.W, d.CIN, d.N, d.NP = NB, H, W, CIN, N, NP
-    d.TH, d.TW = TH, TW
-    d.hh = max(abs(t[0]) for t in taps); d.hw = max(abs(t[1]) for t in taps)
-    d.ntaps = len(taps)
-    for i, (a, b) in enumerate(taps):
-        d.dh[i], d.dw[i] = a, b
-    d.ph = d.pw = 1; d.Hp, d.Wp = H, W
-    d.epilogue = epilogue
-    need = ((TH + 2 * d.hh) * (TW + 2 * d.hw) * 8 + 255) // 256        # float4 patch elements per thread (launch_i3)
+    need = ((d.TH + 2 * d.hh) * (d.TW + 2 * d.hw) * 8 + 255) // 256        # float4 patch elements per thread (launch_i3)
     pv = 12 if need > 9 else (9 if need > 6 else 6)
     _launch((f"igemm3_kernel<{bn}, {1 if epilogue == EPI_STATS else 0}, 1, {pv}>", len(taps), CIN, N, H, W),
             2.0 * NB * H * W * len(taps) * CIN * N, lambda: L.call("bsed_igemm3", ctypes.byref(d), L.stream()))
@@ -430,26 +422,13 @@ def set_igemm3n_wpe(wpe):
 
 def _igemm3n(inp, wtab, N, NB, H, W, CIN, taps, bias, epilogue, valid):
     """bsed_igemm3n: wtab = pack_weight3s table of the layer (K = CIN).  Returns (out, stats (rows,2,N) or None)."""
-    d = IgemmDesc()
-    TH, TW = tile_for(W)
-    NP = wtab.shape[0] * 32
     if wtab.shape[2] * 16 != CIN or wtab.shape[1] != len(taps):
         raise L.BsedError(f"igemm3: weight table packed for K={wtab.shape[2] * 16}, {wtab.shape[1]} taps; "
                           f"called with CIN={CIN}, {len(taps)} taps")
+    d, _ = _igemm_desc(NB, H, W, CIN, N, wtab.shape[0] * 32, taps, epilogue, valid)
     dev = inp.device
     out = (torch.zeros if valid else torch.empty)((NB, H, W, N), device=dev, dtype=inp.dtype)
-    if valid:
-        d.valid_h, d.valid_w = valid
     d.act_bf16 = _abf(inp)
-    d.in_pitch, d.out_pitch, d.e_pitch = CIN, N, N
-    d.NB, d.H, d.W, d.CIN, d.N, d.NP = NB, H, W, CIN, N, NP
-    d.TH, d.TW = TH, TW
-    d.hh = max(abs(t[0]) for t in taps); d.hw = max(abs(t[1]) for t in taps)
-    d.ntaps = len(taps)
-    for i, (a, b) in enumerate(taps):
-        d.dh[i], d.dw[i] = a, b
-    d.ph = d.pw = 1; d.Hp, d.Wp = H, W
-    d.epilogue = epilogue
     d.in_ = _dp(inp); d.w = wtab.data_ptr(); d.bias = _p(bias); d.out = out.data_ptr()
     rows = L.lib().bsed_igemm3n_stats_rows(ctypes.byref(d))
     var = L.lib().bsed_igemm3n_variant(ctypes.byref(d))
@@ -463,6 +442,25 @@ def _igemm3n(inp, wtab, N, NB, H, W, CIN, taps, bias, epilogue, valid):
     return out, stats
 
 
+def contract(inp, wsrc, N, NB, H, W, CIN, taps, s_tap, s_k, s_n, *, mode, bias=None, epilogue=EPI_PLAIN, valid=None,
+             resident=False):
+    """Pack the weights wsrc[tap * s_tap + k * s_k + n * s_n] (k < CIN, n < N) and run the PLAIN / STATS contraction
+    with them.  Returns (out, stats or None).  mode: the caller's conv_mode.  "fp32" = the fp32-core kernel (igemm);
+    "bf16x3" / "bf16" = the bf16 cores: igemm3s where the caller says its table may stay `resident` in LDS
+    (igemm3s_supported and the layer's own condition), igemm3 (slab or N-split, as igemm3_nsplit() says) for CIN a
+    multiple of 32, and the fp32-core kernel for the channel counts neither is built for."""
+    if mode not in ("fp32", "bf16x3", "bf16"):
+        raise L.BsedError(f"contract: unknown mode {mode!r}")
+    if mode != "fp32" and resident:
+        wtab = pack_weight3s(wsrc, len(taps), N, s_tap, s_k, s_n, K=CIN)
+        return igemm3s(inp, wtab, N, NB, H, W, taps, bias=bias, epilogue=epilogue)
+    if mode != "fp32" and CIN % 32 == 0:
+        w3 = pack_weight3(wsrc, len(taps), CIN, N, s_tap, s_k, s_n)
+        return igemm3(inp, w3, N, NB, H, W, CIN, taps, bias=bias, epilogue=epilogue, valid=valid)
+    wpk = pack_weight(wsrc, len(taps), CIN, N, s_tap, s_k, s_n)
+    return igemm(inp, wpk, N, NB, H, W, CIN, taps=taps, bias=bias, epilogue=epilogue, valid=valid)
+
+
 def wgrad(inp, dy, NB, H, W, CIN, N, taps=((0, 0),), in_pitch=None, dy_pitch=None, a_scale=None, a_shift=None,
           in_offset=0, dy_offset=0, *, mode, bn_y=None, bn_coef=None, bn_mean=None, dy_out=None):
     """Partial slabs of dW; returns (part, G, CINP, NP).  mode: the caller's conv_mode -- "fp32" = the fp32-core
@@ -473,9 +471,8 @@ def wgrad(inp, dy, NB, H, W, CIN, N, taps=((0, 0),), in_pitch=None, dy_pitch=Non
         raise L.BsedError(f"wgrad: unknown mode {mode!r}")
     sfx = "3" if mode in ("bf16x3", "bf16") else ""
     d = WgradDesc()
-    TH, TW = tile_for(W)
+    _tile_taps(d, H, W, taps)
     CINP, NP = round_up(CIN, 32), round_up(N, 32)
-    ntiles = NB * ((H + TH - 1) // TH) * (W // TW)
     d.in_ = _dp(inp, in_offset); d.dy = _dp(dy, dy_offset)
     d.a_scale = _p(a_scale); d.a_shift = _p(a_shift)
     d.act_bf16 = _abf(inp, dy, bn_y, dy_out)
@@ -485,11 +482,6 @@ def wgrad(inp, dy, NB, H, W, CIN, N, taps=((0, 0),), in_pitch=None, dy_pitch=Non
     d.in_pitch = CIN if in_pitch is None else in_pitch
     d.dy_pitch = N if dy_pitch is None else dy_pitch
     d.NB, d.H, d.W, d.CIN, d.CINP, d.N, d.NP, d.G = NB, H, W, CIN, CINP, N, NP, 0
-    d.TH, d.TW = TH, TW
-    d.hh = max(abs(t[0]) for t in taps); d.hw = max(abs(t[1]) for t in taps)
-    d.ntaps = len(taps)
-    for i, (a, b) in enumerate(taps):
-        d.dh[i], d.dw[i] = a, b
     G = getattr(L.lib(), f"bsed_wgrad{sfx}_auto_g")(ctypes.byref(d))
     if G <= 0:
         raise L.BsedError("bsed_wgrad_auto_g: " + L.lib().bsed_last_error().decode())

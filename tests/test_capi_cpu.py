@@ -110,3 +110,55 @@ def test_header_parser_refuses_what_it_does_not_know(tmp_path):
         h.write_text(decl + "\n")
         with pytest.raises(L.BsedError):
             L.parse_header(str(h))
+
+
+# ---- tile-geometry validation of the contraction entry points: every check runs before the first HIP call ----
+_CONV_ENTRIES = ("bsed_igemm", "bsed_igemm3", "bsed_igemm3s", "bsed_igemm3n", "bsed_wgrad", "bsed_wgrad3")
+_GEOMETRY_DEFECTS = {
+    "TW=3": dict(TW=3),
+    "TW does not divide W": dict(W=24),
+    "TH*TW != 128": dict(TH=4),
+    "tap outside the halo": dict(dh0=-2),
+    "ntaps=10": dict(ntaps=10),
+    "NP not a multiple of 32": dict(NP=48),
+}
+
+
+def _conv_desc(entry, TW=16, TH=8, W=16, dh0=-1, ntaps=9, NP=32):
+    """A 3 x 3, 32 -> 32 channel contraction over (2, 16, 16) that every entry point accepts, with dummy non-null
+    pointers (never dereferenced on the host), except for what the keyword arguments break."""
+    wg = entry.startswith("bsed_wgrad")
+    d = L.STRUCTS["BsedWgradDesc" if wg else "BsedIgemmDesc"]()
+    dummy = 0x1000
+    d.in_ = dummy
+    d.in_pitch = 32
+    d.NB, d.H, d.W, d.CIN, d.N, d.NP = 2, 16, W, 32, 32, NP
+    d.TH, d.TW, d.hh, d.hw = TH, TW, 1, 1
+    d.ntaps = ntaps
+    for i in range(9):
+        d.dh[i], d.dw[i] = i // 3 - 1, i % 3 - 1
+    d.dh[0] = dh0
+    if wg:
+        d.dy = d.part = dummy
+        d.dy_pitch, d.CINP, d.G = 32, 32, 1
+    else:
+        d.w = d.out = dummy
+        d.out_pitch = d.e_pitch = 32
+        d.ph = d.pw = 1
+        d.Hp, d.Wp = 16, W
+        d.epilogue = L.CONSTANTS["BSED_EPI_PLAIN"]
+    return d
+
+
+@pytest.mark.parametrize("defect", list(_GEOMETRY_DEFECTS))
+@pytest.mark.parametrize("entry", _CONV_ENTRIES)
+def test_ill_formed_tile_geometry_is_rejected_before_any_hip_call(entry, defect):
+    lib = L.lib()
+    d = _conv_desc(entry, **_GEOMETRY_DEFECTS[defect])
+    args = (ctypes.byref(d), 1, None) if entry == "bsed_igemm3s" else (ctypes.byref(d), None)
+    rc = getattr(lib, entry)(*args)
+    msg = lib.bsed_last_error().decode()
+    assert rc == -1, (entry, defect, rc, msg)                     # BSED_ERR_ARG: no HIP call was reached
+    # wgrad_prepare serves both weight-gradient entries and reports as bsed_wgrad
+    prefix = "bsed_wgrad:" if entry == "bsed_wgrad3" else entry + ":"
+    assert msg.startswith(prefix), (entry, defect, msg)
