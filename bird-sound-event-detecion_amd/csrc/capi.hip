@@ -15,22 +15,34 @@ void bsed_set_error(const char* fmt, ...) {
 extern "C" const char* bsed_last_error(void) { return g_err; }
 extern "C" const char* bsed_build_info(void) { return "libbsed gfx950: fp32 storage/accumulation, split-fp32 (bf16x3) contractions on v_mfma_f32_32x32x16_bf16 by default, "
          "exact-fp32 v_mfma_f32_32x32x2_f32 kernels selectable (hand-written HIP)"; }
-extern "C" int bsed_abi_version(void) { return 2; }
+extern "C" int bsed_abi_version(void) { return 3; }
 
 // ----------------------------------------------------------------------------------------------
-// Device-resident step state (HIP-graph replays of a train step, engine.SEDTrainer.capture): a captured launch bakes
-// its scalar arguments, so what changes from step to step -- the dropout seed and the optimizer's step count -- is ALSO
-// read from device memory: every kernel that takes a seed adds *seed_add to it, the Adam kernel adds *step_add to its
-// step, and bsed_step_state_advance (a node of the graph) bumps both.  Eager steps leave the pointers null (or the
-// values zero): same effective seeds and steps, same bits.
+// Device-resident step state (HIP-graph replays of a train step, engine.SEDTrainer.capture_step): a captured launch
+// bakes its scalar arguments, so what changes from step to step -- the dropout seed, the optimizer's step count and the
+// learning rate -- is ALSO read from device memory.  While the pointers are set,
+//   - the dropout kernels of the plain train step add *seed_add to their seed: bsed_dropout, bsed_block0_fwd / _bwd,
+//     bsed_glu_fwd3 / bsed_glu_bwd3 / bsed_glu_bwd3n, bsed_glu16_fwd / _bwd, bsed_glu_bwd_fused and the GLU_POOL /
+//     GLU_BWD epilogues of bsed_igemm.  bsed_leaky_dropout_fwd / _bwd (discriminator) and bsed_mel_noise (mean teacher)
+//     do NOT: no step that can be captured reaches them;
+//   - bsed_adam_step adds *step_add to its step count and takes *lr instead of its lr argument;
+//   - bsed_step_state_advance (a node of the graph) bumps the two addends.
+// Null pointers = eager mode (the default): the host scalars alone, the same arithmetic, the same bits.  The pointers
+// are PROCESS-global and read on the host at launch time: a caller that launches an eager step while they are set must
+// clear them around it (engine.SEDTrainer.train_step does).
 // ----------------------------------------------------------------------------------------------
 static const uint64_t* g_seed_add = nullptr;
 static const int* g_step_add = nullptr;
+static const float* g_lr = nullptr;
 const uint64_t* bsed_seed_add_ptr() { return g_seed_add; }
 const int* bsed_step_add_ptr() { return g_step_add; }
-extern "C" int bsed_set_step_state(const void* seed_add_dev, const void* step_add_dev) {
+const float* bsed_lr_ptr() { return g_lr; }
+extern "C" int bsed_set_step_state(const void* seed_add_dev, const void* step_add_dev, const void* lr_dev) {
+  BSED_CHECK_ARG((seed_add_dev != nullptr) == (step_add_dev != nullptr) && (seed_add_dev != nullptr) == (lr_dev != nullptr),
+                 "bsed_set_step_state: the three pointers are set together or cleared together");
   g_seed_add = (const uint64_t*)seed_add_dev;
   g_step_add = (const int*)step_add_dev;
+  g_lr = (const float*)lr_dev;
   return BSED_OK;
 }
 __global__ void step_state_advance_kernel(uint64_t* seed_add, int* step_add, uint64_t seed_inc, int step_inc) {

@@ -30,6 +30,7 @@ struct GluBwdParams {
   int NB, H, W, TH, TW, lgTW, tilesH, tilesW, ntiles;
   int ph, pw, Hp, Wp;
   float drop_p; uint32_t rng_stream; uint64_t seed;
+  const uint64_t* seed_add;   // device-resident addend of the seed (HIP-graph replays), or null
 };
 
 __device__ __forceinline__ int crow2(int r, int lh) { return (r & 3) + 8 * (r >> 2) + 4 * lh; }
@@ -54,7 +55,7 @@ __global__ __launch_bounds__(NW * 64) void glu_bwd_fused_kernel(const GluBwdPara
   const int m = rbase + li;
   const int sph = P.ph >> 1, spw = P.pw >> 1;
   const float inv_pool = 1.0f / (float)(P.ph * P.pw);
-  const uint32_t dkey = drop_key(P.rng_stream, P.seed), dthr = drop_threshold(P.drop_p);
+  const uint32_t dkey = drop_key(P.rng_stream, P.seed + (P.seed_add ? *P.seed_add : 0)), dthr = drop_threshold(P.drop_p);
   const float dscale = P.drop_p > 0.f ? 1.0f / (1.0f - P.drop_p) : 1.0f;
 
   float bias[NT], sdb[NT], sgs[NT], sgy[NT];
@@ -318,7 +319,7 @@ extern "C" int bsed_glu_bwd_fused(const float* y, const float* scale, const floa
   BSED_CHECK_ARG(ntiles < (1L << 31) && G <= ntiles, "bsed_glu_bwd_fused: G must not exceed the %ld tiles", ntiles);
   P.ntiles = (int)ntiles;
   P.ph = ph; P.pw = pw; P.Hp = H / ph; P.Wp = W / pw;
-  P.drop_p = drop_p; P.rng_stream = rng_stream; P.seed = seed;
+  P.drop_p = drop_p; P.rng_stream = rng_stream; P.seed = seed; P.seed_add = bsed_seed_add_ptr();
   hipStream_t s = (hipStream_t)stream;
   if (C == 128) return launch_glu_bwd<128, 8>(P, G, s);
   if (C == 64) return launch_glu_bwd<64, 4>(P, G, s);

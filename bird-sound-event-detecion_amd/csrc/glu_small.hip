@@ -49,7 +49,8 @@ __device__ __forceinline__ f32x4 mm16(const float (&a)[4], float b0, float b1, f
 __global__ __launch_bounds__(GS_THREADS) void glu16_fwd_kernel(
     const float* __restrict__ y, const float* __restrict__ scale, const float* __restrict__ shift,
     const float* __restrict__ wg, const float* __restrict__ bg, float* __restrict__ out, int B, int H, int W, int ph,
-    int pw, float drop_p, uint32_t rng_stream, uint64_t seed) {
+    int pw, float drop_p, uint32_t rng_stream, uint64_t seed, const uint64_t* __restrict__ seed_add) {
+  if (seed_add) seed += *seed_add;
   constexpr int C = GS_C;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, p = lane & 15, q = lane >> 4;
   const int col = wave * 16 + p;
@@ -105,7 +106,8 @@ __global__ __launch_bounds__(GB16_THREADS, 3) void glu16_bwd_kernel(
     const float* __restrict__ wg, const float* __restrict__ bg, const float* __restrict__ dpool,
     float* __restrict__ g_out, float* __restrict__ part_dw /*(G,C,C)*/, float* __restrict__ part_db /*(G,2,C)*/,
     float* __restrict__ part_st /*(G,2,C)*/, int B, int H, int W, int ph, int pw, float drop_p, uint32_t rng_stream,
-    uint64_t seed) {
+    uint64_t seed, const uint64_t* __restrict__ seed_add) {
+  if (seed_add) seed += *seed_add;
   constexpr int C = GS_C;
   __shared__ float red[GB16_THREADS * 17];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, p = lane & 15, q = lane >> 4;
@@ -241,7 +243,8 @@ extern "C" int bsed_glu16_fwd(const float* y, const float* scale, const float* s
   const long items = (long)B * (H / ph);
   BSED_CHECK_ARG(items > 0, "bsed_glu16_fwd: empty pooled extent");
   hipLaunchKernelGGL(glu16_fwd_kernel, dim3((unsigned)std::min<long>(items, 8192)), dim3(GS_THREADS), 0,
-                     (hipStream_t)stream, y, scale, shift, wg, bg, out, B, H, W, ph, pw, drop_p, rng_stream, seed);
+                     (hipStream_t)stream, y, scale, shift, wg, bg, out, B, H, W, ph, pw, drop_p, rng_stream, seed,
+                     bsed_seed_add_ptr());
   BSED_LAUNCH_CHECK();
   return BSED_OK;
 }
@@ -257,7 +260,8 @@ extern "C" int bsed_glu16_bwd(const float* y, const float* scale, const float* s
                  "bsed_glu16_bwd: bad shape");
   BSED_CHECK_ARG((long)B * H * ((W + 63) / 64) + G < (1L << 31), "bsed_glu16_bwd: too many rows");
   hipLaunchKernelGGL(glu16_bwd_kernel, dim3(G), dim3(GB16_THREADS), 0, (hipStream_t)stream, y, scale, shift, wg, bg,
-                     dpool, g_out, part_dw, part_db, part_st, B, H, W, ph, pw, drop_p, rng_stream, seed);
+                     dpool, g_out, part_dw, part_db, part_st, B, H, W, ph, pw, drop_p, rng_stream, seed,
+                     bsed_seed_add_ptr());
   BSED_LAUNCH_CHECK();
   return BSED_OK;
 }

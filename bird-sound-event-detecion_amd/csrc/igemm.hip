@@ -29,6 +29,7 @@ enum { EPI_PLAIN = 0, EPI_STATS = 1, EPI_GLU_POOL = 2, EPI_GLU_BWD = 3, EPI_ADD_
 struct IgemmParams {
   BsedIgemmDesc d;
   int PW, PH, PP, lgTW, b_off, pw_magic;  // derived on the host; pos / PW == (pos * pw_magic) >> 20
+  const uint64_t* seed_add;               // device-resident addend of d.seed (HIP-graph replays), or null
 };
 
 __device__ __forceinline__ int crow(int r, int lh) { return (r & 3) + 8 * (r >> 2) + 4 * lh; }
@@ -136,7 +137,7 @@ __global__ __launch_bounds__(IG_THREADS) void igemm_kernel(const IgemmParams P) 
   float* Cs = smem;                          // [128][BN+1]
   const int sph = p.ph >> 1, spw = p.pw >> 1;  // pooling windows are 1 or 2
   const float inv_pool = 1.0f / (float)(p.ph * p.pw);
-  const uint32_t dkey = drop_key(p.rng_stream, p.seed);
+  const uint32_t dkey = drop_key(p.rng_stream, p.seed + (P.seed_add ? *P.seed_add : 0));
   const uint32_t dthr = drop_threshold(p.drop_p);
   const float dscale = p.drop_p > 0.f ? 1.0f / (1.0f - p.drop_p) : 1.0f;
   const int nbase = n0 + li;
@@ -1537,6 +1538,7 @@ extern "C" int bsed_igemm(const BsedIgemmDesc* desc, void* stream) {
   BSED_CHECK_ARG(desc, "bsed_igemm: null descriptor");
   IgemmParams P;
   P.d = *desc;
+  P.seed_add = bsed_seed_add_ptr();
   BsedIgemmDesc& d = P.d;
   BSED_CHECK_ARG(d.in && d.w && d.out, "bsed_igemm: null tensor");
   const int ntiles = bsed_tile_geometry(P, "bsed_igemm", 16, 4);

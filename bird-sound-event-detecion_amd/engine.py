@@ -16,6 +16,8 @@ and discriminator live in ONE flat arena (``parallel.GradArena``) whose all-redu
 but the first two CNN blocks' has been enqueued, and overlaps the rest of it; the 1/world factor is folded into
 the optimizer kernel.
 """
+import functools
+
 import numpy as np
 
 import torch
@@ -203,6 +205,34 @@ class FlatSGD:
 
 
 # ----------------------------------------------------------------------------- the train step
+# The trainer whose captured graph the library's device-resident step state belongs to (capture_step .. release_graph),
+# or None.  That state is ONE set of pointers per process, read on the host whenever a dropout or Adam kernel is
+# launched (csrc/capi.hip): every eager step of ANY trainer has to run with the pointers cleared.
+_armed = None
+
+
+def _eager_step(step):
+    """An eager step (train_step / train_step_isp) while some trainer holds a captured graph: the library is pointed
+    away from the graph's device-resident step state for the duration of the step, so the kernels take the host's
+    scalars alone, exactly as without a graph in the process.  If the graph is this trainer's own, the step is one step
+    of ITS sequence: the same ``bsed_step_state_advance`` the graph ends with is enqueued behind it, so the next replay
+    continues one step later (the scalars baked at capture never move)."""
+    @functools.wraps(step)
+    def run(self, *args, **kwargs):
+        owner = _armed
+        if owner is None:
+            return step(self, *args, **kwargs)
+        owner._bind_step_state(False)
+        try:
+            out = step(self, *args, **kwargs)
+        finally:
+            owner._bind_step_state(True)
+        if owner is self:
+            self._advance_step_state()
+        return out
+    return run
+
+
 class SEDTrainer:
     """One object = the state of a training run on ONE GPU (rank).  ``train_step`` is one iteration of the
     reference's ``train_mt`` loop body."""
@@ -232,6 +262,7 @@ class SEDTrainer:
         # the packed weight copies a step needs, made in ONE launch at its start from the second step on
         # (ops.PackPlan; None: one launch per weight at first use, the pre-plan behaviour)
         self._pack_plans = {}
+        self._graph = None          # capture_step / replay_step / release_graph
         self.world = 1
         self.rank = 0
         if process_group is not None or (torch.distributed.is_available() and torch.distributed.is_initialized()):
@@ -352,6 +383,7 @@ class SEDTrainer:
         """wait for the early segment's all-reduce (started inside the last backward pass), exchange the tail"""
         self.arena.finish()
 
+    @_eager_step
     def train_step(self, syn_x, syn_y, real_x=None, real_y_weak=None, real_x_ema=None, consistency_cost=None,
                    from_wave=False, next_waves=None):
         """One iteration (see ``_train_step`` for the arguments).  With the EMA teacher on its own stream the step itself
@@ -498,14 +530,32 @@ class SEDTrainer:
         """Capture the plain train step (synthetic batch only: BASELINE configs[2], the reference's ``train_mt`` without
         ``-mt``) of THIS shape in a HIP graph.  At the reference's batch of 24 (src/data/config.py:70) a step is ~95
         launches of 10-40 us each and the host needs 2.6 ms to enqueue what the GPU runs in < 2 ms: replaying a graph
-        removes the host from the loop.  What changes from step to step lives in DEVICE memory: the dropout seed addend
-        and the optimizer's step count (``bsed_set_step_state``), advanced by a node of the graph itself; inputs are
-        copied into the graph's static tensors.  ``warmup`` eager steps run first (allocator, weight-pack plan, lazy
-        tables).  Returns after the capture; then call ``replay_step(syn_x, syn_y)``.  Replayed steps are bit-identical
-        to eager ones (tests/test_graph_step_gpu.py)."""
+        removes the host from the loop.  ``warmup`` eager steps run first (allocator, weight-pack plan, lazy tables).
+        Returns after the capture; then call ``replay_step(syn_x, syn_y)``.
+
+        What changes from step to step lives in DEVICE memory (``bsed_set_step_state``): an addend of every dropout seed
+        and of Adam's step count, both advanced by the last node of the graph, and the learning rate, which
+        ``replay_step`` refreshes from ``optimizer.lr``; inputs are copied into the graph's static tensors.  The contract,
+        for every ``conv_mode`` and A/B switch of the model (tests/test_graph_step_gpu.py): a sequence of steps gives the
+        same bits whether its steps are replayed or eager, including
+          - ``train_step`` calls of this trainer between replays (any batch size: the last batch of an epoch) -- they
+            run on the host's scalars and advance the device state by one step;
+          - ``adjust_learning_rate`` / any assignment to ``optimizer.lr`` between steps;
+          - eager steps of OTHER trainers in the process, which never see this trainer's state.
+        Refused with ``BsedError``: EMA teacher, discriminator, a data-parallel group (their per-step host decisions
+        are not graph nodes), an optimizer other than ``FlatAdam`` (its per-step scalars are not device-resident), and a
+        capture while another trainer of the process holds a graph (the library has one step state per process)."""
+        global _armed
         if self.ema_crnn is not None or self.domain_loss is not None or self.world != 1:
             raise L.BsedError("capture_step covers the plain single-rank step (no EMA teacher, no discriminator, no "
                               "data-parallel group: their per-step host decisions are not graph nodes yet)")
+        if not isinstance(self.optimizer, FlatAdam):
+            raise L.BsedError("capture_step needs a FlatAdam optimizer: only its step count and learning rate are read "
+                              "from device memory by a replayed step")
+        if _armed is not None and _armed is not self:
+            raise L.BsedError("capture_step: another trainer of this process holds a captured graph (the library keeps "
+                              "one device-resident step state per process): release_graph() it first")
+        self.release_graph()
         dev = self.crnn.flat.device
         self._g_x = syn_x.clone()
         self._g_y = syn_y.clone()
@@ -514,25 +564,59 @@ class SEDTrainer:
             self._train_step(self._g_x, self._g_y, from_wave=from_wave)
         # device-resident step state: zero addends now, the baked scalars are those of THIS step
         self._g_state = torch.zeros(4, device=dev, dtype=torch.int64)     # [0] seed addend (uint64), [1] step addend (int32)
-        L.check(L.lib().bsed_set_step_state(self._g_state[0:1].data_ptr(), self._g_state[1:2].data_ptr()),
-                "bsed_set_step_state")
+        self._g_lr_host = float(self.optimizer.lr)
+        self._g_lr = torch.full((1,), self._g_lr_host, device=dev, dtype=torch.float32)
+        self._g_seed_inc = (parallel.rank_seed(self.seed, 1, self.rank) - parallel.rank_seed(self.seed, 0, self.rank)) * 4
         self._g_base_step = self.global_step
+        base_count = self.optimizer.step_count
         torch.cuda.synchronize()
-        self._graph = torch.cuda.CUDAGraph()
-        seed_inc = (parallel.rank_seed(self.seed, 1, self.rank) - parallel.rank_seed(self.seed, 0, self.rank)) * 4
-        with torch.cuda.graph(self._graph):
-            out = self._train_step(self._g_x, self._g_y, from_wave=from_wave)
-            L.check(L.lib().bsed_step_state_advance(self._g_state[0:1].data_ptr(), self._g_state[1:2].data_ptr(),
-                                                    seed_inc, 1, L.stream()), "bsed_step_state_advance")
-        self._g_out = out
-        # the capture ran no kernel: undo its host-side bookkeeping (the first replay IS that step)
-        self.global_step = self._g_base_step
-        self.optimizer.step_count -= 1
+        graph = torch.cuda.CUDAGraph()
+        self._bind_step_state(True)
+        try:
+            with torch.cuda.graph(graph):
+                out = self._train_step(self._g_x, self._g_y, from_wave=from_wave)
+                self._advance_step_state()
+        except BaseException:
+            self._bind_step_state(False)
+            raise
+        finally:
+            # the capture ran no kernel: undo its host-side bookkeeping (the first replay IS that step)
+            self.global_step = self._g_base_step
+            self.optimizer.step_count = base_count
+        self._graph, self._g_out = graph, out
+        _armed = self
         return self
 
+    def _bind_step_state(self, on):
+        """point the library at this trainer's device-resident step state, or back at the host scalars alone"""
+        s = self._g_state
+        L.check(L.lib().bsed_set_step_state(s[0:1].data_ptr(), s[1:2].data_ptr(), self._g_lr.data_ptr()) if on
+                else L.lib().bsed_set_step_state(None, None, None), "bsed_set_step_state")
+
+    def _advance_step_state(self):
+        """one step further, in stream order: the last node of the graph, and what an eager step between replays enqueues"""
+        s = self._g_state
+        L.check(L.lib().bsed_step_state_advance(s[0:1].data_ptr(), s[1:2].data_ptr(), self._g_seed_inc, 1, L.stream()),
+                "bsed_step_state_advance")
+
     def replay_step(self, syn_x, syn_y):
-        """one captured step on new inputs (same shapes and dtypes as at capture); returns the same dict of device
-        tensors as ``train_step`` (overwritten by the next replay)"""
+        """One captured step on new inputs: tensors of exactly the captured shapes and dtypes, on the captured device (or
+        in host memory: the copy into the static tensor uploads them); anything else raises ``BsedError`` before
+        anything is copied or launched.  The step uses the optimizer's current ``lr``.  Returns the same dict of device
+        tensors as ``train_step`` (overwritten by the next replay)."""
+        if self._graph is None:
+            raise L.BsedError("replay_step: this trainer holds no captured graph (capture_step makes one, release_graph "
+                              "drops it)")
+        for name, t, g in (("syn_x", syn_x, self._g_x), ("syn_y", syn_y, self._g_y)):
+            if not isinstance(t, torch.Tensor) or t.shape != g.shape or t.dtype != g.dtype or \
+                    (t.device != g.device and t.device.type != "cpu"):
+                got = (tuple(t.shape), t.dtype, t.device) if isinstance(t, torch.Tensor) else type(t).__name__
+                raise L.BsedError(f"replay_step: {name} must be {tuple(g.shape)} {g.dtype} on {g.device} as captured, "
+                                  f"got {got}")
+        lr = float(self.optimizer.lr)
+        if lr != self._g_lr_host:
+            self._g_lr.fill_(lr)
+            self._g_lr_host = lr
         self._g_x.copy_(syn_x, non_blocking=True)
         self._g_y.copy_(syn_y, non_blocking=True)
         self._graph.replay()
@@ -541,11 +625,15 @@ class SEDTrainer:
         return self._g_out
 
     def release_graph(self):
-        """back to eager steps: the library stops reading the device-resident step state"""
-        L.check(L.lib().bsed_set_step_state(None, None), "bsed_set_step_state")
+        """back to eager steps only: the library stops reading the device-resident step state, the graph is dropped"""
+        global _armed
+        if _armed is self:
+            self._bind_step_state(False)
+            _armed = None
         self._graph = None
 
     # ------------------------------------------------------------------ ISP (shift-consistency) iteration
+    @_eager_step
     def train_step_isp(self, syn_x, syn_y, real_x, real_y_weak, real_x_ema, shift_frames, shift_bins,
                        consistency_cost=None, pooling_time_ratio=4):
         """One iteration of ``train_mt`` with ``-mt -ISP`` (reference src/main_baseline.py:229-277,337-420,431-529):

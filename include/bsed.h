@@ -508,10 +508,15 @@ int bsed_selftest_mfma(const float* A, const float* B, float* C, int K, void* st
 /* the same through v_mfma_f32_32x32x16_bf16 with bf16x3 split operands (K a multiple of 16) */
 int bsed_selftest_mfma_bf16x3(const float* A, const float* B, float* C, int K, void* stream);
 
-/* Device-resident step state for HIP-graph replays of a train step (csrc/capi.hip): when set, every kernel that takes a
- * dropout seed adds *seed_add_dev (uint64) to it and the Adam kernel adds *step_add_dev (int) to its step count;
- * bsed_step_state_advance is the graph node that bumps both after a step.  NULL, NULL = eager mode (the default). */
-int bsed_set_step_state(const void* seed_add_dev, const void* step_add_dev);
+/* Device-resident step state for HIP-graph replays of a train step (csrc/capi.hip).  While it is set, the dropout kernels
+ * of the plain train step -- bsed_dropout, bsed_block0_fwd / _bwd, bsed_glu_fwd3, bsed_glu_bwd3, bsed_glu_bwd3n,
+ * bsed_glu16_fwd / _bwd, bsed_glu_bwd_fused and the GLU_POOL / GLU_BWD epilogues of bsed_igemm -- add *seed_add_dev
+ * (uint64) to their seed, and bsed_adam_step adds *step_add_dev (int) to its step count and uses *lr_dev (float) in
+ * place of its lr argument.  bsed_leaky_dropout_fwd / _bwd and bsed_mel_noise do not read it.
+ * bsed_step_state_advance is the graph node that bumps the two addends after a step.  The state is process-global and
+ * read on the host when a kernel is launched.  All three NULL = eager mode (the default); a mix of NULL and non-NULL is
+ * refused. */
+int bsed_set_step_state(const void* seed_add_dev, const void* step_add_dev, const void* lr_dev);
 int bsed_step_state_advance(void* seed_add_dev, void* step_add_dev, uint64_t seed_inc, int step_inc, void* stream);
 
 #ifdef __cplusplus

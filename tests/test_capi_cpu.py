@@ -36,6 +36,18 @@ def test_error_convention_without_gpu():
     assert rc < 0 and b"null" in lib.bsed_last_error()
 
 
+def test_step_state_pointers_are_set_or_cleared_together():
+    """bsed_set_step_state (ABI 3: seed addend, step addend, learning rate) only stores pointers -- no HIP call -- and
+    refuses a mix of null and non-null ones: a half-armed library would replay a graph with one scalar still baked"""
+    lib = L.lib()
+    assert lib.bsed_abi_version() >= 3
+    assert len(L.FUNCTIONS["bsed_set_step_state"][1]) == 3
+    assert lib.bsed_set_step_state(None, None, None) == 0
+    for mixed in ((64, None, None), (None, 64, 64), (64, 64, None)):
+        assert lib.bsed_set_step_state(*mixed) < 0 and b"together" in lib.bsed_last_error()
+    assert lib.bsed_set_step_state(None, None, None) == 0
+
+
 def test_no_cpu_fallback():
     import torch
     if torch.cuda.is_available():
