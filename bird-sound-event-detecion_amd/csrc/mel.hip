@@ -23,6 +23,7 @@
 //                     partials that mel_sumsq_finish_kernel adds in fixed order (no float atomics).
 //   mel_noise_kernel: x + N(0, std_bin) with Philox/Box-Muller (or injected unit noise).
 //   mel_db_kernel   : 10*log10(max(1e-10, x^2)) clamped to (clip max - 80 dB), zero pad/trunc.
+//   mel_db_views_kernel : the same plus the ISP step's time-rolled and frequency-rolled views, one read, three writes.
 #include "bsed_common.h"
 #include "../../include/bsed.h"
 #include <math.h>
@@ -734,6 +735,78 @@ __global__ void mel_db_kernel(const float* __restrict__ x, const float* __restri
   }
 }
 
+// mel_db_kernel plus the two rolled views of the ISP step (per-sample torch.roll of the PADDED / TRUNCATED tensor along
+// time by sh[b] and along frequency by sw[b]) from ONE read of the linear mel and one logarithm per element.
+// n_mels = 128: a row is 512 B = 32 lanes x float4, a wave takes two rows per pass (lanes 0-31 / 32-63) and a
+// workgroup of four waves MV_ROWS rows, MV_ROWS / 8 independent passes whose loads are all issued before the first
+// logarithm.  The time roll renumbers rows: the same float4 goes to row t and to row (t + sh) mod T_out, both 16-byte
+// aligned.  The frequency roll by s = 4 q + r moves band 4 l + j of the output row to source band 4 (l - q) + (j - r):
+// component (j - r) & 3 of lane l - q (j >= r) or of lane l - q - 1 (j < r).  q and r are uniform over the workgroup
+// (one clip per blockIdx.y), so every lane first rotates its own float4 by r (uniform selects) and output component j
+// is then ONE ds_bpermute_b32 pull inside the lane's half-wave: four cross-lane moves per float4, no LDS allocation,
+// no barrier, and the rolled row leaves as a full-width store as well.  The dB expression is mel_db_kernel's, letter
+// for letter: the three outputs are bitwise that kernel's output and its permutations.
+#define MV_THREADS 256
+#define MV_ROWS 32
+#define MV_PASSES (MV_ROWS / (2 * MV_THREADS / 64))
+
+__global__ __launch_bounds__(MV_THREADS) void mel_db_views_kernel(const float* __restrict__ x, const float* __restrict__ clip_max,
+                                                                  const int* __restrict__ sh, const int* __restrict__ sw,
+                                                                  float* __restrict__ out, float* __restrict__ out_t,
+                                                                  float* __restrict__ out_f, int T, int T_out, float top_db) {
+  const int n_mels = 128;
+  const int b = blockIdx.y;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, l = lane & 31, hb = lane & 32;
+  const float mx = clip_max[b];
+  const float floor_db = 10.0f * log10f(fmaxf(1e-10f, mx * mx)) - top_db;
+  int st = sh[b] % T_out, sf = sw[b] % n_mels;
+  if (st < 0) st += T_out;
+  if (sf < 0) sf += n_mels;
+  const int q = sf >> 2, r = sf & 3;
+  const int la = ((l - q) & 31) | hb, lb = ((l - q - 1) & 31) | hb;   // source lanes, inside this half-wave
+  const float* xb = x + (size_t)b * T * n_mels + 4 * l;
+  const size_t ob = (size_t)b * T_out * n_mels + 4 * l;
+  const int t0 = blockIdx.x * MV_ROWS + 2 * wv + (lane >> 5);
+  float4 a4[MV_PASSES];
+#pragma unroll
+  for (int k = 0; k < MV_PASSES; ++k) {
+    const int t = t0 + 8 * k;
+    a4[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (t < T && t < T_out) a4[k] = *reinterpret_cast<const float4*>(xb + (size_t)t * n_mels);
+  }
+#pragma unroll
+  for (int k = 0; k < MV_PASSES; ++k) {
+    const int t = t0 + 8 * k;           // uniform over a half-wave, and so is everything decided by it
+    float e[4] = {a4[k].x, a4[k].y, a4[k].z, a4[k].w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float a = e[j];
+      const float v = fmaxf(10.0f * log10f(fmaxf(1e-10f, a * a)), floor_db);
+      e[j] = t < T ? v : 0.f;           // pad rows: 0 dB (a select, not a branch around the logarithm)
+    }
+    const float4 v4 = make_float4(e[0], e[1], e[2], e[3]);
+    // own float4 rotated by r in two select stages: g[j] = e[(j - r) & 3]; the pulls below run with every lane active
+    // (only the stores are predicated)
+    float h[4], g[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) h[j] = (r & 1) ? e[(j + 3) & 3] : e[j];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) g[j] = (r & 2) ? h[(j + 2) & 3] : h[j];
+    float4 f4;
+    f4.x = __shfl(g[0], 0 >= r ? la : lb, 64);
+    f4.y = __shfl(g[1], 1 >= r ? la : lb, 64);
+    f4.z = __shfl(g[2], 2 >= r ? la : lb, 64);
+    f4.w = __shfl(g[3], la, 64);
+    if (t < T_out) {
+      int tr = t + st;
+      if (tr >= T_out) tr -= T_out;
+      *reinterpret_cast<float4*>(out + ob + (size_t)t * n_mels) = v4;
+      *reinterpret_cast<float4*>(out_t + ob + (size_t)tr * n_mels) = v4;
+      *reinterpret_cast<float4*>(out_f + ob + (size_t)t * n_mels) = f4;
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------
@@ -937,6 +1010,23 @@ extern "C" int bsed_mel_db(const float* mel_lin, const float* clip_max, int B, i
   dim3 grid((unsigned)std::min<size_t>(ceil_div(per, 256), 64), B);
   hipLaunchKernelGGL(mel_db_kernel, grid, dim3(256), 0, (hipStream_t)stream, mel_lin, clip_max, out_db, T,
                      T_out, n_mels, top_db);
+  BSED_LAUNCH_CHECK();
+  return BSED_OK;
+}
+
+extern "C" int bsed_mel_db_views(const float* mel_lin, const float* clip_max, int B, int T, int T_out, int n_mels,
+                                 float top_db, const int* shift_frames, const int* shift_bins, float* out_db,
+                                 float* out_db_tshift, float* out_db_fshift, void* stream) {
+  BSED_CHECK_ARG(mel_lin && clip_max && shift_frames && shift_bins && out_db && out_db_tshift && out_db_fshift,
+                 "bsed_mel_db_views: null argument");
+  BSED_CHECK_ARG(B > 0 && B <= 65535 && T > 0 && T_out > 0 && n_mels > 0, "bsed_mel_db_views: bad shape");
+  BSED_CHECK_ARG(out_db != out_db_tshift && out_db != out_db_fshift && out_db_tshift != out_db_fshift,
+                 "bsed_mel_db_views: the three outputs must be distinct buffers");
+  BSED_CHECK_ARG(n_mels == 128, "bsed_mel_db_views: built for n_mels = 128 (a row is 32 lanes x float4), got %d", n_mels);
+  const uintptr_t align = (uintptr_t)mel_lin | (uintptr_t)out_db | (uintptr_t)out_db_tshift | (uintptr_t)out_db_fshift;
+  BSED_CHECK_ARG((align & 15) == 0, "bsed_mel_db_views: mel_lin and the outputs must be 16-byte aligned");
+  hipLaunchKernelGGL(mel_db_views_kernel, dim3(ceil_div(T_out, MV_ROWS), B), dim3(MV_THREADS), 0, (hipStream_t)stream,
+                     mel_lin, clip_max, shift_frames, shift_bins, out_db, out_db_tshift, out_db_fshift, T, T_out, top_db);
   BSED_LAUNCH_CHECK();
   return BSED_OK;
 }

@@ -333,8 +333,10 @@ class SEDTrainer:
                 ev.record()
                 self._uploaded[id(w)] = (w, slots[i], ev, step)
 
-    def _features(self, wav, noisy=False, step=None):
-        pre = self._prefetched.pop(id(wav), None)
+    def _features(self, wav, noisy=False, step=None, views=None):
+        """views: (shift_frames, shift_bins) of the ISP step -- every input comes back as the triple (x, x time-rolled,
+        x frequency-rolled); such inputs are never prefetched"""
+        pre = self._prefetched.pop(id(wav), None) if views is None else None
         if pre is not None and pre[0] is wav and pre[1] == (noisy, self.global_step):
             # computed on the feature stream during the previous step (train_step(..., next_waves=...)): same kernels,
             # same seed, same values
@@ -344,7 +346,7 @@ class SEDTrainer:
             return pre[2]
         dwav = self._device_wave(wav)
         T = self.frontend.num_frames(dwav.shape[1])
-        return self.frontend.transform(dwav, max_frames=T, noisy=noisy,
+        return self.frontend.transform(dwav, max_frames=T, noisy=noisy, views=views,
                                        seed=parallel.rank_seed(self.seed, self.global_step if step is None else step, self.rank))
 
     def _drop_stale_inputs(self):
@@ -634,29 +636,69 @@ class SEDTrainer:
 
     # ------------------------------------------------------------------ ISP (shift-consistency) iteration
     @_eager_step
-    def train_step_isp(self, syn_x, syn_y, real_x, real_y_weak, real_x_ema, shift_frames, shift_bins,
-                       consistency_cost=None, pooling_time_ratio=4):
+    def train_step_isp(self, syn_x, syn_y, real_x, real_y_weak, real_x_ema=None, shift_frames=None, shift_bins=None,
+                       consistency_cost=None, pooling_time_ratio=4, from_wave=False):
         """One iteration of ``train_mt`` with ``-mt -ISP`` (reference src/main_baseline.py:229-277,337-420,431-529):
         on top of the mean-teacher step, time-rolled and frequency-rolled views of the synthetic and the real batch go
         through the student (4 extra forward/backward passes) and of the noisy real batch through the teacher (2 extra
         forwards).  shift_frames[k] (a multiple of pooling_time_ratio) / shift_bins[k] are the per-sample rolls the
         reference draws with random.randint(-64,64)*4 / random.randint(-4,4); the first half of the real batch is the
-        weakly labelled half (its weak targets enter the frequency-shift class loss).  dB-mel inputs (B,1,T,F)."""
+        weakly labelled half (its weak targets enter the frequency-shift class loss).
+
+        Inputs: dB-mel tensors (B,1,T,F) -- the rolled views are then ``bsed_roll`` copies -- or, with ``from_wave=True``,
+        (B,n) waveforms (device or host, as ``train_step``): the mel stage runs inside the step and writes every input
+        together with its two views (``MelFrontEnd.transform(views=...)``, one kernel per batch, no roll pass over a
+        full-size input).  real_x_ema=None (waveforms only) draws the noisy twin of the real batch with the step's
+        rank seed, as ``train_step`` does; a given real_x_ema is a dB-mel tensor in both forms.
+
+        With a ``domain_loss`` (src/main_scmt_ada_weak.py:318-339,527-528,568-574: the script's full mode) the domain
+        loss is evaluated once, on the encodings of the two base passes, its feature gradients join the base passes'
+        backward through the gradient-reverse layer, and ``optimizer_d`` steps the discriminator -- the convention of
+        ``train_step``: one forward pair serves the class losses and the domain loss."""
         if self.ema_crnn is None:
             raise L.BsedError("ISP needs the EMA teacher (the reference's consistency_cost only exists with -mt)")
+        if shift_frames is None or shift_bins is None:
+            raise L.BsedError("train_step_isp needs the per-sample shift_frames and shift_bins")
+        if from_wave and self.frontend is None:
+            raise L.BsedError("train_step_isp(from_wave=True) needs a MelFrontEnd")
+        if real_x_ema is None and not from_wave:
+            raise L.BsedError("train_step_isp on dB-mel tensors needs real_x_ema (the noisy twin of the real batch); "
+                              "from_wave=True draws it from the waveforms")
         crnn, pred, ema_c, ema_p = self.crnn, self.predictor, self.ema_crnn, self.ema_predictor
         cc = self.max_consistency_cost if consistency_cost is None else consistency_cost
-        dev = syn_x.device
+        dev = crnn.flat.device
         B, Tp, C = syn_y.shape
-        T, F = syn_x.shape[2], syn_x.shape[3]
         half = real_y_weak.shape[0] // 2
         sh = torch.as_tensor(list(shift_frames), dtype=torch.int32, device=dev)
         sf = torch.as_tensor(list(shift_bins), dtype=torch.int32, device=dev)
         sp = torch.as_tensor([int(v / pooling_time_ratio) for v in shift_frames], dtype=torch.int32, device=dev)
+        # the three inputs and their rolled views: written by the mel stage (waveforms), or rolled where they are used
+        views = {}
+        if from_wave:
+            views["syn"] = self._features(syn_x, views=(sh, sf))
+            if real_x_ema is None:
+                views["real"], views["ema"] = self._features(real_x, noisy=True, views=(sh, sf))
+            else:
+                views["real"] = self._features(real_x, views=(sh, sf))
+            self._drop_stale_inputs()
+            syn_x, real_x = views["syn"][0], views["real"][0]
+            if "ema" in views:
+                real_x_ema = views["ema"][0]
         step_seed = parallel.rank_seed(self.seed, self.global_step, self.rank)
         crnn.train(); pred.train(); ema_c.train(); ema_p.train()
         self.arena.zero_()
+        adv = self.domain_loss is not None
+        if adv:
+            self.domain_loss.domain_discriminator.train()
         syn_x, real_x, real_x_ema = syn_x.contiguous(), real_x.contiguous(), real_x_ema.contiguous()
+        T, F = syn_x.shape[2], syn_x.shape[3]
+        base = {"syn": syn_x, "real": real_x, "ema": real_x_ema}
+
+        def view(which, axis):
+            if which in views:
+                return views[which][1 if axis == "t" else 2]
+            return ops.roll(base[which], B, T, F, sh=sh) if axis == "t" else ops.roll(base[which], B, T, F, sw=sf)
+
         syn_y = syn_y.contiguous()
         y_weak_syn = ops.max_over_time(syn_y)
         n_s, n_w = B * Tp * C, B * C
@@ -678,24 +720,34 @@ class SEDTrainer:
                     st, _, wk, _ = ema_p.run_forward(e)
                     return st, wk
                 strong_e, weak_e = teacher(real_x_ema, 8)
-                strong_e_sh, _ = teacher(ops.roll(real_x_ema, B, T, F, sh=sh), 9)
-                strong_e_fs, _ = teacher(ops.roll(real_x_ema, B, T, F, sw=sf), 10)
+                strong_e_sh, _ = teacher(view("ema", "t"), 9)
+                strong_e_fs, _ = teacher(view("ema", "f"), 10)
             strong_r_roll = ops.roll(sv_r[0], B, Tp, C, sh=sp)      # detached by construction
             strong_s_roll = ops.roll(sv_s[0], B, Tp, C, sh=sp)
             y_s_roll = ops.roll(syn_y, B, Tp, C, sh=sp)
+            dfs = dft = None
+            if adv:
+                # domain loss on the base passes' encodings; its feature gradients arrive through the gradient-reverse
+                # layer and join the class-loss gradients of those two passes
+                out["domain"] = self.domain_loss(None, enc_s, None, enc_r)
+                dfs, dft = self.domain_loss.backward_features()
             dx, out["syn"] = pred.run_backward(enc_s, sv_s, y_strong=syn_y, y_weak=y_weak_syn)
+            if dfs is not None:
+                ops.axpy(dx, dfs)
             crnn.run_backward(ctx_s, dx)
             dx, out["real"] = pred.run_backward(enc_r, sv_r, y_weak=real_y_weak.contiguous(), ema_strong=strong_e,
                                                 ema_weak=weak_e, w_cons_s=cc, w_cons_w=cc)
+            if dft is not None:
+                ops.axpy(dx, dft)
             crnn.run_backward(ctx_r, dx)
             del ctx_s, ctx_r
             # real, time shift: 1/2 cc MSE vs teacher(shifted) + cc/2 MSE vs the rolled (detached) base prediction
-            enc, sv, ctx = fwd(ops.roll(real_x, B, T, F, sh=sh), 2)
+            enc, sv, ctx = fwd(view("real", "t"), 2)
             dx, out["real_shift"] = pred.run_backward(enc, sv, ema_strong=strong_e_sh, w_cons_s=0.5 * cc,
                                                       ema_strong2=strong_r_roll, w_cons_s2=0.5 * cc)
             crnn.run_backward(ctx, dx)
             # real, frequency shift: 1/2 cc MSE vs teacher(freq-shifted); weak BCE on the weakly labelled half only
-            enc, sv, ctx = fwd(ops.roll(real_x, B, T, F, sw=sf), 3)
+            enc, sv, ctx = fwd(view("real", "f"), 3)
             parts, lps = [], []
             for lo, hi, yw in ((0, half, real_y_weak[:half].contiguous()), (half, B, None)):
                 if hi <= lo:
@@ -706,16 +758,18 @@ class SEDTrainer:
             out["real_fshift_weak_half"], out["real_fshift_rest"] = lps[0], lps[-1]
             crnn.run_backward(ctx, torch.cat(parts, 0))
             # synthetic, time shift: strong BCE vs the rolled target + cc/2 MSE vs the rolled (detached) base prediction
-            enc, sv, ctx = fwd(ops.roll(syn_x, B, T, F, sh=sh), 4)
+            enc, sv, ctx = fwd(view("syn", "t"), 4)
             dx, out["syn_shift"] = pred.run_backward(enc, sv, y_strong=y_s_roll, ema_strong=strong_s_roll, w_cons_s=0.5 * cc)
             crnn.run_backward(ctx, dx)
             # synthetic, frequency shift: strong + weak BCE vs the unshifted targets
-            enc, sv, ctx = fwd(ops.roll(syn_x, B, T, F, sw=sf), 5)
+            enc, sv, ctx = fwd(view("syn", "f"), 5)
             dx, out["syn_fshift"] = pred.run_backward(enc, sv, y_strong=syn_y, y_weak=y_weak_syn)
             crnn.run_backward(ctx, dx, on_early_grads=self.arena.begin_early)
         del ctx
         self._all_reduce_grads()
         self.optimizer.step(grad_scale=1.0 / self.world)
+        if adv:
+            self.optimizer_d.step(grad_scale=1.0 / self.world)
         self.global_step += 1
         update_ema_variables(crnn, ema_c, self.ema_alpha, self.global_step)
         update_ema_variables(pred, ema_p, self.ema_alpha, self.global_step)
@@ -737,6 +791,8 @@ class SEDTrainer:
         loss += 0.5 * cc * (g["syn_shift"][2] / n_s + g["real_shift"][4] / n_s)        # consistency_loss_shift
         fs = g["real_fshift_weak_half"][2] + (g["real_fshift_rest"][2] if half < B else 0.0)
         loss += 0.5 * cc * (g["real_shift"][2] / n_s + fs / n_s)                         # 1/2 (strong shift + freq shift vs EMA)
+        if "domain" in out:
+            loss += float(out["domain"])
         return float(loss)
 
     @staticmethod

@@ -90,6 +90,28 @@ class MelFrontEnd:
                L.ptr(out), L.stream())
         return out
 
+    @staticmethod
+    def _shifts(v, B, dev):
+        """per-sample rolls as an int32 device tensor (B): a sequence of ints, or such a tensor passed through"""
+        t = v if isinstance(v, torch.Tensor) else torch.as_tensor([int(s) for s in v], dtype=torch.int32)
+        if t.dtype != torch.int32 or t.numel() != B:
+            raise L.BsedError(f"per-sample shifts must be {B} int32 values, got {tuple(t.shape)} {t.dtype}")
+        return t.to(dev).contiguous()
+
+    def to_db_views(self, mel_lin, clip_max, shift_frames, shift_bins, max_frames=None):
+        """``to_db`` plus the two rolled views of the ISP step from ONE read of the linear mel (``mel_db_views_kernel``):
+        (x, x rolled per sample along time by shift_frames[b], x rolled along frequency by shift_bins[b]), the rolls
+        being ``torch.roll`` of the padded / truncated (max_frames, n_mels) tensor as the reference applies them after
+        ``PadOrTrunc`` (src/main_scmt_ada_weak.py:234-248).  Bitwise ``to_db`` followed by ``ops.roll``."""
+        B, T, M = mel_lin.shape
+        T_out = T if max_frames is None else max_frames
+        sh, sw = self._shifts(shift_frames, B, mel_lin.device), self._shifts(shift_bins, B, mel_lin.device)
+        outs = tuple(torch.empty((B, 1, T_out, M), device=mel_lin.device, dtype=torch.float32) for _ in range(3))
+        ops._note("mel_db_views_kernel", f"T{T_out}", 4.0 * B * T_out * M, 4.0 * B * M * (T + 3 * T_out))
+        L.call("bsed_mel_db_views", L.ptr(mel_lin), L.ptr(clip_max), B, T, T_out, M, self.cfg.top_db,
+               L.ptr(sh, torch.int32), L.ptr(sw, torch.int32), L.ptr(outs[0]), L.ptr(outs[1]), L.ptr(outs[2]), L.stream())
+        return outs
+
     def add_noise(self, mel_lin, bin_sumsq, seed=0, unit_noise=None):
         B, T, M = mel_lin.shape
         noisy = torch.empty_like(mel_lin)
@@ -99,15 +121,22 @@ class MelFrontEnd:
                self.cfg.noise_snr, seed, L.ptr(noisy), L.ptr(cmax), L.stream())
         return noisy, cmax
 
-    def transform(self, wav, max_frames=None, noisy=False, seed=0, unit_noise=None):
-        """waveforms -> dB-mel CRNN input (B,1,max_frames,n_mels) [, noisy twin for the EMA teacher]."""
+    def transform(self, wav, max_frames=None, noisy=False, seed=0, unit_noise=None, views=None):
+        """waveforms -> dB-mel CRNN input (B,1,max_frames,n_mels) [, noisy twin for the EMA teacher].
+        views=(shift_frames, shift_bins): every returned input becomes the triple (x, x time-rolled, x frequency-rolled)
+        of ``to_db_views`` (the ISP step's inputs, without a separate roll pass)."""
         max_frames = self.cfg.max_frames if max_frames is None else max_frames
         mel, cmax, sumsq = self.linear(wav)
-        clean = self.to_db(mel, cmax, max_frames)
+        if views is None:
+            db = lambda m, c: self.to_db(m, c, max_frames)
+        else:
+            sh, sw = (self._shifts(v, mel.shape[0], mel.device) for v in views)
+            db = lambda m, c: self.to_db_views(m, c, sh, sw, max_frames)
+        clean = db(mel, cmax)
         if not noisy:
             return clean
         nz, nmax = self.add_noise(mel, sumsq, seed=seed, unit_noise=unit_noise)
-        return clean, self.to_db(nz, nmax, max_frames)
+        return clean, db(nz, nmax)
 
 
 _default = {}

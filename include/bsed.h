@@ -65,6 +65,14 @@ int bsed_mel_noise(const float* mel_lin, const float* bin_sumsq, const float* un
  * -> (B, T_out, n_mels), i.e. the (B,1,T_out,n_mels) CRNN input. */
 int bsed_mel_db(const float* mel_lin, const float* clip_max, int B, int T, int T_out, int n_mels,
                 float top_db, float* out_db, void* stream);
+/* bsed_mel_db plus the two rolled views of the ISP shift-consistency step from one read of the linear mel:
+ * out_db as bsed_mel_db writes it; out_db_tshift[b] = torch.roll(out_db[b], shift_frames[b], time);
+ * out_db_fshift[b] = torch.roll(out_db[b], shift_bins[b], frequency)   (src/main_scmt_ada_weak.py:234-248).
+ * The rolls act on the padded / truncated (T_out, n_mels) tensor; shifts (device int32, B each) of any sign or size
+ * are taken modulo the axis length.  Three distinct (B, T_out, n_mels) outputs, bitwise bsed_mel_db + bsed_roll. */
+int bsed_mel_db_views(const float* mel_lin, const float* clip_max, int B, int T, int T_out, int n_mels,
+                      float top_db, const int* shift_frames, const int* shift_bins, float* out_db,
+                      float* out_db_tshift, float* out_db_fshift, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Implicit-GEMM contraction on the fp32 matrix cores (v_mfma_f32_32x32x2_f32).
