@@ -464,6 +464,39 @@ int bsed_decode_count(const float* mask, int B, int T, int C, int* counts, void*
 int bsed_decode_write(const float* mask, const int* offsets, int B, int T, int C, double scale, double max_len,
                       int* ev_clip, int* ev_class, int* ev_frames, double* ev_seconds, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Recording-level detection (csrc/detect.hip): one long waveform -> overlapping clip-sized windows -> the clip path ->
+ * window probabilities stitched onto the recording's frame grid -> events.  One output frame is frame_samples =
+ * hop * pooling_time_ratio samples (1020); window starts are given in OUTPUT FRAMES so that local frame j of a window
+ * that starts at frame s is frame s + j of the recording.
+ * ---------------------------------------------------------------------------------------------- */
+/* wave (n) + starts (W, int32 output frames) -> out (W, win): out[w] = wave[starts[w] * frame_samples : ... + win], bit
+ * for bit, in one launch.  win and frame_samples must be multiples of 4 and wave / out 16-byte aligned (rows move as
+ * 16-byte pieces; any other geometry is refused).  A window that does not lie inside the recording is zero-filled. */
+int bsed_gather_windows(const float* wave, long n, const int* starts, int W, int win, int frame_samples, float* out,
+                        void* stream);
+
+#define BSED_STITCH_UNIFORM 0
+#define BSED_STITCH_TRIANGULAR 1
+/* p (W, Tp, C) window probabilities + starts (W, int32 output frames) -> out (T_total, C): the weighted mean over the
+ * windows that cover a frame, summed in ascending window order (no atomics: bitwise repeatable); a frame covered by
+ * one window is copied.  weighting: BSED_STITCH_UNIFORM, or BSED_STITCH_TRIANGULAR wgt(j) = min(j + 1, Tp - j).
+ * Contract: starts[w] = w * hop_frames for w < W - 1, 1 <= hop_frames <= Tp; the last window may instead be aligned to
+ * the end of the recording, (W - 2) * hop_frames < starts[W - 1] <= (W - 1) * hop_frames; T_total = starts[W - 1] + Tp. */
+int bsed_stitch_windows(const float* p, const int* starts, int W, int Tp, int C, int hop_frames, int T_total,
+                        int weighting, float* out, void* stream);
+
+/* Contiguous-region decode of ONE (T, C) 0/1 mask with a long time axis, parallel over time: chunks of
+ * BSED_DECODE_LONG_FRAMES frames, nchunks = ceil(T / BSED_DECODE_LONG_FRAMES).
+ *   bsed_decode_long_count: counts (C * nchunks), counts[c * nchunks + k] = regions of class c that start in chunk k;
+ *   bsed_decode_long_write: offsets (C * nchunks) = exclusive prefix sum of counts (caller's), E = total; writes
+ *     ev_class (E), ev_frames (E,2) [onset, offset) and ev_seconds (E,2) = clip(frame * scale, 0, max_len) in float64,
+ *     ordered by class, then time -- what bsed_decode_write gives for one clip.  C <= 512. */
+#define BSED_DECODE_LONG_FRAMES 64
+int bsed_decode_long_count(const float* mask, int T, int C, int* counts, void* stream);
+int bsed_decode_long_write(const float* mask, const int* offsets, int T, int C, double scale, double max_len,
+                           int* ev_class, int* ev_frames, double* ev_seconds, void* stream);
+
 typedef struct BsedHeadBwdDesc {
   const float* x;            /* (B,T,K) encoder output */
   const float* w;            /* (2C,K) */
