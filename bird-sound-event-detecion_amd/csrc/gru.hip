@@ -26,6 +26,7 @@ __global__ __launch_bounds__(GRU_THREADS) void gru_fwd_kernel(
     float* __restrict__ out,         // (B,T,256): [dir*128 + k]
     float* __restrict__ gates,       // (B,T,2,4,128) r,z,n,gh_n  (nullable: inference)
     int B, int T) {
+  static_assert(R * GRU_H <= GRU_THREADS, "the combine phase needs one thread per (row, unit) pair");
   __shared__ __align__(16) float hs[R][GRU_H];
   __shared__ float gh[R][GRU_G];
   const int tid = threadIdx.x;
@@ -109,6 +110,7 @@ __global__ __launch_bounds__(GRU_THREADS) void gru_bwd_kernel(
     float* __restrict__ dxp,          // (B,T,768) input-side pre-activation gradients
     float* __restrict__ dgh,          // (B,T,768) hidden-side pre-activation gradients
     int B, int T) {
+  static_assert(R * GRU_H <= GRU_THREADS, "the combine phase needs one thread per (row, unit) pair");
   __shared__ __align__(16) float dg[R][GRU_G];
   __shared__ float part[R][3][GRU_H];
   const int tid = threadIdx.x;
@@ -413,14 +415,14 @@ __global__ __launch_bounds__(GM_THREADS) void gru_bwd_mfma_kernel(
 extern "C" int bsed_gru_fwd(const float* xp, const float* w_hh, const float* b_hh, float* out, float* gates, int B,
                             int T, int rows_per_wg, void* stream) {
   BSED_CHECK_ARG(xp && w_hh && b_hh && out, "bsed_gru_fwd: null tensor");
-  BSED_CHECK_ARG(B > 0 && T > 0 && rows_per_wg > 0, "bsed_gru_fwd: bad shape");
+  BSED_CHECK_ARG(B > 0 && T > 0, "bsed_gru_fwd: bad shape");
+  // the combine phase maps one thread to one (row, unit) pair: R * 128 <= GRU_THREADS, so R = 3 at most (not built)
+  BSED_CHECK_ARG(rows_per_wg == 1 || rows_per_wg == 2, "bsed_gru_fwd: rows_per_wg must be 1 or 2 (got %d)", rows_per_wg);
   hipStream_t s = (hipStream_t)stream;
   const int R = rows_per_wg;
   dim3 grid(ceil_div(B, R), 2);
   if (R == 1) hipLaunchKernelGGL(gru_fwd_kernel<1>, grid, dim3(GRU_THREADS), 0, s, xp, w_hh, b_hh, out, gates, B, T);
-  else if (R == 2) hipLaunchKernelGGL(gru_fwd_kernel<2>, grid, dim3(GRU_THREADS), 0, s, xp, w_hh, b_hh, out, gates, B, T);
-  else if (R == 4) hipLaunchKernelGGL(gru_fwd_kernel<4>, grid, dim3(GRU_THREADS), 0, s, xp, w_hh, b_hh, out, gates, B, T);
-  else { bsed_set_error("bsed_gru_fwd: rows_per_wg must be 1, 2 or 4"); return BSED_ERR_ARG; }
+  else hipLaunchKernelGGL(gru_fwd_kernel<2>, grid, dim3(GRU_THREADS), 0, s, xp, w_hh, b_hh, out, gates, B, T);
   BSED_LAUNCH_CHECK();
   return BSED_OK;
 }
@@ -428,13 +430,13 @@ extern "C" int bsed_gru_fwd(const float* xp, const float* w_hh, const float* b_h
 extern "C" int bsed_gru_bwd(const float* dout, const float* out, const float* gates, const float* w_hh, float* dxp,
                             float* dgh, int B, int T, int rows_per_wg, void* stream) {
   BSED_CHECK_ARG(dout && out && gates && w_hh && dxp && dgh, "bsed_gru_bwd: null tensor");
-  BSED_CHECK_ARG(B > 0 && T > 0 && rows_per_wg > 0, "bsed_gru_bwd: bad shape");
+  BSED_CHECK_ARG(B > 0 && T > 0, "bsed_gru_bwd: bad shape");
+  BSED_CHECK_ARG(rows_per_wg == 1 || rows_per_wg == 2, "bsed_gru_bwd: rows_per_wg must be 1 or 2 (got %d)", rows_per_wg);
   hipStream_t s = (hipStream_t)stream;
   const int R = rows_per_wg;
   dim3 grid(ceil_div(B, R), 2);
   if (R == 1) hipLaunchKernelGGL(gru_bwd_kernel<1>, grid, dim3(GRU_THREADS), 0, s, dout, out, gates, w_hh, dxp, dgh, B, T);
-  else if (R == 2) hipLaunchKernelGGL(gru_bwd_kernel<2>, grid, dim3(GRU_THREADS), 0, s, dout, out, gates, w_hh, dxp, dgh, B, T);
-  else { bsed_set_error("bsed_gru_bwd: rows_per_wg must be 1 or 2"); return BSED_ERR_ARG; }
+  else hipLaunchKernelGGL(gru_bwd_kernel<2>, grid, dim3(GRU_THREADS), 0, s, dout, out, gates, w_hh, dxp, dgh, B, T);
   BSED_LAUNCH_CHECK();
   return BSED_OK;
 }

@@ -411,6 +411,8 @@ int bsed_upsample_time_bwd(const float* dout, float* din, int B, int T_in, int T
  *   xp    (B,T,768)  x @ [W_ih; W_ih_reverse]^T + b_ih   (from bsed_igemm), [dir*384 + gate*128 + k]
  *   w_hh  (2,384,128), b_hh (2,384)                       gate order r,z,n
  *   out   (B,T,256)  [dir*128 + k];  gates (B,T,2,4,128) r,z,n,(W_hn h + b_hn) saved for backward
+ *   rows_per_wg  batch rows per workgroup of the fp32 register kernels: 1 or 2, at both entries; any other value
+ *                returns BSED_ERR_ARG before anything is launched.  gates may be NULL in the forward entries (inference).
  * ---------------------------------------------------------------------------------------------- */
 int bsed_gru_fwd(const float* xp, const float* w_hh, const float* b_hh, float* out, float* gates, int B, int T,
                  int rows_per_wg, void* stream);
