@@ -12,12 +12,32 @@
                             src/data/Transforms.py:304-322) for the WHOLE batch on the GPU (csrc/mel.hip kernels):
                             returns ((x, x_noisy), target), paths like the reference's DataLoader batches.
   write_features         preprocess() + the reference's file layout (np.save + to_csv(sep="\\t"))
+  read_wav               a PCM16 WAV file as it is on disk: int16 (n, channels) and its rate (the file-reading half of
+                            the reference's librosa.load, src/data/preprocess.py:182; features.load_audio does the rest)
 """
 import glob
 import os
 
 import numpy as np
 import torch
+
+
+def read_wav(path):
+    """PCM16 WAV file -> (int16 array (n, channels), sample rate), through the stdlib ``wave`` module: the samples as
+    the file holds them, no conversion, no mix.  Any other sample width is refused."""
+    import wave
+    from ._lib import BsedError
+    try:
+        f = wave.open(os.fspath(path), "rb")
+    except wave.Error as e:                                 # compressed / float / extensible formats
+        raise BsedError(f"read_wav: {path}: not a PCM WAV file that the wave module reads ({e})") from e
+    with f:
+        width, channels, sr, n = f.getsampwidth(), f.getnchannels(), f.getframerate(), f.getnframes()
+        if width != 2:
+            raise BsedError(f"read_wav: {path}: sample width is {width} byte(s) ({8 * width}-bit); only 16-bit PCM is read")
+        raw = f.readframes(n)
+    x = np.frombuffer(raw, dtype="<i2")
+    return x[:len(x) // channels * channels].reshape(-1, channels).astype(np.int16), sr    # a writable native-endian copy
 
 
 def read_annotation(path):

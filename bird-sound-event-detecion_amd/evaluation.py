@@ -336,10 +336,13 @@ def gather_windows(wave, starts, win, frame_samples):
 def detect_recording(model, wave, decoder, predictor=None, fpn=False, *, mel=None, hop_frames=None,
                      weighting="triangular", thresholds=(0.5,), median_window=1, learned_post=False,
                      classwise_median_window=None, pooling_time_ratio=4, batch_windows=64, filename=None,
-                     return_probabilities=False, stage_events=None):
+                     return_probabilities=False, stage_events=None, sr=None, resample_quality=None):
     """Events of ONE whole recording.  ``wave``: mono waveform (numpy array or GPU tensor) already at ``mel.cfg.sr`` (no
-    file reading, no resampling here); ``mel``: the ``MelFrontEnd`` the model was trained with (default: the reference
-    configuration); ``decoder``: ``ManyHotEncoder.decode_strong`` as for ``get_predictions``.  Returns a DataFrame with
+    file reading here; see ``features.load_audio``) -- or, with ``sr`` given, the recording as its file holds it: int16 or
+    float32, (n,) or (n, channels), at ``sr`` Hz, which ``features.Resampler(sr, mel.cfg.sr, **resample_quality)`` first
+    mixes to mono and resamples in one launch (a "resample" stage in ``stage_events``; mono float32 with
+    ``sr == mel.cfg.sr`` needs none and takes the ``sr=None`` route).  The resampling filter is this package's own, not
+    librosa's.  ``mel``: the ``MelFrontEnd`` the model was trained with (default: the reference configuration); ``decoder``: ``ManyHotEncoder.decode_strong`` as for ``get_predictions``.  Returns a DataFrame with
     the columns of ``get_predictions`` (event_label / onset / offset / filename; seconds from the start of the
     recording, clipped to its duration), or a list of them, one per threshold; with ``return_probabilities`` the tuple
     (that, stitched (T_total, C) GPU probabilities, per-window (W, Tp, C) GPU probabilities).
@@ -362,16 +365,35 @@ def detect_recording(model, wave, decoder, predictor=None, fpn=False, *, mel=Non
                         "ManyHotEncoder as decoder")
     if batch_windows < 1:
         raise BsedError(f"detect_recording: batch_windows must be at least 1, got {batch_windows}")
+    if sr is None and resample_quality is not None:
+        raise BsedError("detect_recording: resample_quality needs sr, the rate of the samples passed")
+    if sr is not None:
+        if isinstance(sr, bool) or not isinstance(sr, (int, np.integer)) or sr < 1:
+            raise BsedError(f"detect_recording: sr must be the recording's rate in Hz, a positive integer, got {sr!r}")
+        if not isinstance(resample_quality, (dict, type(None))) or set(resample_quality or ()) - {"rolloff", "attenuation_db"}:
+            raise BsedError("detect_recording: resample_quality is a dict with the keys rolloff and / or attenuation_db, "
+                            f"got {resample_quality!r}")
+        from .features import Resampler, resampler
+        raw_form = Resampler.form(wave)                 # dtype, shape, channels: BsedError before any GPU work
     mel = MelFrontEnd() if mel is None else mel
     cfg = mel.cfg
-    wave = torch.as_tensor(np.asarray(wave, dtype=np.float32) if not isinstance(wave, torch.Tensor) else wave)
-    if wave.dim() != 1 or wave.numel() == 0:
-        raise BsedError(f"detect_recording takes one mono waveform (n,), got shape {tuple(wave.shape)}")
-    n = wave.numel()
+    rs = None
+    if sr is not None:
+        rs = resampler(int(sr), cfg.sr, **(resample_quality or {}))
+        if rs.passes_through(wave):
+            rs = None
+    if rs is not None:
+        n = rs.n_out(raw_form[0])                       # the resampled length, for the window plan
+    else:
+        wave = torch.as_tensor(np.asarray(wave, dtype=np.float32) if not isinstance(wave, torch.Tensor) else wave)
+        if wave.dim() != 1 or wave.numel() == 0:
+            raise BsedError(f"detect_recording takes one mono waveform (n,), got shape {tuple(wave.shape)}")
+        n = wave.numel()
     starts, Tp, T_total = window_plan(n, cfg.sr, cfg.hop_size, pooling_time_ratio, cfg.max_len_seconds, hop_frames)
     if learned_post and classwise_median_window is None:
         classwise_median_window = classwise_median_windows(cfg.sr, cfg.hop_size, pooling_time_ratio)
-    wave = wave.float().cuda().contiguous()
+    if rs is None:
+        wave = wave.float().cuda().contiguous()
     win, frame = int(cfg.max_len_seconds * cfg.sr), cfg.hop_size * pooling_time_ratio
 
     def stage(name, fn):
@@ -395,6 +417,8 @@ def detect_recording(model, wave, decoder, predictor=None, fpn=False, *, mel=Non
         predictor.eval()
     try:
         with torch.no_grad():
+            if rs is not None:
+                wave = stage("resample", lambda: rs(wave))
             windows = stage("front_end", lambda: wave[None] if n < win else gather_windows(wave, starts, win, frame))
             probs = []
             for i in range(0, len(starts), batch_windows):

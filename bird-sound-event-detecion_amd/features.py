@@ -7,10 +7,17 @@
 The reference runs these per clip on the CPU (librosa, offline + DataLoader).  Here a whole batch of
 raw waveforms goes through three HIP kernels (csrc/mel.hip) and comes out as the (B,1,T,128) CRNN
 input without leaving HBM.
+
+  load_audio(path, sr)                   <- librosa.load(path, sr=cfg.sr) (src/data/preprocess.py:182): the file's PCM16
+  Resampler(sr_in, sr_out)(x)               frames are uploaded as they are and mixed to mono and resampled by ONE kernel
+  resample_filter(sr_in, sr_out)            (csrc/resample.hip).  The filter is this project's own Kaiser-windowed sinc,
+                                            fully specified in ``resample_filter``; it is NOT librosa's (soxr's)
+                                            resampler and no bit parity with it is claimed.
 """
 import ctypes
 import math
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -156,3 +163,134 @@ def preprocess(audio, compute_log=False, cfg=None):
     if compute_log:
         mel = fe.to_db(mel, cmax)[:, 0]
     return mel[0].cpu().numpy()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Resampling
+# ---------------------------------------------------------------------------------------------------------------------
+def resample_filter(sr_in, sr_out, rolloff=0.91, attenuation_db=100.0):
+    """The low-pass of the polyphase resampler sr_in -> sr_out, designed on the host in float64 ->
+    ``(taps, up, down, half_len)``: ``taps`` float64, odd length ``2 * half_len + 1``, symmetric.
+
+      g = gcd(sr_in, sr_out), up = sr_out / g, down = sr_in / g, fs_up = sr_in * up, low = min(sr_in, sr_out)
+      pass band to fp = rolloff * low / 2, stop band from fst = low / 2, cutoff fc = (fp + fst) / 2
+      Kaiser window: beta = 0.1102 (A - 8.7), N = ceil((A - 8) / (2.285 * 2 pi (fst - fp) / fs_up)), half_len = (N + 1) // 2
+      taps[k + half_len] = up * (2 fc / fs_up) * sinc(2 fc k / fs_up) * kaiser[k + half_len],   k = -half_len .. half_len
+
+    The resampler is ``y[m] = sum_j x[j] * taps[m * down - j * up + half_len]`` over the j with the tap index in range and
+    0 <= j < n_in (zero outside the signal), ``n_out = ceil(n_in * up / down)``; zero-phase: y[m] sits at input time
+    m * down / up.  At the defaults the stop band is at -100 dB and the pass-band ripple below 2e-4 dB."""
+    for name, v in (("sr_in", sr_in), ("sr_out", sr_out)):
+        if isinstance(v, bool) or int(v) != v or int(v) < 1:
+            raise L.BsedError(f"resample_filter: {name} must be a positive integer rate in Hz, got {v!r}")
+    sr_in, sr_out, rolloff, A = int(sr_in), int(sr_out), float(rolloff), float(attenuation_db)
+    if not 0.0 < rolloff < 1.0:
+        raise L.BsedError(f"resample_filter: rolloff must lie inside (0, 1), got {rolloff}")
+    if not 21.0 < A <= 160.0:
+        raise L.BsedError(f"resample_filter: attenuation_db must lie in (21, 160] (Kaiser's formulas; float64), got {A}")
+    g = math.gcd(sr_in, sr_out)
+    up, down = sr_out // g, sr_in // g
+    fs_up, low = float(sr_in) * up, float(min(sr_in, sr_out))
+    fp, fst = rolloff * low / 2.0, low / 2.0
+    fc = (fp + fst) / 2.0
+    beta = 0.1102 * (A - 8.7)
+    N = math.ceil((A - 8.0) / (2.285 * 2.0 * math.pi * (fst - fp) / fs_up))
+    half_len = (N + 1) // 2
+    k = np.arange(-half_len, half_len + 1, dtype=np.float64)
+    taps = up * (2.0 * fc / fs_up) * np.sinc(2.0 * fc * k / fs_up) * np.kaiser(2 * half_len + 1, beta)
+    return taps, up, down, half_len
+
+
+def resample_table(taps, up, down, half_len):
+    """``taps`` -> the (up, P) float32 table ``bsed_resample_poly`` reads, one row per output residue c = m % up:
+    ``table[c, i] = taps[(c * down + half_len) % up + i * up]``, 0 past the filter's end; P = (2 * half_len) // up + 1."""
+    taps = np.asarray(taps, dtype=np.float64)
+    P = (2 * half_len) // up + 1
+    idx = ((np.arange(up, dtype=np.int64) * down + half_len) % up)[:, None] + np.arange(P, dtype=np.int64)[None, :] * up
+    table = np.where(idx < len(taps), taps[np.minimum(idx, len(taps) - 1)], 0.0)
+    return np.ascontiguousarray(table, dtype=np.float32)
+
+
+class Resampler:
+    """sr_in -> sr_out for whole recordings on the GPU, with the mono mix and the int16 conversion inside the same
+    kernel.  The filter (``resample_filter``) is designed once, on the host; the device table is made on first use.
+    ``sr_in == sr_out`` is the convert / mix-only case (one tap of 1.0).
+
+    ``rs(x)``: x a numpy array or a GPU tensor, int16 or float32, shaped (n,) or (n, channels) as a WAV file interleaves
+    them -> (n_out,) float32 GPU tensor.  Mono float32 input with ``sr_in == sr_out`` is returned as it is."""
+
+    def __init__(self, sr_in, sr_out, rolloff=0.91, attenuation_db=100.0):
+        taps, self.up, self.down, self.half_len = resample_filter(sr_in, sr_out, rolloff, attenuation_db)
+        self.sr_in, self.sr_out = int(sr_in), int(sr_out)
+        if self.sr_in == self.sr_out:
+            taps, self.half_len = np.ones(1), 0
+        self.taps = taps
+        self.table = resample_table(taps, self.up, self.down, self.half_len)      # host copy (up, P) float32
+        self.taps_per_phase = self.table.shape[1]
+        self._dev = {}
+
+    def n_out(self, n_in):
+        return -(-int(n_in) * self.up // self.down)
+
+    @staticmethod
+    def form(x):
+        """host-side check of an input -> (n frames, channels); raises BsedError, touches no GPU"""
+        if not isinstance(x, (np.ndarray, torch.Tensor)):
+            raise L.BsedError(f"Resampler takes a numpy array or a GPU tensor, got {type(x).__name__}")
+        dt = str(x.dtype).replace("torch.", "")
+        if dt not in ("int16", "float32"):
+            raise L.BsedError(f"Resampler takes int16 or float32 samples, got {dt}")
+        if x.ndim not in (1, 2):
+            raise L.BsedError(f"Resampler takes samples shaped (n,) or (n, channels), got shape {tuple(x.shape)}")
+        n, channels = int(x.shape[0]), int(x.shape[1]) if x.ndim == 2 else 1
+        if n < 1 or not 1 <= channels <= 64:
+            raise L.BsedError(f"Resampler needs at least one frame of 1..64 channels, got shape {tuple(x.shape)}")
+        return n, channels
+
+    def passes_through(self, x):
+        """mono (n,) float32 at the target rate: nothing to compute"""
+        return self.sr_in == self.sr_out and x.ndim == 1 and str(x.dtype).replace("torch.", "") == "float32"
+
+    def __call__(self, x):
+        n, channels = self.form(x)
+        L._require_gpu()
+        if isinstance(x, np.ndarray):
+            x = torch.from_numpy(np.ascontiguousarray(x)).cuda()
+        elif not x.is_cuda:
+            raise L.BsedError("Resampler takes a numpy array or a GPU tensor, got a CPU tensor")
+        x = x.contiguous()
+        if self.passes_through(x):
+            return x
+        table = self._dev.get(x.device)
+        if table is None:
+            table = self._dev[x.device] = torch.from_numpy(self.table).to(x.device)
+        s16 = x.dtype == torch.int16
+        n_out = self.n_out(n)
+        out = torch.empty((n_out,), device=x.device, dtype=torch.float32)
+        ops._note(f"resample_poly_kernel<{int(s16)}>", f"{self.up}/{self.down} ch{channels}", 2.0 * n_out * self.taps_per_phase,
+                  float(n * channels * (2 if s16 else 4) + 4 * n_out + 4 * self.table.size))
+        L.call("bsed_resample_poly", L.ptr(x, x.dtype), L.CONSTANTS["BSED_PCM_S16" if s16 else "BSED_PCM_F32"], n, channels,
+               L.ptr(table), self.up, self.down, self.half_len, L.ptr(out), n_out, L.stream())
+        return out
+
+
+_resamplers = {}
+
+
+def resampler(sr_in, sr_out, rolloff=0.91, attenuation_db=100.0):
+    """the cached ``Resampler`` of a rate pair and quality (the filter design and the device table are made once)"""
+    key = (int(sr_in), int(sr_out), float(rolloff), float(attenuation_db))
+    rs = _resamplers.get(key)
+    if rs is None:
+        rs = _resamplers[key] = Resampler(*key)
+    return rs
+
+
+def load_audio(path, sr=32000, **quality):
+    """Counterpart of the reference's ``librosa.load(path, sr=cfg.sr)``: a PCM16 WAV file -> (mono float32 GPU waveform at
+    ``sr``, sr).  ``data.read_wav`` reads the frames, they are uploaded as int16 and one launch mixes, converts and
+    resamples them.  ``quality``: ``rolloff`` / ``attenuation_db`` of ``resample_filter``.  The samples are those of this
+    project's filter, not librosa's."""
+    from .data import read_wav
+    x, sr_in = read_wav(path)
+    return resampler(sr_in, sr, **quality)(x), int(sr)

@@ -499,6 +499,31 @@ int bsed_decode_long_count(const float* mask, int T, int C, int* counts, void* s
 int bsed_decode_long_write(const float* mask, const int* offsets, int T, int C, double scale, double max_len,
                            int* ev_class, int* ev_frames, double* ev_seconds, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Resampling (csrc/resample.hip).  stands in for librosa.load(path, sr=cfg.sr)'s mono mix + resampling
+ * (reference src/data/preprocess.py:182); the filter is this project's own (features.resample_filter), NOT
+ * librosa's / soxr's: no bit parity with them is claimed.
+ * ---------------------------------------------------------------------------------------------- */
+#define BSED_PCM_F32 0
+#define BSED_PCM_S16 1
+/* in: n_in interleaved frames of `channels` samples, float32 (BSED_PCM_F32) or int16 (BSED_PCM_S16) -> out (n_out) mono
+ * float32,   out[m] = sum_j x[j] * taps[m * down - j * up + half_len]   over 0 <= j < n_in and tap indices in
+ * 0 .. 2 * half_len (zero outside the signal; zero-phase: out[m] sits at input time m * down / up), with the mono mix
+ * made while the frames are loaded, in fp32:
+ *   BSED_PCM_S16:  x[j] = (float)(s[j][0] + s[j][1] + ... as int32) * (float)(1.0 / (32768.0 * channels))
+ *   BSED_PCM_F32:  x[j] = (((s[j][0] + s[j][1]) + s[j][2]) + ...)   * (float)(1.0 / channels)
+ * table: the taps by output residue.  With P = (2 * half_len) / up + 1 taps per phase, a(c) = (c * down + half_len) / up
+ * and r(c) = (c * down + half_len) % up (integer division), row c = m % up of the (up, P) table is
+ *   table[c * P + i] = taps[r(c) + i * up], 0 where r(c) + i * up > 2 * half_len,
+ * and out[k * up + c] = fmaf chain over i = 0 .. P - 1, in that order, of x[k * down + a(c) - i] * table[c * P + i]: one
+ * fp32 sum per output in a fixed order, no atomics, independent of the launch partition, bitwise repeatable.
+ * up = down = 1, half_len = 0, table = {1.0f} converts and mixes only.
+ * Refused before any launch: null pointers; n_in < 1; channels outside 1..64; an unknown format; up or down < 1 or
+ * not coprime; n_out != ceil(n_in * up / down); in and out overlapping; a filter whose 64 (or `up`, if fewer) table
+ * rows plus the samples of 1024 outputs do not fit the 160 KB of LDS (4 * (65 * P + 15 * down + (63 * down) / up + 1 + P) bytes for up > 32). */
+int bsed_resample_poly(const void* in, int format, long n_in, int channels, const float* table, int up, int down,
+                       int half_len, float* out, long n_out, void* stream);
+
 typedef struct BsedHeadBwdDesc {
   const float* x;            /* (B,T,K) encoder output */
   const float* w;            /* (2C,K) */
