@@ -9,13 +9,21 @@
 Everything per frame runs on the GPU for the whole batch: forward (HIP), threshold + median filter
 (``bsed_binarize_median``), contiguous-region decode and the seconds conversion (``bsed_decode_count`` /
 ``bsed_decode_write``).  Only the event list (a few rows per clip) travels to the host, where the DataFrames are
-assembled without a per-clip Python loop.  Metric values (sed_eval / psds_eval) stay external.
+assembled without a per-clip Python loop.  The collar-based event F1 that picks the best checkpoint is computed here too
+(``validate`` below); the intersection F1 and PSDS (psds_eval) and the segment-based metric stay external.
 
   detect_recording  <- no counterpart in the reference, which cuts recordings into 10 s clips offline
                        (src/data/preprocess.py:176-229) and only ever sees clips: one whole recording -> overlapping
                        clip-sized windows on the recording's frame grid (``window_plan``, ``bsed_gather_windows``) -> the clip
                        path above -> one (T_total, C) time line (``stitch_windows``) -> threshold / median / contiguous
                        regions decoded in parallel over time (``decode_long_gpu``) -> events in seconds of the recording.
+
+  validate          <- the reference's per-epoch validation (src/main_baseline.py:1010-1032: ``get_predictions`` ->
+                       ``compute_metrics`` -> sed_eval event-based F1, t_collar 0.2 s, 20 % of the length on the offset,
+                       macro average) and its threshold sweep: the event lists of ALL thresholds from one pair of launches
+                       (``sweep_events_gpu``), Ntp / Nsys / Nref per (threshold, class) counted on the GPU with sed_eval's
+                       optimal matching (``event_counts_gpu``), F1 from the integer counts on the host (``event_f1``).
+                       ``score_recording`` applies the same counts to a ``detect_recording`` result.
 """
 import math
 import os
@@ -448,3 +456,433 @@ def detect_recording(model, wave, decoder, predictor=None, fpn=False, *, mel=Non
                                 columns=["event_label", "onset", "offset", "filename"]))
     predictions = dfs[0] if len(dfs) == 1 else dfs
     return (predictions, stitched, win_probs) if return_probabilities else predictions
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Validation: threshold sweep, collar-based event counts, event F1
+# ---------------------------------------------------------------------------------------------------------------------
+MATCH_MAX_REF = L.CONSTANTS["BSED_MATCH_MAX_REF"]
+_EVENT_COLUMNS = ["event_label", "onset", "offset", "filename"]
+
+
+class EventLists:
+    """Estimated events of S thresholds x B clips x C classes, held on the GPU: ``offsets`` (S*B*C + 1) int32, the
+    exclusive prefix of the list lengths with the total last; ``seconds`` (max(E, 1), 2) float64 [onset, offset];
+    ``frames`` (max(E, 1), 2) int32 or None.  Grouped by threshold, clip, class and ordered by time inside a group --
+    the layout ``bsed_event_match`` reads.  ``sweep_events_gpu`` makes one per batch; ``from_host`` wraps any list."""
+
+    def __init__(self, offsets, seconds, S, B, C, total, frames=None, thresholds=None):
+        self.offsets, self.seconds, self.frame_pairs = offsets, seconds, frames
+        self.S, self.B, self.C, self.total = int(S), int(B), int(C), int(total)
+        self.thresholds = thresholds
+
+    @classmethod
+    def from_host(cls, counts, seconds, thresholds=None):
+        """counts (S,B,C) list lengths + seconds (E,2) in the grouped order -> the lists on the current GPU"""
+        counts = np.asarray(counts)
+        seconds = np.ascontiguousarray(np.asarray(seconds, np.float64).reshape(-1, 2))
+        if counts.ndim != 3 or counts.min(initial=0) < 0 or int(counts.sum()) != len(seconds):
+            raise BsedError(f"EventLists.from_host: counts must be (S,B,C) list lengths that add up to the {len(seconds)} "
+                            f"events given, got shape {counts.shape} with sum {int(counts.sum())}")
+        if counts.sum() > 2 ** 31 - 1:
+            raise BsedError("EventLists.from_host: more than 2^31 - 1 events")
+        off = np.concatenate([[0], np.cumsum(counts.ravel())]).astype(np.int32)
+        S, B, C = counts.shape
+        sec = torch.from_numpy(seconds if len(seconds) else np.zeros((1, 2))).cuda()
+        return cls(torch.from_numpy(off).cuda(), sec, S, B, C, len(seconds), thresholds=thresholds)
+
+    def host(self):
+        """(counts (S,B,C) int64, frames (E,2) int32 or None, seconds (E,2) float64) numpy arrays"""
+        off = self.offsets.cpu().numpy().astype(np.int64)
+        fr = None if self.frame_pairs is None else self.frame_pairs[:self.total].cpu().numpy()
+        return np.diff(off).reshape(self.S, self.B, self.C), fr, self.seconds[:self.total].cpu().numpy()
+
+    def frames(self, labels, names):
+        """One DataFrame per threshold with the columns, dtypes and row order (clip, class, time) that ``get_predictions``
+        gives for that threshold on the same batch: event_label / onset / offset / filename."""
+        import pandas as pd
+        if len(labels) < self.C or len(names) != self.B:
+            raise BsedError(f"EventLists.frames: need at least {self.C} labels and {self.B} names, got {len(labels)} and {len(names)}")
+        counts, _, sec = self.host()
+        group = np.repeat(np.arange(counts.size), counts.ravel())
+        per_s = np.concatenate([[0], np.cumsum(counts.reshape(self.S, -1).sum(1))])
+        lab, nam = np.asarray(labels, dtype=object), np.asarray(names, dtype=object)
+        out = []
+        for s in range(self.S):
+            g = group[per_s[s]:per_s[s + 1]]
+            rows = sec[per_s[s]:per_s[s + 1]]
+            out.append(pd.DataFrame({"event_label": lab[g % self.C], "onset": rows[:, 0], "offset": rows[:, 1],
+                                     "filename": nam[(g // self.C) % self.B]}))
+        return out
+
+
+def _sweep_thresholds(thresholds):
+    if isinstance(thresholds, torch.Tensor):
+        thr = thresholds.detach().to(device="cuda", dtype=torch.float32).reshape(-1).contiguous()
+    else:
+        thr = torch.tensor([float(t) for t in np.atleast_1d(np.asarray(thresholds, dtype=np.float64))],
+                           dtype=torch.float32).cuda()
+    if thr.numel() == 0:
+        raise BsedError("sweep_events_gpu: at least one threshold is needed")
+    return thr
+
+
+def _sweep_windows(median_window, classwise_median_window, C):
+    """the (C) int32 window list of the sweep kernel: one window for every class, or ``learned_post``'s list, where
+    classes beyond the list get 0 = no events (what ``binarize_median_classwise_gpu`` does with them)"""
+    if classwise_median_window is None:
+        if isinstance(median_window, bool) or int(median_window) != median_window or median_window < 1:
+            raise BsedError(f"sweep_events_gpu: median_window must be an integer of at least 1, got {median_window!r}")
+        w = [int(median_window)] * C
+    else:
+        w = [int(v) for v in list(classwise_median_window)[:C]]
+        if any(v < 1 for v in w):
+            raise BsedError(f"sweep_events_gpu: class-wise median windows must be at least 1, got {w}")
+        w += [0] * (C - len(w))
+    return torch.tensor(w, dtype=torch.int32).cuda() if C else torch.zeros(0, dtype=torch.int32).cuda()
+
+
+def _sweep(x, thr, win, scale, max_len_seconds):
+    B, T, C = x.shape
+    S = thr.numel()
+    n = S * B * C
+    offsets = torch.zeros(n + 1, device=x.device, dtype=torch.int32)
+    if n == 0 or T == 0:                                # an empty batch decodes to empty lists
+        return EventLists(offsets, torch.zeros((1, 2), device=x.device, dtype=torch.float64), S, B, C, 0,
+                          torch.zeros((1, 2), device=x.device, dtype=torch.int32), thr)
+    counts = torch.empty(n, device=x.device, dtype=torch.int32)
+    L.call("bsed_sweep_count", L.ptr(x), L.ptr(thr), L.ptr(win, torch.int32), S, B, T, C, L.ptr(counts, torch.int32), L.stream())
+    torch.cumsum(counts, 0, dtype=torch.int32, out=offsets[1:])
+    E = int(offsets[-1])                                # the one host sync of the sweep: the total list length
+    ev_frames = torch.empty((max(E, 1), 2), device=x.device, dtype=torch.int32)
+    ev_seconds = torch.empty((max(E, 1), 2), device=x.device, dtype=torch.float64)
+    if E:
+        L.call("bsed_sweep_write", L.ptr(x), L.ptr(thr), L.ptr(win, torch.int32), L.ptr(offsets, torch.int32), S, B, T, C,
+               scale, max_len_seconds, L.ptr(ev_frames, torch.int32), L.ptr(ev_seconds, torch.float64), L.stream())
+    return EventLists(offsets, ev_seconds, S, B, C, E, ev_frames, thr)
+
+
+def sweep_events_gpu(pred_strong, thresholds, median_window=1, classwise_median_window=None, scale=4 / (32000 / 255),
+                     max_len_seconds=10.0):
+    """(B,T',C) GPU probabilities -> ``EventLists`` with the events of EVERY threshold: what ``binarize_median_gpu``
+    (or ``binarize_median_classwise_gpu`` with ``classwise_median_window``) followed by ``decode_regions_gpu`` gives per
+    threshold, bit for bit, from two HIP launches and one host sync (the total list length) whatever the number of
+    thresholds.  ``scale``: seconds per output frame, ``pooling_time_ratio / (sr / hop_size)``."""
+    x = pred_strong.contiguous()
+    if x.dim() != 3:
+        raise BsedError(f"sweep_events_gpu takes (B,T,C) probabilities, got shape {tuple(x.shape)}")
+    return _sweep(x, _sweep_thresholds(thresholds), _sweep_windows(median_window, classwise_median_window, x.shape[2]),
+                  float(scale), float(max_len_seconds))
+
+
+def _read_annotations(names, folders, require_annotations=False):
+    """the ``annotation/<name>.txt`` files of ``get_predictions`` for these clips (first occurrence of a name), each with
+    a ``filename`` column -> list of non-empty DataFrames"""
+    import pandas as pd
+    seen, out = {}, []
+    for name, folder in zip(names, folders):
+        seen.setdefault(name, folder)
+    for name, folder in seen.items():
+        path = os.path.join(folder, name + ".txt")
+        if not os.path.exists(path):
+            if require_annotations:
+                raise FileNotFoundError(f"annotation file {path} is missing (the reference reads annotation/<name>.txt next to "
+                                        "wav/<name>.npy)")
+            continue
+        df = pd.read_csv(path, sep="\t")
+        df["filename"] = name
+        if len(df):
+            out.append(df)
+    return out
+
+
+class EventReference:
+    """Reference events of B clips x C classes, grouped by clip and class and sorted by onset: ``offsets`` (B*C + 1) int32
+    exclusive prefix, ``seconds`` (R,2) float64, ``counts`` (B,C), all numpy; ``device()`` uploads them once.
+    ``evaluated`` (B) bool: clips that have a row in the ground truth.  As in the reference's
+    ``event_based_evaluation_df`` (src/evaluation_measures.py:61-75), which walks the file names of the ground truth only,
+    estimated events of the other clips are not scored."""
+
+    def __init__(self, counts, seconds, names, labels, evaluated=None):
+        self.counts = np.asarray(counts, np.int64)
+        self.B, self.C = self.counts.shape
+        self.seconds = np.ascontiguousarray(np.asarray(seconds, np.float64).reshape(-1, 2))
+        self.offsets = np.concatenate([[0], np.cumsum(self.counts.ravel())]).astype(np.int32)
+        self.names, self.labels = list(names), list(labels)
+        self.evaluated = np.ones(self.B, bool) if evaluated is None else np.asarray(evaluated, bool)
+        self._dev = None
+
+    @classmethod
+    def from_frame(cls, groundtruth_df, labels, names, ignore_unknown=False):
+        """``groundtruth_df``: onset / offset / event_label / filename rows (``get_predictions``' second return value, or
+        None); ``names``: the clips of the batch in order; rows of other files are ignored, so the ground truth of a
+        whole set can be passed batch by batch.  Rows with a NaN onset or offset (how DESED-style files mark a clip
+        without events) are dropped but keep their clip evaluated.  A label outside ``labels`` raises ``BsedError``
+        unless ``ignore_unknown`` (then the row is dropped)."""
+        names, labels = list(names), list(labels)
+        B, C = len(names), len(labels)
+        index = {n: i for i, n in enumerate(names)}
+        if len(index) != B:
+            raise BsedError("EventReference: a clip name appears twice in the batch; scoring needs one event list per file")
+        evaluated = np.zeros(B, bool)
+        if groundtruth_df is None or len(groundtruth_df) == 0:
+            return cls(np.zeros((B, C), np.int64), np.zeros((0, 2)), names, labels, evaluated)
+        clip = np.asarray([index.get(f, -1) for f in groundtruth_df["filename"]], np.int64)
+        evaluated[clip[clip >= 0]] = True
+        on = np.asarray(groundtruth_df["onset"], np.float64)
+        off = np.asarray(groundtruth_df["offset"], np.float64)
+        keep = (clip >= 0) & ~np.isnan(on) & ~np.isnan(off)
+        lab_index = {l: i for i, l in enumerate(labels)}
+        cls_ = np.full(len(clip), -1, np.int64)
+        for i in np.nonzero(keep)[0]:
+            lab = groundtruth_df["event_label"].iloc[i]
+            k = lab_index.get(lab, -1)
+            if k < 0 and not ignore_unknown:
+                raise BsedError(f"EventReference: event label {lab!r} of clip {names[clip[i]]!r} is not in the label list")
+            cls_[i] = k
+        keep &= cls_ >= 0
+        clip, cls_, on, off = clip[keep], cls_[keep], on[keep], off[keep]
+        order = np.lexsort((off, on, cls_, clip))
+        counts = np.bincount(clip * C + cls_, minlength=B * C).reshape(B, C)
+        return cls(counts, np.stack([on[order], off[order]], 1), names, labels, evaluated)
+
+    @classmethod
+    def from_annotation_dirs(cls, names, folders, labels, ignore_unknown=False, require_annotations=False):
+        """the reference of a batch from ``<folder>/<name>.txt`` (tab-separated onset / offset / event_label), the files
+        ``get_predictions`` reads; a clip whose file is missing or has no row is not evaluated"""
+        import pandas as pd
+        dfs = _read_annotations(names, folders, require_annotations)
+        return cls.from_frame(pd.concat(dfs, ignore_index=True) if dfs else None, labels, names, ignore_unknown)
+
+    def check_cap(self, cap=MATCH_MAX_REF):
+        """the matcher holds one reference event per lane of a wave: at most ``cap`` per (clip, class)"""
+        if self.counts.size and self.counts.max() > cap:
+            b, c = np.unravel_index(int(np.argmax(self.counts)), self.counts.shape)
+            raise BsedError(f"event matching takes at most {cap} reference events per (clip, class): clip {self.names[b]!r} "
+                            f"has {int(self.counts[b, c])} of class {self.labels[c]!r}")
+
+    def device(self):
+        if self._dev is None:
+            sec = self.seconds if len(self.seconds) else np.zeros((1, 2))
+            self._dev = (torch.from_numpy(self.offsets).cuda(), torch.from_numpy(sec).cuda())
+        return self._dev
+
+
+def event_counts_gpu(events, reference, t_collar=0.2, percentage_of_length=0.2, out=None):
+    """``EventLists`` x ``EventReference`` of the same batch -> (S,C,3) int64 GPU tensor of (Ntp, Nsys, Nref) summed over the
+    clips, ADDED into ``out`` when given (the accumulator of a validation pass).  sed_eval's event-based counts with its
+    optimal matching: a reference and an estimated event of one clip and class hit when the onsets lie within ``t_collar``
+    and the offsets within ``max(t_collar, percentage_of_length * reference length)``; Ntp is the size of a maximum
+    matching of the hit graph.  One HIP launch, no host sync.  At most ``MATCH_MAX_REF`` = 64 reference events per
+    (clip, class): checked here, before the launch."""
+    if (events.B, events.C) != (reference.B, reference.C):
+        raise BsedError(f"event_counts_gpu: the events cover {events.B} clips x {events.C} classes, the reference "
+                        f"{reference.B} x {reference.C}")
+    reference.check_cap()
+    S, B, C = events.S, events.B, events.C
+    if out is None:
+        out = torch.zeros((S, C, 3), device=events.offsets.device, dtype=torch.int64)
+    elif tuple(out.shape) != (S, C, 3):
+        raise BsedError(f"event_counts_gpu: out must be ({S}, {C}, 3), got {tuple(out.shape)}")
+    if S * B * C == 0:
+        return out
+    ref_off, ref_sec = reference.device()
+    L.call("bsed_event_match", L.ptr(events.offsets, torch.int32), L.ptr(events.seconds, torch.float64),
+           L.ptr(ref_off, torch.int32), L.ptr(ref_sec, torch.float64), S, B, C, float(t_collar), float(percentage_of_length),
+           L.ptr(out, torch.int64), L.stream())
+    if not reference.evaluated.all():                   # clips outside the ground truth: their events are not scored
+        skip = torch.from_numpy(np.nonzero(~reference.evaluated)[0]).to(events.offsets.device)
+        n = (events.offsets[1:] - events.offsets[:-1]).reshape(S, B, C)
+        out[:, :, 1] -= n[:, skip, :].sum(1)
+    return out
+
+
+def event_f1(counts):
+    """(..., C, 3) integer counts (Ntp, Nsys, Nref) -> dict of float64 numpy arrays: ``class_f1`` (..., C), ``macro`` and
+    ``micro`` (...).  Per class F = 2 Ntp / (Nsys + Nref), which equals 2PR / (P + R) with P = Ntp / Nsys, R = Ntp / Nref
+    wherever both are defined, and is 0 where only one is; F is NaN where Nsys + Nref == 0 (the class neither occurs nor
+    is predicted).  ``macro`` is the mean over the classes whose F is not NaN, summed in class order (NaN if there is none); ``micro`` is F of
+    the sums over classes, which equals sed_eval's overall matching because a hit requires equal labels.
+    How sed_eval itself averages classes with Nsys = 0 or Nref = 0 could not be checked against the library, which is
+    not installed where this project is developed; the integer counts are the primary result, so a caller can apply
+    another rule."""
+    c = counts.detach().cpu().numpy() if isinstance(counts, torch.Tensor) else np.asarray(counts)
+    if c.ndim < 2 or c.shape[-1] != 3:
+        raise BsedError(f"event_f1 takes (..., C, 3) counts, got shape {c.shape}")
+    c = c.astype(np.float64)
+
+    def f(ntp, den):
+        return np.divide(2.0 * ntp, den, out=np.full(den.shape, np.nan), where=den > 0)
+
+    class_f1 = f(c[..., 0], c[..., 1] + c[..., 2])
+    valid = ~np.isnan(class_f1)
+    n_valid = valid.sum(-1)
+    total = np.zeros(n_valid.shape)
+    for k in range(class_f1.shape[-1]):                 # summed in class order, so that the value is defined to the bit
+        total = total + np.where(valid[..., k], class_f1[..., k], 0.0)
+    macro = np.divide(total, n_valid, out=np.full(n_valid.shape, np.nan), where=n_valid > 0)
+    tot = c.sum(-2)
+    return {"class_f1": class_f1, "macro": macro, "micro": f(tot[..., 0], tot[..., 1] + tot[..., 2])}
+
+
+class ValidationResult:
+    """``validate``'s return value: ``thresholds`` (list), ``counts`` (S,C,3) int64 numpy (Ntp, Nsys, Nref), ``class_f1``
+    (S,C), ``macro_f1`` / ``micro_f1`` (S), ``best_index`` / ``best_threshold`` (highest macro F, ties to the lowest
+    threshold; NaN counts as lowest), ``labels``, and -- on request -- ``predictions`` (one DataFrame per threshold) and
+    ``groundtruth_df``."""
+
+    def __init__(self, thresholds, counts, labels, predictions=None, groundtruth_df=None):
+        self.thresholds, self.counts, self.labels = list(thresholds), counts, list(labels)
+        f = event_f1(counts)
+        self.class_f1, self.macro_f1, self.micro_f1 = f["class_f1"], f["macro"], f["micro"]
+        key = np.where(np.isnan(self.macro_f1), -np.inf, self.macro_f1)
+        best = np.nonzero(key == key.max())[0]
+        self.best_index = int(min(best, key=lambda i: (self.thresholds[i], i)))
+        self.best_threshold = self.thresholds[self.best_index]
+        self.best_macro_f1 = float(self.macro_f1[self.best_index])
+        self.predictions, self.groundtruth_df = predictions, groundtruth_df
+
+
+def validate(model, dataloader, decoder, predictor=None, fpn=False, thresholds=(0.5,), median_window=1, learned_post=False,
+             t_collar=0.2, percentage_of_length=0.2, pooling_time_ratio=1, sr=32000, hop_size=255, max_len_seconds=10.0,
+             classwise_median_window=None, return_predictions=False, require_annotations=False, ignore_unknown=False):
+    """One validation pass, scored on the GPU: the eval-mode forward of ``get_predictions`` (same ``dataloader``, ``decoder``,
+    ``predictor`` / ``fpn`` forms and the same ``annotation/<name>.txt`` files), every batch swept over ALL ``thresholds``
+    (``sweep_events_gpu``: one host sync per batch) and matched against its reference (``event_counts_gpu``), the counts
+    accumulated on the device and read once at the end.  Returns a ``ValidationResult``: the counts, per-class / macro /
+    micro event F1 per threshold and the best threshold by macro F1 -- the number the reference keeps ``baseline_best``
+    by.  The prediction frames (as ``get_predictions`` returns them per threshold) and the ground-truth frame are built
+    only with ``return_predictions``.  A clip name may occur once per pass.  Training flags are restored on exit."""
+    import pandas as pd
+    if predictor is None and not fpn:
+        raise NotImplementedError("validate(predictor=None, fpn=False): pass predictor=... or a self-contained model with "
+                                  "fpn=True (see get_predictions)")
+    labels = _decoder_labels(decoder)
+    if labels is None:
+        raise BsedError("validate decodes and scores on the GPU and needs the label list: pass the bound decode_strong of a "
+                        "ManyHotEncoder as decoder")
+    thresholds = [float(t) for t in thresholds]
+    if learned_post and classwise_median_window is None:
+        classwise_median_window = classwise_median_windows(sr, hop_size, pooling_time_ratio)
+    scale = pooling_time_ratio / (sr / hop_size)
+    thr, win, acc = _sweep_thresholds(thresholds), None, None
+    frames, gts, seen = [[] for _ in thresholds], [], set()
+    was_training = (model.training, predictor.training if predictor is not None else False)
+    model.eval()
+    if predictor is not None:
+        predictor.eval()
+    try:
+        for ((input_data, _ema), _target), paths in dataloader:
+            names = [os.path.splitext(os.path.basename(p))[0] for p in paths]
+            folders = [os.path.join(os.path.dirname(os.path.dirname(p)), "annotation") for p in paths]
+            if seen & set(names):
+                raise BsedError(f"validate: clip(s) {sorted(seen & set(names))[:3]} occur in more than one batch")
+            seen |= set(names)
+            with torch.no_grad():
+                x = torch.as_tensor(input_data).float().cuda()
+                if predictor is not None:
+                    pred_strong, _ = predictor(model(x)[0], inference=fpn)
+                else:
+                    pred_strong = model(x, inference=True)[0]
+            pred_strong = pred_strong.contiguous()
+            C = pred_strong.shape[2]
+            if C > len(labels):
+                raise BsedError(f"validate: the model returned {C} classes, the decoder has {len(labels)} labels")
+            if win is None:
+                win = _sweep_windows(median_window, classwise_median_window if learned_post else None, C)
+                acc = torch.zeros((len(thresholds), C, 3), device=pred_strong.device, dtype=torch.int64)
+            events = _sweep(pred_strong, thr, win, scale, float(max_len_seconds))
+            dfs = _read_annotations(names, folders, require_annotations)
+            reference = EventReference.from_frame(pd.concat(dfs, ignore_index=True) if dfs else None, labels[:C], names,
+                                                  ignore_unknown)
+            event_counts_gpu(events, reference, t_collar, percentage_of_length, out=acc)
+            if return_predictions:
+                gts += dfs
+                for s, df in enumerate(events.frames(labels, names)):
+                    frames[s].append(df)
+    finally:
+        model.train(was_training[0])
+        if predictor is not None:
+            predictor.train(was_training[1])
+    if acc is None:
+        raise BsedError("validate: the dataloader yielded no batch")
+    predictions = groundtruth_df = None
+    if return_predictions:
+        predictions = [pd.concat(f, ignore_index=True)[_EVENT_COLUMNS] for f in frames]
+        groundtruth_df = pd.concat(gts, ignore_index=True) if gts else None
+    return ValidationResult(thresholds, acc.cpu().numpy(), labels[:acc.shape[1]], predictions, groundtruth_df)
+
+
+_SEGMENT_SLACK = 1e-6       # seconds; far above the rounding of second-valued float64 differences, far below any collar
+
+
+def recording_problem(events_df, groundtruth_df, labels, t_collar=0.2, ignore_unknown=False):
+    """Host preparation of ``score_recording`` -> ``(counts (S,B',C), est seconds, EventReference)``.  One recording has one
+    long list per class, so the time line of every class is cut into independent pieces that play the part of clips: a
+    hit needs the onsets within ``t_collar``, so where two neighbouring reference onsets of a class lie more than
+    ``2 * t_collar`` (+ 1 us) apart no estimated event can hit on both sides, and the maximum matching is the sum over
+    the pieces.  An estimated event goes to the piece whose onsets it can reach (to the nearest earlier one if none)."""
+    labels = list(labels)
+    C = len(labels)
+    lab_index = {l: i for i, l in enumerate(labels)}
+    dfs = list(events_df) if isinstance(events_df, (list, tuple)) else [events_df]
+
+    def columns(df, what):
+        if df is None or len(df) == 0:
+            return np.zeros(0, np.int64), np.zeros(0), np.zeros(0)
+        on, off = np.asarray(df["onset"], np.float64), np.asarray(df["offset"], np.float64)
+        keep = ~np.isnan(on) & ~np.isnan(off)
+        k = np.asarray([lab_index.get(l, -1) if kp else -1 for l, kp in zip(df["event_label"], keep)], np.int64)
+        if (k[keep] < 0).any() and not (ignore_unknown and what == "reference"):
+            bad = [l for l, kk, kp in zip(df["event_label"], k, keep) if kp and kk < 0][0]
+            raise BsedError(f"score_recording: {what} event label {bad!r} is not in the label list")
+        keep &= k >= 0
+        return k[keep], on[keep], off[keep]
+
+    rk, ron, roff = columns(groundtruth_df, "reference")
+    order = np.lexsort((roff, ron, rk))
+    rk, ron, roff = rk[order], ron[order], roff[order]
+    gap = 2.0 * float(t_collar) + _SEGMENT_SLACK
+    piece = np.zeros(len(rk), np.int64)                 # piece index of every reference event inside its class
+    starts = []                                         # per class: first onset of every piece
+    for c in range(C):
+        idx = np.nonzero(rk == c)[0]
+        new = np.concatenate([[True], np.diff(ron[idx]) > gap]) if len(idx) else np.zeros(0, bool)
+        piece[idx] = np.cumsum(new) - 1
+        starts.append(ron[idx][new])
+    Bp = max([1] + [len(s) for s in starts])
+    ref_counts = np.bincount(piece * C + rk, minlength=Bp * C).reshape(Bp, C)
+    rorder = np.lexsort((roff, ron, rk, piece))
+    names = [f"piece {i}" for i in range(Bp)]
+    reference = EventReference(ref_counts, np.stack([ron[rorder], roff[rorder]], 1), names, labels)
+    if ref_counts.max(initial=0) > MATCH_MAX_REF:
+        b, c = np.unravel_index(int(np.argmax(ref_counts)), ref_counts.shape)
+        raise BsedError(f"score_recording: {int(ref_counts[b, c])} reference events of class {labels[c]!r} from "
+                        f"{starts[c][b]:.3f} s on follow each other within {gap:.3f} s; the matcher takes at most "
+                        f"{MATCH_MAX_REF} per such run")
+    counts = np.zeros((len(dfs), Bp, C), np.int64)
+    secs = []
+    for s, df in enumerate(dfs):
+        ek, eon, eoff = columns(df, "estimated")
+        ep = np.zeros(len(ek), np.int64)
+        for c in range(C):
+            idx = np.nonzero(ek == c)[0]
+            if len(idx) and len(starts[c]):
+                ep[idx] = np.maximum(np.searchsorted(starts[c] - float(t_collar) - _SEGMENT_SLACK / 2, eon[idx], "right") - 1, 0)
+        o = np.lexsort((eoff, eon, ek, ep))
+        counts[s] = np.bincount(ep * C + ek, minlength=Bp * C).reshape(Bp, C)
+        secs.append(np.stack([eon[o], eoff[o]], 1))
+    return counts, np.concatenate(secs) if secs else np.zeros((0, 2)), reference
+
+
+def score_recording(events_df, groundtruth_df, labels, t_collar=0.2, percentage_of_length=0.2, ignore_unknown=False):
+    """The event counts of ``validate`` for ONE recording: ``events_df`` is what ``detect_recording`` returns (a DataFrame,
+    or a list of them, one per threshold), ``groundtruth_df`` has onset / offset / event_label rows in seconds of the
+    recording (rows with NaN are dropped).  Returns the (S,C,3) int64 numpy counts (Ntp, Nsys, Nref); ``event_f1`` turns
+    them into F1.  The match kernel works on lists of at most 64 reference events, so each class's time line is first
+    cut where two neighbouring reference onsets lie more than ``2 * t_collar`` apart (``recording_problem``); the cap that
+    remains: at most 64 reference events of one class in a run whose neighbouring onsets all lie within ``2 * t_collar``.
+    The estimated lists have no cap."""
+    counts, seconds, reference = recording_problem(events_df, groundtruth_df, labels, t_collar, ignore_unknown)
+    events = EventLists.from_host(counts, seconds)
+    return event_counts_gpu(events, reference, t_collar, percentage_of_length).cpu().numpy()

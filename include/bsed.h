@@ -500,6 +500,41 @@ int bsed_decode_long_write(const float* mask, const int* offsets, int T, int C, 
                            int* ev_class, int* ev_frames, double* ev_seconds, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Validation (csrc/metrics.hip, ABI 6): the event lists of S thresholds from one launch, and the collar-based event
+ * counts behind the reference's model-selection F1 (compute_metrics -> sed_eval EventBasedMetrics, t_collar 0.2 s,
+ * percentage_of_length 0.2; src/main_baseline.py:1010-1032).
+ * ---------------------------------------------------------------------------------------------- */
+/* Threshold sweep.  strong (B,T,C); thresholds (S) float32 on the DEVICE; windows (C) int32 on the device, the median
+ * window of each class, 0 (or less) = the class yields no events (learned_post's classes beyond its list).
+ *   bsed_sweep_count: counts (S,B,C) = number of events per (threshold, clip, class);
+ *   bsed_sweep_write: offsets (S*B*C, or S*B*C + 1 with the total last: only the first S*B*C are read) = exclusive prefix
+ *     sum of counts (caller's), E = total; writes ev_frames (E,2) int32 [onset, offset) and ev_seconds (E,2) float64 =
+ *     clip(frame * scale, 0, max_len), ordered by threshold, clip, class, time.
+ * The events of threshold s are bit for bit those of bsed_binarize_median(thresholds[s], windows[c]) ->
+ * bsed_decode_count / bsed_decode_write, for every T and every window (win > T and win > 2T included).  Each clip's
+ * tile is read from HBM once per launch and staged in LDS; a tile above 160 KB (T * C > 40960) is walked in global
+ * memory instead, with the same results.  Refused before any launch: null pointers, a non-positive size, and geometry
+ * whose worst-case event total S * B * C * ceil(T / 2) exceeds 2^31 - 1. */
+int bsed_sweep_count(const float* strong, const float* thresholds, const int* windows, int S, int B, int T, int C,
+                     int* counts, void* stream);
+int bsed_sweep_write(const float* strong, const float* thresholds, const int* windows, const int* offsets, int S, int B,
+                     int T, int C, double scale, double max_len, int* ev_frames, double* ev_seconds, void* stream);
+
+/* Event matching.  est_offsets (S*B*C + 1) int32: exclusive prefix of the estimated lists, grouped by (threshold, clip,
+ * class), the total last; est_seconds (E,2) float64 [onset, offset].  ref_offsets (B*C + 1) and ref_seconds (R,2): the
+ * reference events grouped by (clip, class).  The lists need not come from bsed_sweep_write and may overlap.  Hit rule, in
+ * float64:  fabs(ref_on - est_on) <= t_collar  and
+ *           fabs(ref_off - est_off) <= fmax(t_collar, percentage_of_length * (ref_off - ref_on)).
+ * acc (S,C,3) int64 += (Ntp, Nsys, Nref) summed over the clips: Ntp the size of a MAXIMUM bipartite matching of the hit
+ * graph of each (threshold, clip, class), Nsys / Nref the list lengths.  Integer atomics: the accumulator persists
+ * across calls (zero it first) and repeated runs give the same bits.
+ * Contract (the CALLER's check, the offsets live on the device): at most BSED_MATCH_MAX_REF reference events per
+ * (clip, class); events beyond that are counted in Nref but never matched.  B <= 524280 per call. */
+#define BSED_MATCH_MAX_REF 64
+int bsed_event_match(const int* est_offsets, const double* est_seconds, const int* ref_offsets, const double* ref_seconds,
+                     int S, int B, int C, double t_collar, double percentage_of_length, long long* acc, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Resampling (csrc/resample.hip).  stands in for librosa.load(path, sr=cfg.sr)'s mono mix + resampling
  * (reference src/data/preprocess.py:182); the filter is this project's own (features.resample_filter), NOT
  * librosa's / soxr's: no bit parity with them is claimed.
