@@ -535,6 +535,32 @@ int bsed_event_match(const int* est_offsets, const double* est_seconds, const in
                      int S, int B, int C, double t_collar, double percentage_of_length, long long* acc, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Clip-level tagging (csrc/tagging.hip, ABI 7): the counts behind the reference's per-class weak F1
+ * (get_f_measure_by_class, src/evaluation_measures.py:346-427, intermediate_at_measures :430-446) for a whole threshold
+ * sweep, and the pseudo weak labels of a batch (src/audio_tagging_inference.py:289-316).
+ * ---------------------------------------------------------------------------------------------- */
+/* scores (B,C) with T_scores = 0, or (B,T_scores,C), reduced by its maximum over time (:390-392); targets (B,C) with
+ * T_targets = 0, used as given, or (B,T_targets,C), reduced by its maximum over time and binarised with `> 0.5`
+ * (:394-398).  Both maxima propagate NaN as numpy's do.  thresholds: (S) float32 on the DEVICE, or (S,C) with
+ * per_class = 1.  est = score > threshold (strict; a NaN score or threshold gives est = 0).
+ * counts (S,C,4) int64 += (tp, fp, fn, tn) over the B clips, as intermediate_at_measures writes them, evaluated in
+ * float64 on the target value:  est + ref == 2,  est - ref == 1,  ref - est == 1,  est + ref == 0  -- a target of -1
+ * (encode_weak("empty")) is an fp where est = 0 and a tn where est = 1.  Integer atomics, at most one 64-bit add per
+ * workgroup per (s, c, kind): the accumulator persists across calls (zero it first), repeated runs give the same bits.
+ * Every score and target element is read from HBM once per call whatever S is (the reduced rows of a workgroup's clips
+ * are staged in LDS); when even one clip's two rows do not fit (C > 8192) the thresholds read global memory instead,
+ * with the same results.  B = 0 returns 0 and launches nothing.  Refused before any launch: null pointers (B > 0), a
+ * non-positive S or C, a negative B or T, per_class outside {0, 1}, T * C > (2^31 - 1) / 2, S * C > (2^31 - 1) / 4. */
+int bsed_tag_counts(const float* scores, int T_scores, const float* targets, int T_targets, const float* thresholds,
+                    int per_class, int S, int B, int C, long long* counts, void* stream);
+/* scores as above -> masks[row_offset + b] (uint64, a device buffer of N rows): bit c set when score[b][c] >
+ * class_thresholds[c] ((C) float32 on the device) or, with class_thresholds = NULL, > threshold.  *nonempty (device
+ * int64) += the number of clips of the batch with a non-zero mask.  C <= 64; rows row_offset .. row_offset + B must lie
+ * inside the buffer; B = 0 returns 0 and launches nothing. */
+int bsed_tag_masks(const float* scores, int T_scores, const float* class_thresholds, float threshold, int B, int C,
+                   long row_offset, long N, uint64_t* masks, long long* nonempty, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Resampling (csrc/resample.hip).  stands in for librosa.load(path, sr=cfg.sr)'s mono mix + resampling
  * (reference src/data/preprocess.py:182); the filter is this project's own (features.resample_filter), NOT
  * librosa's / soxr's: no bit parity with them is claimed.
