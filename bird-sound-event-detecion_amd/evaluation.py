@@ -35,6 +35,7 @@ assembled without a per-clip Python loop.  The collar-based event F1 that picks 
 """
 import math
 import os
+from contextlib import contextmanager as _contextmanager
 from fractions import Fraction
 
 import numpy as np
@@ -42,6 +43,126 @@ import torch
 
 from . import _lib as L
 from ._lib import BsedError
+
+
+_EVENT_COLUMNS = ["event_label", "onset", "offset", "filename"]
+
+
+@_contextmanager
+def _eval_mode(model, predictor=None):
+    """``model`` and ``predictor`` (may be None) in eval mode for the body; their training flags come back on exit,
+    also when the body raises"""
+    was_training = (model.training, predictor.training if predictor is not None else False)
+    model.eval()
+    if predictor is not None:
+        predictor.eval()
+    try:
+        yield
+    finally:
+        model.train(was_training[0])
+        if predictor is not None:
+            predictor.train(was_training[1])
+
+
+def _check_form(who, predictor, fpn, trained=False):
+    if predictor is None and not fpn and not trained:
+        raise NotImplementedError(f"{who}: predictor=None without fpn=True is the reference's seg_index call of a model "
+                                  "class outside the hot path; pass predictor=..., a self-contained model with fpn=True "
+                                  "or, to the clip-level passes, trained=True")
+
+
+def _forward(model, predictor, fpn, x, trained=False, weak=False, features=False):
+    """One batch under no_grad in the reference's call forms (src/evaluation_measures.py:163-181, 373-385) ->
+    ``(strong, weak, features)``.  ``weak`` and ``features`` (the encoder's second output, what ``saved_feature_dir``
+    dumps) are taken from what the modules return only when asked for and are None otherwise; ``trained=True`` is the
+    tagger's ``pred_weak = torch_model(batch_x)``: weak only, the weak part of a ``(strong, weak)`` return."""
+    with torch.no_grad():
+        if trained:
+            out = model(x)
+            return None, (out[1] if isinstance(out, (tuple, list)) else out), None
+        if predictor is not None:
+            encoded = model(x)
+            out = predictor(encoded[0], inference=fpn)
+        else:
+            encoded, out = None, model(x, inference=True)
+        return out[0], (out[1] if weak else None), (encoded[1] if features and encoded is not None else None)
+
+
+def _batches(dataloader, clips=False):
+    """the loader passes' unpack of ``(((input, ema_input), target), paths)`` batches -> ``(float32 GPU input, target,
+    paths, names, folders)``; with ``clips`` the clip names and their ``annotation/`` folders next to the features
+    (``<root>/wav/<name>.npy`` -> ``<name>``, ``<root>/annotation``), else None"""
+    for ((input_data, _ema), target), paths in dataloader:
+        names = folders = None
+        if clips:
+            names = [os.path.splitext(os.path.basename(p))[0] for p in paths]
+            folders = [os.path.join(os.path.dirname(os.path.dirname(p)), "annotation") for p in paths]
+        yield torch.as_tensor(input_data).float().cuda(), target, paths, names, folders
+
+
+def _encoder_labels(decoder, method_name):
+    """label list of the ManyHotEncoder whose bound ``method_name`` (``decode_strong`` / ``decode_weak``) was passed as
+    ``decoder`` (the reference's call sites pass ``many_hot_encoder.decode_strong``, src/main_baseline.py:1010-1032, and
+    ``.decode_weak``, src/audio_tagging_inference.py:287), or None for any other callable"""
+    owner = getattr(decoder, "__self__", None)
+    if owner is not None and getattr(decoder, "__name__", "") == method_name and hasattr(owner, "labels"):
+        return list(owner.labels)
+    return None
+
+
+def _read_annotations(names, folders, require_annotations=False):
+    """the ``annotation/<name>.txt`` files of these clips (first occurrence of a name), each with a ``filename`` column
+    -> ``(list of the non-empty DataFrames, number of files found)``; a missing file is skipped (an unlabelled clip:
+    predictions only) or, with ``require_annotations``, raises as the reference does"""
+    import pandas as pd
+    seen, out, n_found = {}, [], 0
+    for name, folder in zip(names, folders):
+        seen.setdefault(name, folder)
+    for name, folder in seen.items():
+        path = os.path.join(folder, name + ".txt")
+        if not os.path.exists(path):
+            if require_annotations:
+                raise FileNotFoundError(f"annotation file {path} is missing (the reference reads annotation/<name>.txt next to "
+                                        "wav/<name>.npy)")
+            continue
+        n_found += 1
+        df = pd.read_csv(path, sep="\t")
+        df["filename"] = name
+        if len(df):
+            out.append(df)
+    return out, n_found
+
+
+def _event_frame(labels, ev_class, seconds, filenames):
+    """the prediction frame of every route: event_label (object) / onset / offset (float64) / filename (object), one row
+    per event in the order given; ``filenames``: an object array, one entry per event"""
+    import pandas as pd
+    return pd.DataFrame({"event_label": np.asarray(labels, dtype=object)[ev_class], "onset": seconds[:, 0],
+                         "offset": seconds[:, 1], "filename": filenames}, columns=_EVENT_COLUMNS)
+
+
+_EVENT_OUTPUTS = {"clip": ((), torch.int32), "class": ((), torch.int32), "frames": ((2,), torch.int32),
+                  "seconds": ((2,), torch.float64)}
+
+
+def _no_events():
+    return (np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros((0, 2), np.int32), np.zeros((0, 2), np.float64))
+
+
+def _count_then_write(n, device, outputs, count, write):
+    """The two launches of every decoder: ``count(counts)`` fills the ``n`` int32 list lengths, their prefix sum gives the
+    place of every list and the total ``E`` -- read here, the one host sync of a decode --, the ``outputs`` (names of
+    ``_EVENT_OUTPUTS``) are allocated with ``max(E, 1)`` rows and ``write(offsets, *outputs)`` fills them if there is an
+    event.  The callbacks get device pointers.  -> ``(offsets (n + 1) int32: exclusive prefix, total last; E; tensors)``"""
+    offsets = torch.zeros(n + 1, device=device, dtype=torch.int32)
+    counts = torch.empty(n, device=device, dtype=torch.int32)
+    count(L.ptr(counts, torch.int32))
+    torch.cumsum(counts, 0, dtype=torch.int32, out=offsets[1:])
+    E = int(offsets[-1])
+    outs = [torch.empty((max(E, 1), *_EVENT_OUTPUTS[k][0]), device=device, dtype=_EVENT_OUTPUTS[k][1]) for k in outputs]
+    if E:
+        write(L.ptr(offsets, torch.int32), *(L.ptr(o, _EVENT_OUTPUTS[k][1]) for k, o in zip(outputs, outs)))
+    return offsets, E, outs
 
 
 def post_process(pred_strong, decoder, threshold=0.5, median_window=1, pooling_time_ratio=1, sr=32000,
@@ -73,31 +194,12 @@ def decode_regions_gpu(mask, scale, max_len_seconds):
     mask = mask.contiguous()
     B, T, C = mask.shape
     if B * C == 0 or T == 0:                            # an empty batch decodes to an empty event list
-        return (np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros((0, 2), np.int32), np.zeros((0, 2), np.float64))
-    counts = torch.empty(B * C, device=mask.device, dtype=torch.int32)
-    L.call("bsed_decode_count", L.ptr(mask), B, T, C, L.ptr(counts, torch.int32), L.stream())
-    csum = torch.cumsum(counts, 0, dtype=torch.int32)
-    offsets = (csum - counts).contiguous()
-    E = int(csum[-1])                                   # the one host sync of the decode: the list length
-    ev_clip = torch.empty(max(E, 1), device=mask.device, dtype=torch.int32)
-    ev_class = torch.empty(max(E, 1), device=mask.device, dtype=torch.int32)
-    ev_frames = torch.empty((max(E, 1), 2), device=mask.device, dtype=torch.int32)
-    ev_seconds = torch.empty((max(E, 1), 2), device=mask.device, dtype=torch.float64)
-    if E:
-        L.call("bsed_decode_write", L.ptr(mask), L.ptr(offsets, torch.int32), B, T, C, scale,
-               max_len_seconds, L.ptr(ev_clip, torch.int32), L.ptr(ev_class, torch.int32), L.ptr(ev_frames, torch.int32),
-               L.ptr(ev_seconds, torch.float64), L.stream())
-    return (ev_clip[:E].cpu().numpy(), ev_class[:E].cpu().numpy(), ev_frames[:E].cpu().numpy(),
-            ev_seconds[:E].cpu().numpy())
-
-
-def _decoder_labels(decoder):
-    """label list of the ManyHotEncoder whose bound ``decode_strong`` was passed as ``decoder`` (the reference's call
-    sites pass ``many_hot_encoder.decode_strong``, src/main_baseline.py:1010-1032), or None for any other callable"""
-    owner = getattr(decoder, "__self__", None)
-    if owner is not None and getattr(decoder, "__name__", "") == "decode_strong" and hasattr(owner, "labels"):
-        return list(owner.labels)
-    return None
+        return _no_events()
+    _, E, outs = _count_then_write(
+        B * C, mask.device, ("clip", "class", "frames", "seconds"),
+        lambda counts: L.call("bsed_decode_count", L.ptr(mask), B, T, C, counts, L.stream()),
+        lambda offsets, *ev: L.call("bsed_decode_write", L.ptr(mask), offsets, B, T, C, scale, max_len_seconds, *ev, L.stream()))
+    return tuple(o[:E].cpu().numpy() for o in outs)
 
 
 # reference src/data/config.py:62-63: cfg.median_window = [max(int(s * out_nb_frames_1s), 1) for s in median_window_s_classwise]
@@ -136,77 +238,43 @@ def get_predictions(model, dataloader, decoder, pooling_time_ratio=1, thresholds
     not on the path).  Clips without an ``annotation/<name>.txt`` (unlabelled / pseudo-labelled sets) are left out of
     groundtruth_df -- None when no clip has one -- unless ``require_annotations`` (the reference's behaviour: it raises)."""
     import pandas as pd
-    if predictor is None and not fpn:
-        raise NotImplementedError("get_predictions(predictor=None, fpn=False) is the reference's seg_index call of a model "
-                                  "class outside the hot path; pass predictor=... or a self-contained model with fpn=True")
+    _check_form("get_predictions", predictor, fpn)
     if learned_post and classwise_median_window is None:
         classwise_median_window = classwise_median_windows(sr, hop_size, pooling_time_ratio)
-    was_training = (model.training, predictor.training if predictor is not None else False)
-    model.eval()
-    if predictor is not None:
-        predictor.eval()
-    labels = _decoder_labels(decoder)
+    labels = _encoder_labels(decoder, "decode_strong")
     scale = pooling_time_ratio / (sr / hop_size)
     frames = {t: [] for t in thresholds}
     filename_list, annotation_folder_list = [], []
-    for i, (((input_data, _ema), _target), paths) in enumerate(dataloader):
-        names = [os.path.splitext(os.path.basename(p))[0] for p in paths]
-        folders = [os.path.join(os.path.dirname(os.path.dirname(p)), "annotation") for p in paths]
-        with torch.no_grad():
-            x = torch.as_tensor(input_data).float().cuda()
-            if predictor is not None:
-                encoded_x, feature_out = model(x)
-                pred_strong, _ = predictor(encoded_x, inference=fpn)
-            else:
-                pred_strong, feature_out = model(x, inference=True)[0], None
-        if saved_feature_dir is not None and feature_out is not None:
-            np.save(os.path.join(saved_feature_dir, f"{i}"), feature_out.cpu().numpy())
-        for t in thresholds:
-            mask = (binarize_median_classwise_gpu(pred_strong, t, list(classwise_median_window)) if learned_post
-                    else binarize_median_gpu(pred_strong, t, median_window))
-            if labels is not None:
-                ev_clip, ev_class, _, ev_sec = decode_regions_gpu(mask, scale, max_len_seconds)
-                frames[t].append(pd.DataFrame({"event_label": np.asarray(labels, dtype=object)[ev_class],
-                                               "onset": ev_sec[:, 0], "offset": ev_sec[:, 1],
-                                               "filename": np.asarray(names, dtype=object)[ev_clip]}))
-            else:
-                # a caller-supplied decoder function can only run on the host, clip by clip
-                rows = []
-                for j, m in enumerate(mask.cpu().numpy()):
-                    for lab, on, off in decoder(m):
-                        rows.append({"event_label": lab, "onset": float(np.clip(on * scale, 0, max_len_seconds)),
-                                     "offset": float(np.clip(off * scale, 0, max_len_seconds)), "filename": names[j]})
-                frames[t].append(pd.DataFrame(rows, columns=["event_label", "onset", "offset", "filename"]))
-        filename_list += names
-        annotation_folder_list += folders
-    model.train(was_training[0])
-    if predictor is not None:
-        predictor.train(was_training[1])
-    cols = ["event_label", "onset", "offset", "filename"]
-    dfs = [pd.concat(frames[t], ignore_index=True)[cols] if frames[t] else pd.DataFrame(columns=cols)
+    with _eval_mode(model, predictor):
+        for i, (x, _target, _paths, names, folders) in enumerate(_batches(dataloader, clips=True)):
+            pred_strong, _, feature_out = _forward(model, predictor, fpn, x, features=True)
+            if saved_feature_dir is not None and feature_out is not None:
+                np.save(os.path.join(saved_feature_dir, f"{i}"), feature_out.cpu().numpy())
+            for t in thresholds:
+                mask = (binarize_median_classwise_gpu(pred_strong, t, list(classwise_median_window)) if learned_post
+                        else binarize_median_gpu(pred_strong, t, median_window))
+                if labels is not None:
+                    ev_clip, ev_class, _, ev_sec = decode_regions_gpu(mask, scale, max_len_seconds)
+                    frames[t].append(_event_frame(labels, ev_class, ev_sec, np.asarray(names, dtype=object)[ev_clip]))
+                else:
+                    # a caller-supplied decoder function can only run on the host, clip by clip
+                    rows = []
+                    for j, m in enumerate(mask.cpu().numpy()):
+                        for lab, on, off in decoder(m):
+                            rows.append({"event_label": lab, "onset": float(np.clip(on * scale, 0, max_len_seconds)),
+                                         "offset": float(np.clip(off * scale, 0, max_len_seconds)), "filename": names[j]})
+                    frames[t].append(pd.DataFrame(rows, columns=_EVENT_COLUMNS))
+            filename_list += names
+            annotation_folder_list += folders
+    dfs = [pd.concat(frames[t], ignore_index=True)[_EVENT_COLUMNS] if frames[t] else pd.DataFrame(columns=_EVENT_COLUMNS)
            for t in thresholds]
 
     # ground-truth and duration frames (reference :226-247): first occurrence of every file name, its annotation file
     # next to the features, duration 10
-    seen = {}
-    for name, folder in zip(filename_list, annotation_folder_list):
-        seen.setdefault(name, folder)
-    duration_df = pd.DataFrame(list(seen.keys()), columns=["filename"])
+    duration_df = pd.DataFrame(list(dict.fromkeys(filename_list)), columns=["filename"])
     duration_df["duration"] = 10
+    gts, n_found = _read_annotations(filename_list, annotation_folder_list, require_annotations)
     groundtruth_df = None
-    gts, n_found = [], 0
-    for name, folder in seen.items():
-        path = os.path.join(folder, name + ".txt")
-        if not os.path.exists(path):
-            if require_annotations:
-                raise FileNotFoundError(f"get_predictions: annotation file {path} is missing (the reference reads "
-                                        "annotation/<name>.txt next to wav/<name>.npy)")
-            continue                                    # unlabelled clip: predictions only
-        n_found += 1
-        df = pd.read_csv(path, sep="\t")
-        df["filename"] = name
-        if len(df):
-            gts.append(df)
     if gts:
         groundtruth_df = pd.concat(gts, ignore_index=True)
     elif n_found:
@@ -319,20 +387,13 @@ def decode_long_gpu(mask, scale, max_len_seconds):
         raise BsedError(f"decode_long_gpu takes one (T, C) mask, got shape {tuple(mask.shape)}")
     T, C = mask.shape
     if T * C == 0:
-        return (np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros((0, 2), np.int32), np.zeros((0, 2), np.float64))
+        return _no_events()
     nchunks = -(-T // L.CONSTANTS["BSED_DECODE_LONG_FRAMES"])
-    counts = torch.empty(C * nchunks, device=mask.device, dtype=torch.int32)
-    L.call("bsed_decode_long_count", L.ptr(mask), T, C, L.ptr(counts, torch.int32), L.stream())
-    csum = torch.cumsum(counts, 0, dtype=torch.int32)
-    offsets = (csum - counts).contiguous()
-    E = int(csum[-1])                                   # the one host sync of the decode: the list length
-    ev_class = torch.empty(max(E, 1), device=mask.device, dtype=torch.int32)
-    ev_frames = torch.empty((max(E, 1), 2), device=mask.device, dtype=torch.int32)
-    ev_seconds = torch.empty((max(E, 1), 2), device=mask.device, dtype=torch.float64)
-    if E:
-        L.call("bsed_decode_long_write", L.ptr(mask), L.ptr(offsets, torch.int32), T, C, scale, max_len_seconds,
-               L.ptr(ev_class, torch.int32), L.ptr(ev_frames, torch.int32), L.ptr(ev_seconds, torch.float64), L.stream())
-    return (np.zeros(E, np.int32), ev_class[:E].cpu().numpy(), ev_frames[:E].cpu().numpy(), ev_seconds[:E].cpu().numpy())
+    _, E, outs = _count_then_write(
+        C * nchunks, mask.device, ("class", "frames", "seconds"),
+        lambda counts: L.call("bsed_decode_long_count", L.ptr(mask), T, C, counts, L.stream()),
+        lambda offsets, *ev: L.call("bsed_decode_long_write", L.ptr(mask), offsets, T, C, scale, max_len_seconds, *ev, L.stream()))
+    return (np.zeros(E, np.int32), *(o[:E].cpu().numpy() for o in outs))
 
 
 def gather_windows(wave, starts, win, frame_samples):
@@ -371,12 +432,9 @@ def detect_recording(model, wave, decoder, predictor=None, fpn=False, *, mel=Non
     shorter than one window is one clip, padded as ``MelFrontEnd.transform`` pads clips.  The models' training flags are
     restored on exit; the one host sync per threshold is the event count.  ``stage_events``: a list that receives
     (stage, start event, end event) triples for tools that time the stages."""
-    import pandas as pd
     from .features import MelFrontEnd
-    if predictor is None and not fpn:
-        raise NotImplementedError("detect_recording(predictor=None, fpn=False): pass predictor=... or a self-contained "
-                                  "model with fpn=True (see get_predictions)")
-    labels = _decoder_labels(decoder)
+    _check_form("detect_recording", predictor, fpn)
+    labels = _encoder_labels(decoder, "decode_strong")
     if labels is None:
         raise BsedError("detect_recording decodes on the GPU and needs the label list: pass the bound decode_strong of a "
                         "ManyHotEncoder as decoder")
@@ -423,33 +481,19 @@ def detect_recording(model, wave, decoder, predictor=None, fpn=False, *, mel=Non
         stage_events.append((name, s, e))
         return out
 
-    def forward(x):
-        if predictor is not None:
-            return predictor(model(x)[0], inference=fpn)[0]
-        return model(x, inference=True)[0]
-
-    was_training = (model.training, predictor.training if predictor is not None else False)
-    model.eval()
-    if predictor is not None:
-        predictor.eval()
-    try:
-        with torch.no_grad():
-            if rs is not None:
-                wave = stage("resample", lambda: rs(wave))
-            windows = stage("front_end", lambda: wave[None] if n < win else gather_windows(wave, starts, win, frame))
-            probs = []
-            for i in range(0, len(starts), batch_windows):
-                x = stage("front_end", lambda: mel.transform(windows[i:i + batch_windows]))
-                probs.append(stage("forward", lambda: forward(x)))
-            win_probs = probs[0] if len(probs) == 1 else torch.cat(probs)
-            if tuple(win_probs.shape[:2]) != (len(starts), Tp):
-                raise BsedError(f"detect_recording: the model returned {tuple(win_probs.shape)} for {len(starts)} windows "
-                                f"of {Tp} output frames (pooling_time_ratio={pooling_time_ratio})")
-            stitched = stage("stitch", lambda: stitch_windows(win_probs, starts, weighting))
-    finally:
-        model.train(was_training[0])
-        if predictor is not None:
-            predictor.train(was_training[1])
+    with _eval_mode(model, predictor), torch.no_grad():
+        if rs is not None:
+            wave = stage("resample", lambda: rs(wave))
+        windows = stage("front_end", lambda: wave[None] if n < win else gather_windows(wave, starts, win, frame))
+        probs = []
+        for i in range(0, len(starts), batch_windows):
+            x = stage("front_end", lambda: mel.transform(windows[i:i + batch_windows]))
+            probs.append(stage("forward", lambda: _forward(model, predictor, fpn, x)[0]))
+        win_probs = probs[0] if len(probs) == 1 else torch.cat(probs)
+        if tuple(win_probs.shape[:2]) != (len(starts), Tp):
+            raise BsedError(f"detect_recording: the model returned {tuple(win_probs.shape)} for {len(starts)} windows "
+                            f"of {Tp} output frames (pooling_time_ratio={pooling_time_ratio})")
+        stitched = stage("stitch", lambda: stitch_windows(win_probs, starts, weighting))
     scale = pooling_time_ratio / (cfg.sr / cfg.hop_size)
     duration = n / cfg.sr
     dfs = []
@@ -460,9 +504,7 @@ def detect_recording(model, wave, decoder, predictor=None, fpn=False, *, mel=Non
                     else binarize_median_gpu(p3, t, median_window))
             return decode_long_gpu(mask[0], scale, duration)
         _, ev_class, _, ev_sec = stage("post", post)
-        dfs.append(pd.DataFrame({"event_label": np.asarray(labels, dtype=object)[ev_class], "onset": ev_sec[:, 0],
-                                 "offset": ev_sec[:, 1], "filename": np.full(len(ev_class), filename, dtype=object)},
-                                columns=["event_label", "onset", "offset", "filename"]))
+        dfs.append(_event_frame(labels, ev_class, ev_sec, np.full(len(ev_class), filename, dtype=object)))
     predictions = dfs[0] if len(dfs) == 1 else dfs
     return (predictions, stitched, win_probs) if return_probabilities else predictions
 
@@ -471,7 +513,6 @@ def detect_recording(model, wave, decoder, predictor=None, fpn=False, *, mel=Non
 # Validation: threshold sweep, collar-based event counts, event F1
 # ---------------------------------------------------------------------------------------------------------------------
 MATCH_MAX_REF = L.CONSTANTS["BSED_MATCH_MAX_REF"]
-_EVENT_COLUMNS = ["event_label", "onset", "offset", "filename"]
 
 
 class EventLists:
@@ -509,19 +550,15 @@ class EventLists:
     def frames(self, labels, names):
         """One DataFrame per threshold with the columns, dtypes and row order (clip, class, time) that ``get_predictions``
         gives for that threshold on the same batch: event_label / onset / offset / filename."""
-        import pandas as pd
         if len(labels) < self.C or len(names) != self.B:
             raise BsedError(f"EventLists.frames: need at least {self.C} labels and {self.B} names, got {len(labels)} and {len(names)}")
         counts, _, sec = self.host()
         group = np.repeat(np.arange(counts.size), counts.ravel())
         per_s = np.concatenate([[0], np.cumsum(counts.reshape(self.S, -1).sum(1))])
-        lab, nam = np.asarray(labels, dtype=object), np.asarray(names, dtype=object)
-        out = []
+        nam, out = np.asarray(names, dtype=object), []
         for s in range(self.S):
             g = group[per_s[s]:per_s[s + 1]]
-            rows = sec[per_s[s]:per_s[s + 1]]
-            out.append(pd.DataFrame({"event_label": lab[g % self.C], "onset": rows[:, 0], "offset": rows[:, 1],
-                                     "filename": nam[(g // self.C) % self.B]}))
+            out.append(_event_frame(labels, g % self.C, sec[per_s[s]:per_s[s + 1]], nam[(g // self.C) % self.B]))
         return out
 
 
@@ -555,19 +592,15 @@ def _sweep(x, thr, win, scale, max_len_seconds):
     B, T, C = x.shape
     S = thr.numel()
     n = S * B * C
-    offsets = torch.zeros(n + 1, device=x.device, dtype=torch.int32)
     if n == 0 or T == 0:                                # an empty batch decodes to empty lists
-        return EventLists(offsets, torch.zeros((1, 2), device=x.device, dtype=torch.float64), S, B, C, 0,
+        return EventLists(torch.zeros(n + 1, device=x.device, dtype=torch.int32),
+                          torch.zeros((1, 2), device=x.device, dtype=torch.float64), S, B, C, 0,
                           torch.zeros((1, 2), device=x.device, dtype=torch.int32), thr)
-    counts = torch.empty(n, device=x.device, dtype=torch.int32)
-    L.call("bsed_sweep_count", L.ptr(x), L.ptr(thr), L.ptr(win, torch.int32), S, B, T, C, L.ptr(counts, torch.int32), L.stream())
-    torch.cumsum(counts, 0, dtype=torch.int32, out=offsets[1:])
-    E = int(offsets[-1])                                # the one host sync of the sweep: the total list length
-    ev_frames = torch.empty((max(E, 1), 2), device=x.device, dtype=torch.int32)
-    ev_seconds = torch.empty((max(E, 1), 2), device=x.device, dtype=torch.float64)
-    if E:
-        L.call("bsed_sweep_write", L.ptr(x), L.ptr(thr), L.ptr(win, torch.int32), L.ptr(offsets, torch.int32), S, B, T, C,
-               scale, max_len_seconds, L.ptr(ev_frames, torch.int32), L.ptr(ev_seconds, torch.float64), L.stream())
+    offsets, E, (ev_frames, ev_seconds) = _count_then_write(
+        n, x.device, ("frames", "seconds"),
+        lambda counts: L.call("bsed_sweep_count", L.ptr(x), L.ptr(thr), L.ptr(win, torch.int32), S, B, T, C, counts, L.stream()),
+        lambda offsets, *ev: L.call("bsed_sweep_write", L.ptr(x), L.ptr(thr), L.ptr(win, torch.int32), offsets, S, B, T, C,
+                                    scale, max_len_seconds, *ev, L.stream()))
     return EventLists(offsets, ev_seconds, S, B, C, E, ev_frames, thr)
 
 
@@ -584,25 +617,19 @@ def sweep_events_gpu(pred_strong, thresholds, median_window=1, classwise_median_
                   float(scale), float(max_len_seconds))
 
 
-def _read_annotations(names, folders, require_annotations=False):
-    """the ``annotation/<name>.txt`` files of ``get_predictions`` for these clips (first occurrence of a name), each with
-    a ``filename`` column -> list of non-empty DataFrames"""
-    import pandas as pd
-    seen, out = {}, []
-    for name, folder in zip(names, folders):
-        seen.setdefault(name, folder)
-    for name, folder in seen.items():
-        path = os.path.join(folder, name + ".txt")
-        if not os.path.exists(path):
-            if require_annotations:
-                raise FileNotFoundError(f"annotation file {path} is missing (the reference reads annotation/<name>.txt next to "
-                                        "wav/<name>.npy)")
-            continue
-        df = pd.read_csv(path, sep="\t")
-        df["filename"] = name
-        if len(df):
-            out.append(df)
-    return out
+def _event_table(df, labels, ignore_unknown, rows=None):
+    """onset / offset / event_label columns of an event frame -> ``(class (n) int64, onset (n), offset (n), keep (n) bool,
+    bad)`` in the frame's row order.  ``keep``: the rows (of ``rows``, a mask, when given) with a known label and neither
+    onset nor offset NaN (how DESED-style files mark a clip without events); ``bad``: the first row of them whose label
+    is not in ``labels``, for the caller's own error, or None -- always None with ``ignore_unknown``, which drops them."""
+    on, off = np.asarray(df["onset"], np.float64), np.asarray(df["offset"], np.float64)
+    valid = ~np.isnan(on) & ~np.isnan(off)
+    if rows is not None:
+        valid &= rows
+    index = {l: i for i, l in enumerate(labels)}
+    k = np.asarray([index.get(l, -1) for l in df["event_label"]], np.int64)
+    bad = np.nonzero(valid & (k < 0))[0]
+    return k, on, off, valid & (k >= 0), (int(bad[0]) if len(bad) and not ignore_unknown else None)
 
 
 class EventReference:
@@ -638,18 +665,10 @@ class EventReference:
             return cls(np.zeros((B, C), np.int64), np.zeros((0, 2)), names, labels, evaluated)
         clip = np.asarray([index.get(f, -1) for f in groundtruth_df["filename"]], np.int64)
         evaluated[clip[clip >= 0]] = True
-        on = np.asarray(groundtruth_df["onset"], np.float64)
-        off = np.asarray(groundtruth_df["offset"], np.float64)
-        keep = (clip >= 0) & ~np.isnan(on) & ~np.isnan(off)
-        lab_index = {l: i for i, l in enumerate(labels)}
-        cls_ = np.full(len(clip), -1, np.int64)
-        for i in np.nonzero(keep)[0]:
-            lab = groundtruth_df["event_label"].iloc[i]
-            k = lab_index.get(lab, -1)
-            if k < 0 and not ignore_unknown:
-                raise BsedError(f"EventReference: event label {lab!r} of clip {names[clip[i]]!r} is not in the label list")
-            cls_[i] = k
-        keep &= cls_ >= 0
+        cls_, on, off, keep, bad = _event_table(groundtruth_df, labels, ignore_unknown, clip >= 0)
+        if bad is not None:
+            raise BsedError(f"EventReference: event label {groundtruth_df['event_label'].iloc[bad]!r} of clip "
+                            f"{names[clip[bad]]!r} is not in the label list")
         clip, cls_, on, off = clip[keep], cls_[keep], on[keep], off[keep]
         order = np.lexsort((off, on, cls_, clip))
         counts = np.bincount(clip * C + cls_, minlength=B * C).reshape(B, C)
@@ -660,7 +679,7 @@ class EventReference:
         """the reference of a batch from ``<folder>/<name>.txt`` (tab-separated onset / offset / event_label), the files
         ``get_predictions`` reads; a clip whose file is missing or has no row is not evaluated"""
         import pandas as pd
-        dfs = _read_annotations(names, folders, require_annotations)
+        dfs, _ = _read_annotations(names, folders, require_annotations)
         return cls.from_frame(pd.concat(dfs, ignore_index=True) if dfs else None, labels, names, ignore_unknown)
 
     def check_cap(self, cap=MATCH_MAX_REF):
@@ -769,10 +788,8 @@ def validate(model, dataloader, decoder, predictor=None, fpn=False, thresholds=(
     these thresholds (``tag_counts_gpu``, one more launch per batch) and the ``TaggingResult`` hangs on ``.tagging``; with
     the default None the pass launches and returns what it did without the argument."""
     import pandas as pd
-    if predictor is None and not fpn:
-        raise NotImplementedError("validate(predictor=None, fpn=False): pass predictor=... or a self-contained model with "
-                                  "fpn=True (see get_predictions)")
-    labels = _decoder_labels(decoder)
+    _check_form("validate", predictor, fpn)
+    labels = _encoder_labels(decoder, "decode_strong")
     if labels is None:
         raise BsedError("validate decodes and scores on the GPU and needs the label list: pass the bound decode_strong of a "
                         "ManyHotEncoder as decoder")
@@ -783,24 +800,12 @@ def validate(model, dataloader, decoder, predictor=None, fpn=False, thresholds=(
     thr, win, acc = _sweep_thresholds(thresholds), None, None
     tag_thr, tag_acc = (None if tagging_thresholds is None else TagThresholds(tagging_thresholds)), None
     frames, gts, seen = [[] for _ in thresholds], [], set()
-    was_training = (model.training, predictor.training if predictor is not None else False)
-    model.eval()
-    if predictor is not None:
-        predictor.eval()
-    try:
-        for ((input_data, _ema), target), paths in dataloader:
-            names = [os.path.splitext(os.path.basename(p))[0] for p in paths]
-            folders = [os.path.join(os.path.dirname(os.path.dirname(p)), "annotation") for p in paths]
+    with _eval_mode(model, predictor):
+        for x, target, _paths, names, folders in _batches(dataloader, clips=True):
             if seen & set(names):
                 raise BsedError(f"validate: clip(s) {sorted(seen & set(names))[:3]} occur in more than one batch")
             seen |= set(names)
-            with torch.no_grad():
-                x = torch.as_tensor(input_data).float().cuda()
-                if predictor is not None:
-                    pred_strong, pred_weak = predictor(model(x)[0], inference=fpn)
-                else:
-                    out = model(x, inference=True)
-                    pred_strong, pred_weak = out[0], (None if tag_thr is None else out[1])
+            pred_strong, pred_weak, _ = _forward(model, predictor, fpn, x, weak=tag_thr is not None)
             if tag_thr is not None:
                 tag_acc = tag_counts_gpu(pred_weak, _loader_targets(target, "validate(tagging_thresholds=...)"), tag_thr,
                                          out=tag_acc)
@@ -812,7 +817,7 @@ def validate(model, dataloader, decoder, predictor=None, fpn=False, thresholds=(
                 win = _sweep_windows(median_window, classwise_median_window if learned_post else None, C)
                 acc = torch.zeros((len(thresholds), C, 3), device=pred_strong.device, dtype=torch.int64)
             events = _sweep(pred_strong, thr, win, scale, float(max_len_seconds))
-            dfs = _read_annotations(names, folders, require_annotations)
+            dfs, _ = _read_annotations(names, folders, require_annotations)
             reference = EventReference.from_frame(pd.concat(dfs, ignore_index=True) if dfs else None, labels[:C], names,
                                                   ignore_unknown)
             event_counts_gpu(events, reference, t_collar, percentage_of_length, out=acc)
@@ -820,10 +825,6 @@ def validate(model, dataloader, decoder, predictor=None, fpn=False, thresholds=(
                 gts += dfs
                 for s, df in enumerate(events.frames(labels, names)):
                     frames[s].append(df)
-    finally:
-        model.train(was_training[0])
-        if predictor is not None:
-            predictor.train(was_training[1])
     if acc is None:
         raise BsedError("validate: the dataloader yielded no batch")
     predictions = groundtruth_df = None
@@ -845,19 +846,14 @@ def recording_problem(events_df, groundtruth_df, labels, t_collar=0.2, ignore_un
     the pieces.  An estimated event goes to the piece whose onsets it can reach (to the nearest earlier one if none)."""
     labels = list(labels)
     C = len(labels)
-    lab_index = {l: i for i, l in enumerate(labels)}
     dfs = list(events_df) if isinstance(events_df, (list, tuple)) else [events_df]
 
     def columns(df, what):
         if df is None or len(df) == 0:
             return np.zeros(0, np.int64), np.zeros(0), np.zeros(0)
-        on, off = np.asarray(df["onset"], np.float64), np.asarray(df["offset"], np.float64)
-        keep = ~np.isnan(on) & ~np.isnan(off)
-        k = np.asarray([lab_index.get(l, -1) if kp else -1 for l, kp in zip(df["event_label"], keep)], np.int64)
-        if (k[keep] < 0).any() and not (ignore_unknown and what == "reference"):
-            bad = [l for l, kk, kp in zip(df["event_label"], k, keep) if kp and kk < 0][0]
-            raise BsedError(f"score_recording: {what} event label {bad!r} is not in the label list")
-        keep &= k >= 0
+        k, on, off, keep, bad = _event_table(df, labels, ignore_unknown and what == "reference")
+        if bad is not None:
+            raise BsedError(f"score_recording: {what} event label {df['event_label'].iloc[bad]!r} is not in the label list")
         return k[keep], on[keep], off[keep]
 
     rk, ron, roff = columns(groundtruth_df, "reference")
@@ -1057,23 +1053,6 @@ def _loader_targets(y, who):
     return y if isinstance(y, torch.Tensor) else torch.as_tensor(np.asarray(y))
 
 
-def _weak_forward(model, predictor, trained, fpn, x):
-    """the weak output of one batch in the reference's call forms (src/evaluation_measures.py:373-385)"""
-    if trained:
-        out = model(x)                                  # reference: pred_weak = torch_model(batch_x)
-        return out[1] if isinstance(out, (tuple, list)) else out
-    if predictor is not None:
-        return predictor(model(x)[0], inference=fpn)[1]
-    return model(x, inference=True)[1]
-
-
-def _weak_form_check(who, predictor, trained, fpn):
-    if predictor is None and not trained and not fpn:
-        raise NotImplementedError(f"{who}(predictor=None, trained=False, fpn=False) is the reference's seg_index call of a "
-                                  "model class outside the hot path; pass predictor=..., trained=True or a "
-                                  "self-contained model with fpn=True")
-
-
 def validate_weak(model, dataloader, predictor=None, trained=False, fpn=False, thresholds=(0.5,), class_thresholds=None):
     """One pass of clip-level (weak) scoring on the GPU -> ``TaggingResult``.  The eval-mode forward of ``get_predictions``
     on the same ``(((input, ema_input), target), paths)`` batches; the weak output of every batch is scored against the
@@ -1082,23 +1061,13 @@ def validate_weak(model, dataloader, predictor=None, trained=False, fpn=False, t
     (one row: the reference's ``thresholds_``).  ``trained=True``: ``model(x)`` is the tagger itself (the reference's
     ``pred_weak = torch_model(batch_x)``); a ``(strong, weak)`` return, as ``CRNN_pred`` gives, contributes its weak part.
     Training flags are restored on exit."""
-    _weak_form_check("validate_weak", predictor, trained, fpn)
+    _check_form("validate_weak", predictor, fpn, trained)
     thr = TagThresholds([list(class_thresholds)] if class_thresholds is not None else list(thresholds))
     acc = None
-    was_training = (model.training, predictor.training if predictor is not None else False)
-    model.eval()
-    if predictor is not None:
-        predictor.eval()
-    try:
-        for ((input_data, _ema), target), _paths in dataloader:
-            with torch.no_grad():
-                x = torch.as_tensor(input_data).float().cuda()
-                pred_weak = _weak_forward(model, predictor, trained, fpn, x)
+    with _eval_mode(model, predictor):
+        for x, target, _paths, _, _ in _batches(dataloader):
+            pred_weak = _forward(model, predictor, fpn, x, trained, weak=True)[1]
             acc = tag_counts_gpu(pred_weak, _loader_targets(target, "validate_weak"), thr, out=acc)
-    finally:
-        model.train(was_training[0])
-        if predictor is not None:
-            predictor.train(was_training[1])
     if acc is None:
         raise BsedError("validate_weak: the dataloader yielded no batch")
     return TaggingResult(thr, acc.cpu().numpy())        # the one read-back of the pass
@@ -1113,15 +1082,6 @@ def get_f_measure_by_class(torch_model, nb_tags, dataloader_, thresholds_=None, 
     if res.counts.shape[1] != nb_tags:
         raise BsedError(f"get_f_measure_by_class: the model returned {res.counts.shape[1]} classes, nb_tags is {nb_tags}")
     return res.class_f1[0].copy()
-
-
-def _weak_decoder_labels(decoder):
-    """label list of the ManyHotEncoder whose bound ``decode_weak`` was passed as ``decoder`` (the reference's call site
-    passes ``many_hot_encoder.decode_weak``, src/audio_tagging_inference.py:287), or None for any other callable"""
-    owner = getattr(decoder, "__self__", None)
-    if owner is not None and getattr(decoder, "__name__", "") == "decode_weak" and hasattr(owner, "labels"):
-        return list(owner.labels)
-    return None
 
 
 def pseudo_label_frame(masks, filenames, labels):
@@ -1151,8 +1111,8 @@ def pseudo_label(model, dataloader, decoder, predictor=None, trained=False, fpn=
     ``decoder``: the bound ``decode_weak`` of a ManyHotEncoder (its label list names the bits); ``filename`` is the path
     string the loader yielded; clips without a label are left out; row order is loader order.  ``save_path``: also
     written as ``to_csv(index=False, sep="\\t")``.  Training flags are restored on exit."""
-    _weak_form_check("pseudo_label", predictor, trained, fpn)
-    labels = _weak_decoder_labels(decoder)
+    _check_form("pseudo_label", predictor, fpn, trained)
+    labels = _encoder_labels(decoder, "decode_weak")
     if labels is None:
         raise BsedError("pseudo_label thresholds on the GPU and needs the label list: pass the bound decode_weak of a "
                         "ManyHotEncoder as decoder")
@@ -1162,15 +1122,9 @@ def pseudo_label(model, dataloader, decoder, predictor=None, trained=False, fpn=
         capacity = 4096
     buf = nonempty = None
     filenames = []
-    was_training = (model.training, predictor.training if predictor is not None else False)
-    model.eval()
-    if predictor is not None:
-        predictor.eval()
-    try:
-        for ((input_data, _ema), _target), paths in dataloader:
-            with torch.no_grad():
-                x = torch.as_tensor(input_data).float().cuda()
-                pred_weak = _weak_forward(model, predictor, trained, fpn, x)
+    with _eval_mode(model, predictor):
+        for x, _target, paths, _, _ in _batches(dataloader):
+            pred_weak = _forward(model, predictor, fpn, x, trained, weak=True)[1]
             B, C = pred_weak.shape[0], pred_weak.shape[-1]
             if C > len(labels):
                 raise BsedError(f"pseudo_label: the model returned {C} classes, the decoder has {len(labels)} labels")
@@ -1186,10 +1140,6 @@ def pseudo_label(model, dataloader, decoder, predictor=None, trained=False, fpn=
                 buf = grown
             tag_masks_gpu(pred_weak, threshold, class_thresholds, out=buf, row_offset=n, nonempty=nonempty)
             filenames += [str(p) for p in paths]
-    finally:
-        model.train(was_training[0])
-        if predictor is not None:
-            predictor.train(was_training[1])
     if buf is None:
         raise BsedError("pseudo_label: the dataloader yielded no batch")
     masks = buf[:len(filenames)].cpu().numpy().view(np.uint64)      # the one read-back of the pool

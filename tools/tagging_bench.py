@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from bsed_amd.evaluation import TagThresholds, _weak_forward, tag_counts_gpu  # noqa: E402
+from bsed_amd.evaluation import TagThresholds, _forward, tag_counts_gpu  # noqa: E402
 
 CLIPS, BATCH, C, S, T = 3008, 64, 20, 50, 313
 ROUNDS, WARMUP, REPEAT = 9, 3, 20
@@ -122,7 +122,7 @@ def main():
             for _ in range(CLIPS // BATCH):
                 e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
                 e[0].record()
-                weak = _weak_forward(crnn, pred, False, False, x)
+                weak = _forward(crnn, pred, False, x, weak=True)[1]
                 e[1].record()
                 out = tag_counts_gpu(weak, y, thr, out=out)
                 e[2].record()
