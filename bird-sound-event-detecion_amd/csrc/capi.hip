@@ -20,7 +20,7 @@ extern "C" int bsed_abi_version(void) { return 7; }   // 7: clip-level tagging c
 // ----------------------------------------------------------------------------------------------
 // Device-resident step state (HIP-graph replays of a train step, engine.SEDTrainer.capture_step): a captured launch
 // bakes its scalar arguments, so what changes from step to step -- the dropout seed, the optimizer's step count and the
-// learning rate -- is ALSO read from device memory.  While the pointers are set,
+// learning rate -- is ALSO read from device memory.  For a launch made while the pointers are set,
 //   - the dropout kernels of the plain train step add *seed_add to their seed: bsed_dropout, bsed_block0_fwd / _bwd,
 //     bsed_glu_fwd3 / bsed_glu_bwd3 / bsed_glu_bwd3n, bsed_glu16_fwd / _bwd, bsed_glu_bwd_fused and the GLU_POOL /
 //     GLU_BWD epilogues of bsed_igemm.  bsed_leaky_dropout_fwd / _bwd (discriminator) and bsed_mel_noise (mean teacher)
@@ -28,12 +28,14 @@ extern "C" int bsed_abi_version(void) { return 7; }   // 7: clip-level tagging c
 //   - bsed_adam_step adds *step_add to its step count and takes *lr instead of its lr argument;
 //   - bsed_step_state_advance (a node of the graph) bumps the two addends.
 // Null pointers = eager mode (the default): the host scalars alone, the same arithmetic, the same bits.  The pointers
-// are PROCESS-global and read on the host at launch time: a caller that launches an eager step while they are set must
-// clear them around it (engine.SEDTrainer.train_step does).
+// are read on the host at launch time and are meant to be set only for the duration of a stream capture, on the
+// capturing thread (they are thread_local: launches of other threads never see them): the captured nodes carry the
+// pointers they were captured with, so a replay does not consult the library, and the memory behind them must outlive
+// the graph.
 // ----------------------------------------------------------------------------------------------
-static const uint64_t* g_seed_add = nullptr;
-static const int* g_step_add = nullptr;
-static const float* g_lr = nullptr;
+static thread_local const uint64_t* g_seed_add = nullptr;
+static thread_local const int* g_step_add = nullptr;
+static thread_local const float* g_lr = nullptr;
 const uint64_t* bsed_seed_add_ptr() { return g_seed_add; }
 const int* bsed_step_add_ptr() { return g_step_add; }
 const float* bsed_lr_ptr() { return g_lr; }

@@ -16,7 +16,7 @@ and discriminator live in ONE flat arena (``parallel.GradArena``) whose all-redu
 but the first two CNN blocks' has been enqueued, and overlaps the rest of it; the 1/world factor is folded into
 the optimizer kernel.
 """
-import functools
+import contextlib
 
 import numpy as np
 
@@ -205,34 +205,6 @@ class FlatSGD:
 
 
 # ----------------------------------------------------------------------------- the train step
-# The trainer whose captured graph the library's device-resident step state belongs to (capture_step .. release_graph),
-# or None.  That state is ONE set of pointers per process, read on the host whenever a dropout or Adam kernel is
-# launched (csrc/capi.hip): every eager step of ANY trainer has to run with the pointers cleared.
-_armed = None
-
-
-def _eager_step(step):
-    """An eager step (train_step / train_step_isp) while some trainer holds a captured graph: the library is pointed
-    away from the graph's device-resident step state for the duration of the step, so the kernels take the host's
-    scalars alone, exactly as without a graph in the process.  If the graph is this trainer's own, the step is one step
-    of ITS sequence: the same ``bsed_step_state_advance`` the graph ends with is enqueued behind it, so the next replay
-    continues one step later (the scalars baked at capture never move)."""
-    @functools.wraps(step)
-    def run(self, *args, **kwargs):
-        owner = _armed
-        if owner is None:
-            return step(self, *args, **kwargs)
-        owner._bind_step_state(False)
-        try:
-            out = step(self, *args, **kwargs)
-        finally:
-            owner._bind_step_state(True)
-        if owner is self:
-            self._advance_step_state()
-        return out
-    return run
-
-
 class SEDTrainer:
     """One object = the state of a training run on ONE GPU (rank).  ``train_step`` is one iteration of the
     reference's ``train_mt`` loop body."""
@@ -385,7 +357,6 @@ class SEDTrainer:
         """wait for the early segment's all-reduce (started inside the last backward pass), exchange the tail"""
         self.arena.finish()
 
-    @_eager_step
     def train_step(self, syn_x, syn_y, real_x=None, real_y_weak=None, real_x_ema=None, consistency_cost=None,
                    from_wave=False, next_waves=None):
         """One iteration (see ``_train_step`` for the arguments).  With the EMA teacher on its own stream the step itself
@@ -397,7 +368,13 @@ class SEDTrainer:
         (measured: no gain for the plain step, 13.48-13.50 vs 13.52-13.53 ms)."""
         mt = self.ema_crnn is not None and real_x is not None
         if not (mt and self.teacher_overlap):
-            return self._train_step(syn_x, syn_y, real_x, real_y_weak, real_x_ema, consistency_cost, from_wave, next_waves)
+            out = self._train_step(syn_x, syn_y, real_x, real_y_weak, real_x_ema, consistency_cost, from_wave, next_waves)
+            if self._graph is not None:
+                # an eager step of a trainer that holds a graph is one step of ITS sequence: the advance the graph ends
+                # with is enqueued behind it, so the next replay continues one step later (no EMA teacher here: a
+                # trainer that has one cannot capture)
+                self._advance_step_state()
+            return out
         caller = torch.cuda.current_stream()
         if self._step_stream is None:
             self._step_stream = torch.cuda.Stream(priority=-1)
@@ -535,28 +512,28 @@ class SEDTrainer:
         removes the host from the loop.  ``warmup`` eager steps run first (allocator, weight-pack plan, lazy tables).
         Returns after the capture; then call ``replay_step(syn_x, syn_y)``.
 
-        What changes from step to step lives in DEVICE memory (``bsed_set_step_state``): an addend of every dropout seed
-        and of Adam's step count, both advanced by the last node of the graph, and the learning rate, which
-        ``replay_step`` refreshes from ``optimizer.lr``; inputs are copied into the graph's static tensors.  The contract,
+        What changes from step to step lives in DEVICE memory: an addend of every dropout seed and of Adam's step count,
+        both advanced by the last node of the graph, and the learning rate, which ``replay_step`` refreshes from
+        ``optimizer.lr``; inputs are copied into the graph's static tensors.  The library is pointed at that memory
+        (``bsed_set_step_state``) only while the step is being captured, on the capturing thread: the graph's nodes carry
+        the pointers they were captured with, the trainer keeps the memory for as long as it keeps the graph, and after
+        ``capture_step`` has returned or raised the library holds no pointer.  Any number of trainers of a process may
+        hold a graph.  The contract,
         for every ``conv_mode`` and A/B switch of the model (tests/test_graph_step_gpu.py): a sequence of steps gives the
         same bits whether its steps are replayed or eager, including
           - ``train_step`` calls of this trainer between replays (any batch size: the last batch of an epoch) -- they
             run on the host's scalars and advance the device state by one step;
           - ``adjust_learning_rate`` / any assignment to ``optimizer.lr`` between steps;
-          - eager steps of OTHER trainers in the process, which never see this trainer's state.
+          - steps of OTHER trainers in the process, eager or replayed, and direct calls of ``ops.dropout``, the GLU
+            wrappers or ``ops.adam_step``, which never see this trainer's state.
         Refused with ``BsedError``: EMA teacher, discriminator, a data-parallel group (their per-step host decisions
-        are not graph nodes), an optimizer other than ``FlatAdam`` (its per-step scalars are not device-resident), and a
-        capture while another trainer of the process holds a graph (the library has one step state per process)."""
-        global _armed
+        are not graph nodes) and an optimizer other than ``FlatAdam`` (its per-step scalars are not device-resident)."""
         if self.ema_crnn is not None or self.domain_loss is not None or self.world != 1:
             raise L.BsedError("capture_step covers the plain single-rank step (no EMA teacher, no discriminator, no "
                               "data-parallel group: their per-step host decisions are not graph nodes yet)")
         if not isinstance(self.optimizer, FlatAdam):
             raise L.BsedError("capture_step needs a FlatAdam optimizer: only its step count and learning rate are read "
                               "from device memory by a replayed step")
-        if _armed is not None and _armed is not self:
-            raise L.BsedError("capture_step: another trainer of this process holds a captured graph (the library keeps "
-                              "one device-resident step state per process): release_graph() it first")
         self.release_graph()
         dev = self.crnn.flat.device
         self._g_x = syn_x.clone()
@@ -573,27 +550,27 @@ class SEDTrainer:
         base_count = self.optimizer.step_count
         torch.cuda.synchronize()
         graph = torch.cuda.CUDAGraph()
-        self._bind_step_state(True)
         try:
-            with torch.cuda.graph(graph):
+            with self._step_state_bound(), torch.cuda.graph(graph):
                 out = self._train_step(self._g_x, self._g_y, from_wave=from_wave)
                 self._advance_step_state()
-        except BaseException:
-            self._bind_step_state(False)
-            raise
         finally:
             # the capture ran no kernel: undo its host-side bookkeeping (the first replay IS that step)
             self.global_step = self._g_base_step
             self.optimizer.step_count = base_count
         self._graph, self._g_out = graph, out
-        _armed = self
         return self
 
-    def _bind_step_state(self, on):
-        """point the library at this trainer's device-resident step state, or back at the host scalars alone"""
+    @contextlib.contextmanager
+    def _step_state_bound(self):
+        """the library reads this trainer's device-resident step state inside the block (the capture), and nowhere else"""
         s = self._g_state
-        L.check(L.lib().bsed_set_step_state(s[0:1].data_ptr(), s[1:2].data_ptr(), self._g_lr.data_ptr()) if on
-                else L.lib().bsed_set_step_state(None, None, None), "bsed_set_step_state")
+        L.check(L.lib().bsed_set_step_state(s[0:1].data_ptr(), s[1:2].data_ptr(), self._g_lr.data_ptr()),
+                "bsed_set_step_state")
+        try:
+            yield
+        finally:
+            L.check(L.lib().bsed_set_step_state(None, None, None), "bsed_set_step_state")
 
     def _advance_step_state(self):
         """one step further, in stream order: the last node of the graph, and what an eager step between replays enqueues"""
@@ -627,15 +604,12 @@ class SEDTrainer:
         return self._g_out
 
     def release_graph(self):
-        """back to eager steps only: the library stops reading the device-resident step state, the graph is dropped"""
-        global _armed
-        if _armed is self:
-            self._bind_step_state(False)
-            _armed = None
+        """back to eager steps only: the graph is dropped (its step state and static tensors go with the next capture or
+        with the trainer)"""
         self._graph = None
 
     # ------------------------------------------------------------------ ISP (shift-consistency) iteration
-    @_eager_step
+    # (no step-state advance as in train_step: ISP needs the EMA teacher, and a trainer that has one cannot hold a graph)
     def train_step_isp(self, syn_x, syn_y, real_x, real_y_weak, real_x_ema=None, shift_frames=None, shift_bins=None,
                        consistency_cost=None, pooling_time_ratio=4, from_wave=False):
         """One iteration of ``train_mt`` with ``-mt -ISP`` (reference src/main_baseline.py:229-277,337-420,431-529):

@@ -637,14 +637,16 @@ int bsed_selftest_mfma(const float* A, const float* B, float* C, int K, void* st
 /* the same through v_mfma_f32_32x32x16_bf16 with bf16x3 split operands (K a multiple of 16) */
 int bsed_selftest_mfma_bf16x3(const float* A, const float* B, float* C, int K, void* stream);
 
-/* Device-resident step state for HIP-graph replays of a train step (csrc/capi.hip).  While it is set, the dropout kernels
- * of the plain train step -- bsed_dropout, bsed_block0_fwd / _bwd, bsed_glu_fwd3, bsed_glu_bwd3, bsed_glu_bwd3n,
- * bsed_glu16_fwd / _bwd, bsed_glu_bwd_fused and the GLU_POOL / GLU_BWD epilogues of bsed_igemm -- add *seed_add_dev
- * (uint64) to their seed, and bsed_adam_step adds *step_add_dev (int) to its step count and uses *lr_dev (float) in
- * place of its lr argument.  bsed_leaky_dropout_fwd / _bwd and bsed_mel_noise do not read it.
- * bsed_step_state_advance is the graph node that bumps the two addends after a step.  The state is process-global and
- * read on the host when a kernel is launched.  All three NULL = eager mode (the default); a mix of NULL and non-NULL is
- * refused. */
+/* Device-resident step state for HIP-graph replays of a train step (csrc/capi.hip).  In a launch made while it is set,
+ * the dropout kernels of the plain train step -- bsed_dropout, bsed_block0_fwd / _bwd, bsed_glu_fwd3, bsed_glu_bwd3,
+ * bsed_glu_bwd3n, bsed_glu16_fwd / _bwd, bsed_glu_bwd_fused and the GLU_POOL / GLU_BWD epilogues of bsed_igemm -- add
+ * *seed_add_dev (uint64) to their seed, and bsed_adam_step adds *step_add_dev (int) to its step count and uses *lr_dev
+ * (float) in place of its lr argument.  bsed_leaky_dropout_fwd / _bwd and bsed_mel_noise do not read it.
+ * bsed_step_state_advance is the graph node that bumps the two addends after a step.  The state belongs to the calling
+ * thread and is read on the host when a kernel is launched: set it immediately before a stream capture and clear it
+ * immediately after, on the capturing thread.  A captured graph carries the pointers it was captured with and never
+ * consults the library again; the memory behind them must outlive the graph.  All three NULL = eager mode (the
+ * default); a mix of NULL and non-NULL is refused. */
 int bsed_set_step_state(const void* seed_add_dev, const void* step_add_dev, const void* lr_dev);
 int bsed_step_state_advance(void* seed_add_dev, void* step_add_dev, uint64_t seed_inc, int step_inc, void* stream);
 

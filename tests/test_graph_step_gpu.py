@@ -1,8 +1,9 @@
 """HIP-graph replay of the plain train step (engine.SEDTrainer.capture_step / replay_step): the reference's batch of 24
-(/root/reference/src/data/config.py:70 batch_size = 12 -> 24 clips per step, src/main_baseline.py:737-740) is host-bound
+(its src/data/config.py:70: batch_size = 12 -> 24 clips per step, src/main_baseline.py:737-740) is host-bound
 in eager mode.  A replayed step must equal the eager step BIT FOR BIT: the per-step scalars a capture bakes (dropout seed,
-Adam step count, learning rate) are also read from device memory (bsed_set_step_state); the first two are advanced by a
-node of the graph, the third is refreshed by replay_step.
+Adam step count, learning rate) are also read from device memory, which the library is pointed at (bsed_set_step_state)
+only while the step is being captured; the first two are advanced by a node of the graph, the third is refreshed by
+replay_step.  A graph carries the pointers it was captured with: nothing outside a capture reads them.
 
 The reference of every test here is the EAGER path of the same build: a fresh trainer with the same seeds and inputs that
 takes the same sequence of steps through ``train_step`` only and never captures a graph (the eager path itself is pinned
@@ -13,11 +14,14 @@ after EVERY compared step.  No tolerance anywhere.  Dropout is 0.5 throughout so
 What the cases cover (each one states the failure it would catch):
   a. every kernel route that carries a dropout seed (exact-fp32 mode, both A/B switches, the waveform front end);
   b. the masks really advance from replay to replay (guards a. against a seed frozen on BOTH sides);
-  c. eager steps of the armed trainer between replays (the smaller last batch of an epoch), release, re-capture;
+  c. eager steps of the same trainer between replays (the smaller last batch of an epoch), release, re-capture;
   d. a learning-rate schedule (engine.adjust_learning_rate before every step);
-  e. a second trainer's eager steps while the first holds a graph (the library's step state is process-global);
+  e. what a held graph must not touch (the step state is bound for the capture only): a second trainer's eager steps,
+     its own capture and replays interleaved with the first's, direct calls of ops.dropout / ops.adam_step, and
+     whatever runs after a trainer was dropped without release_graph;
   f. replay_step / capture_step refuse what they cannot do, before touching anything."""
 import contextlib
+import gc
 
 import pytest
 import torch
@@ -113,32 +117,37 @@ def _run(tr, script, graph, from_wave=False):
          ("eager", x, y)            train_step on both sides
          ("release",)               graph side: release_graph
          ("lr", ramp)               engine.adjust_learning_rate(optimizer, rampup_value=ramp) on both sides"""
-    from bsed_amd.engine import SEDTrainer, adjust_learning_rate
-    kw = {"from_wave": True} if from_wave else {}
-    snaps = []
     try:
-        for op, *a in script:
-            if op == "capture":
-                if graph:
-                    tr.capture_step(a[0], a[1], warmup=a[2], **kw)
-                else:
-                    for _ in range(a[2]):
-                        tr.train_step(a[0], a[1], **kw)
-            elif op == "replay":
-                out = tr.replay_step(a[0], a[1]) if graph else tr.train_step(a[0], a[1], **kw)
-                snaps.append(_snap(tr, SEDTrainer.loss_value(out)))
-            elif op == "eager":
-                snaps.append(_snap(tr, SEDTrainer.loss_value(tr.train_step(a[0], a[1], **kw))))
-            elif op == "release":
-                if graph:
-                    tr.release_graph()
-            elif op == "lr":
-                adjust_learning_rate(tr.optimizer, rampup_value=a[0])
-            else:
-                raise AssertionError(op)
+        snaps = [_apply(tr, entry, graph, from_wave) for entry in script]
     finally:
         tr.release_graph()
-    return snaps
+    return [s for s in snaps if s is not None]
+
+
+def _apply(tr, entry, graph, from_wave=False):
+    """one entry of a ``_run`` script; the snapshot after it if it is a step, else None"""
+    from bsed_amd.engine import SEDTrainer, adjust_learning_rate
+    kw = {"from_wave": True} if from_wave else {}
+    op, *a = entry
+    if op == "capture":
+        if graph:
+            tr.capture_step(a[0], a[1], warmup=a[2], **kw)
+        else:
+            for _ in range(a[2]):
+                tr.train_step(a[0], a[1], **kw)
+    elif op == "replay":
+        out = tr.replay_step(a[0], a[1]) if graph else tr.train_step(a[0], a[1], **kw)
+        return _snap(tr, SEDTrainer.loss_value(out))
+    elif op == "eager":
+        return _snap(tr, SEDTrainer.loss_value(tr.train_step(a[0], a[1], **kw)))
+    elif op == "release":
+        if graph:
+            tr.release_graph()
+    elif op == "lr":
+        adjust_learning_rate(tr.optimizer, rampup_value=a[0])
+    else:
+        raise AssertionError(op)
+    return None
 
 
 def _compare(make_trainer, script, from_wave=False, what=""):
@@ -279,39 +288,102 @@ def test_replayed_steps_follow_the_learning_rate_schedule():
 
 
 # ------------------------------------------------------------------------------------------------------------------
-# e. two trainers in one process
+# e. what a held graph must not touch
 # ------------------------------------------------------------------------------------------------------------------
 def test_second_trainer_steps_eagerly_beside_an_armed_one():
-    """The library's device-resident step state is ONE set of pointers per process.  This build SERVES a second trainer:
-    its eager steps run with the pointers cleared and are bit-identical to the same steps with no graph anywhere in the
-    process (with trainer A's addends they would use A's progress as extra seed and step offsets).  A's replays are
-    undisturbed.  What a second trainer cannot do is capture a graph of its own while A holds one: BsedError, nothing
-    launched, nothing changed."""
-    from bsed_amd._lib import BsedError
-    da, db = _batches(6), _batches(3, base=30)
-    b_script = [("eager", *db[0]), ("eager", *db[1])]
-    b_alone = _run(_trainer(weights=21, seed=5), b_script, graph=False)       # no graph exists yet
-    a_eager = _run(_trainer(), _standard_script(da[:5]), graph=False)
+    """Two trainers, each with a graph of its own.  The library is pointed at a trainer's device-resident step state only
+    while that trainer captures, so B's eager steps beside A's graph equal the same steps with no graph anywhere in the
+    process, B captures while A holds a graph, and their replays and eager steps (A's on the smaller last batch of an
+    epoch, B's at its captured shape) alternate: after EVERY step the stepping trainer equals the same trainer run alone,
+    all eager, through the same sequence.  A capture that left the library pointed at B's state would give A's eager step
+    B's addends; graphs that shared one state would advance each other's seeds and step counts."""
+    da, db = _batches(5), _batches(7, base=30)
+    small = _batches(1, B=2, base=40)[0]
+    a_script = [("capture", *da[0], 3), ("replay", *da[1]), ("eager", *small), ("replay", *da[2]), ("replay", *da[3])]
+    b_script = [("eager", *db[0]), ("eager", *db[1]), ("capture", *db[2], 2), ("replay", *db[3]), ("replay", *db[4]),
+                ("eager", *db[5]), ("replay", *db[6])]
+    # both references before any graph exists: B's first two steps are its steps with no graph anywhere in the process
+    want = {"A": _run(_trainer(), a_script, graph=False), "B": _run(_trainer(weights=21, seed=5), b_script, graph=False)}
     A, B = _trainer(), _trainer(weights=21, seed=5)
+    todo = {"A": (A, iter(a_script)), "B": (B, iter(b_script))}
+    done = {"A": 0, "B": 0}
+
+    def step(who):
+        tr, entries = todo[who]
+        snap = _apply(tr, next(entries), graph=True)
+        if snap is not None:
+            _assert_same(snap, want[who][done[who]], f"trainer {who} step {done[who] + 1} beside the other trainer")
+            done[who] += 1
     try:
-        A.capture_step(*da[0], warmup=3)
-        from bsed_amd.engine import SEDTrainer
-        got = [_snap(A, SEDTrainer.loss_value(A.replay_step(*da[1])))]
-        b_beside = _run(B, b_script, graph=False)                             # (its release_graph is a no-op for A)
-        for i, (g, w) in enumerate(zip(b_beside, b_alone)):
-            _assert_same(g, w, f"trainer B step {i + 1} beside an armed trainer A")
-        got.append(_snap(A, SEDTrainer.loss_value(A.replay_step(*da[2]))))
-        before = _snap(B)
-        with pytest.raises(BsedError):
-            B.capture_step(*db[2], warmup=2)
-        _assert_same(_snap(B), before, "trainer B after its refused capture")
-        got.append(_snap(A, SEDTrainer.loss_value(A.replay_step(*da[3]))))
-        got.append(_snap(A, SEDTrainer.loss_value(A.replay_step(*da[4]))))
-        for i, (g, w) in enumerate(zip(got, a_eager)):
-            _assert_same(g, w, f"trainer A replay {i + 1} around trainer B's steps")
+        step("A")                                       # A captures
+        step("B")                                       # B steps eagerly beside A's graph, twice
+        step("B")
+        assert A._graph is not None and B._graph is None
+        step("B")                                       # B captures while A holds a graph
+        assert A._graph is not None and B._graph is not None
+        for _ in range(4):                              # A replay, B replay, A eager (B = 2), B replay,
+            step("A")                                   # A replay, B eager, A replay, B replay
+            step("B")
+        assert done == {"A": len(want["A"]), "B": len(want["B"])} == {"A": 4, "B": 6}
     finally:
         A.release_graph()
         B.release_graph()
+
+
+def test_direct_op_calls_do_not_see_a_held_graphs_step_state():
+    """ops.dropout and ops.adam_step called directly while a trainer holds a graph whose device addends are both non-zero
+    (two replays) give the bits of the same calls made before the trainer existed: the mask of (rng_stream, seed) alone,
+    the bias correction of ``step`` alone.  With the library still pointed at the graph's state they would run with
+    seed + 2 steps' worth of addend and step + 2.  The replay after them equals the all-eager trainer's step: the direct
+    calls did not disturb the graph either.  3 x 1000 elements: not a multiple of the wave size."""
+    from bsed_amd import ops
+    from bsed_amd.engine import SEDTrainer
+    g = torch.Generator().manual_seed(3)
+    x = torch.randn(3, 1000, generator=g).cuda()
+    adam_in = [torch.randn(1000, generator=g).cuda() for _ in range(3)] + [torch.rand(1000, generator=g).cuda()]
+
+    def direct():
+        p, grad, m, v = [t.clone() for t in adam_in]
+        ops.adam_step(p, grad, m, v, 1e-3, 3)
+        out = {"dropout": ops.dropout(x, 0.5, 200, 1234567), "p": p, "m": m, "v": v}
+        torch.cuda.synchronize()
+        return out
+    before = direct()
+    assert 0.3 < float((before["dropout"] == 0).float().mean()) < 0.7 and not torch.equal(before["p"], adam_in[0])
+    d = _batches(4)
+    eager = _run(_trainer(), _standard_script(d), graph=False)
+    tr = _trainer()
+    try:
+        tr.capture_step(*d[0], warmup=3)
+        for k in (1, 2):
+            _assert_same(_snap(tr, SEDTrainer.loss_value(tr.replay_step(*d[k]))), eager[k - 1], f"replay {k}")
+        assert bool((tr._g_state[:2] != 0).all())       # seed addend, step addend
+        during = direct()
+        for k, w in before.items():
+            assert torch.equal(during[k], w), f"{k} of a direct call differs in {int((during[k] != w).sum())} of " \
+                                              f"{w.numel()} entries while a graph is held"
+        _assert_same(_snap(tr, SEDTrainer.loss_value(tr.replay_step(*d[3]))), eager[2], "the replay after the direct calls")
+    finally:
+        tr.release_graph()
+
+
+def test_a_trainer_dropped_without_release_leaves_nothing_behind():
+    """A trainer that captured and replayed is garbage-collected WITHOUT release_graph: its step state is freed device
+    memory.  The library must not be pointing at it: two eager steps of a fresh trainer afterwards equal the same steps
+    taken before any graph existed in the process."""
+    d, db = _batches(2), _batches(2, base=30)
+    b_script = [("eager", *db[0]), ("eager", *db[1])]
+    b_alone = _run(_trainer(weights=21, seed=5), b_script, graph=False)       # no graph exists yet
+    A = _trainer()
+    A.capture_step(*d[0], warmup=3)
+    A.replay_step(*d[1])
+    del A
+    gc.collect()
+    torch.cuda.synchronize()
+    b_after = _run(_trainer(weights=21, seed=5), b_script, graph=False)
+    assert len(b_after) == len(b_alone) == 2
+    for i, (g, w) in enumerate(zip(b_after, b_alone)):
+        _assert_same(g, w, f"trainer B step {i + 1} after trainer A was dropped unreleased")
 
 
 # ------------------------------------------------------------------------------------------------------------------
