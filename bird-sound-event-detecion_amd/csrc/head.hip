@@ -39,119 +39,6 @@ __device__ __forceinline__ void head_stage_rows(float* dst, const float* __restr
 // row of register r in the 32 x 32 MFMA result fragment (column = lane & 31, lh = lane >> 5)
 __device__ __forceinline__ int hd_crow(int r, int lh) { return (r & 3) + 8 * (r >> 2) + 4 * lh; }
 
-// logits for a chunk of frames: lg[f][0..C) dense head, lg[f][C..2C) softmax head.
-// The (32 frames x 2C) x 256 contraction runs on v_mfma_f32_32x32x2_f32 (f32 operands, exact fp32 products and sums): with
-// scalar FMAs every multiply-add paid an LDS read of the weight (1.2 reads per FMA: the kernel was LDS-bound).  Wave w
-// takes column tile w & 1 (classes 32 (w & 1) ..; columns beyond 2C compute on a clamped weight row and are dropped) and
-// the K half w >> 1; the two K halves meet in LDS.  Operands: one dword per lane and MFMA, conflict-free (pitch 257).
-template <int C>
-__device__ __forceinline__ void head_logits(const float* xs /*[HD_FR][HD_K+1]*/, const float* ws /*[2C][HD_K+1]*/,
-                                            const float* bs /*[2C]*/, float* lg /*[HD_FR][2C]*/,
-                                            float* lgp /*[2][HD_FR][2C] scratch*/, int tid) {
-  const int wave = tid >> 6, lane = tid & 63, li = lane & 31, lh = lane >> 5;
-  const int nt = wave & 1, kh = wave >> 1;
-  const int n = 32 * nt + li;
-  const float* ap = xs + li * (HD_K + 1) + (HD_K / 2) * kh + lh;
-  const float* bp = ws + min(n, 2 * C - 1) * (HD_K + 1) + (HD_K / 2) * kh + lh;
-  f32x16 acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll 8
-  for (int s = 0; s < HD_K / 4; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[2 * s], bp[2 * s], acc, 0, 0, 0);
-  if (n < 2 * C) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) lgp[(kh * HD_FR + hd_crow(r, lh)) * (2 * C) + n] = acc[r];
-  }
-  __syncthreads();
-  for (int e = tid; e < HD_FR * 2 * C; e += HD_THREADS) lg[e] = (lgp[e] + lgp[HD_FR * 2 * C + e]) + bs[e % (2 * C)];
-}
-
-template <int C>
-__global__ __launch_bounds__(HD_THREADS) void head_fwd_kernel(
-    const float* __restrict__ x, const float* __restrict__ w /*(2C,256): dense rows then softmax rows*/,
-    const float* __restrict__ b /*(2C)*/, float* __restrict__ strong, float* __restrict__ sof_raw,
-    float* __restrict__ weak, float* __restrict__ den_out, float* __restrict__ part /*(B,S,2,C), S = gridDim.y > 1*/,
-    int T, int attention) {
-  extern __shared__ __align__(16) float smem[];
-  float* ws = smem;                          // [2C][257]
-  float* xs = ws + 2 * C * (HD_K + 1);       // [32][257]
-  float* lg = xs + HD_FR * (HD_K + 1);       // [32][2C]
-  float* bsm = lg + HD_FR * 2 * C;           // [2C]
-  float* sS = bsm + 2 * C;                   // [32][C]
-  float* sA = sS + HD_FR * C;                // [32][C]
-  float* lgp = sS;                           // [2][32][2C] K-half partials of head_logits: over sS | sA and 32*2C more
-  float* exS = sA + HD_FR * C;               // [32][C] exp(logit - max): the second half of lgp (dead after head_logits)
-  const int tid = threadIdx.x, b_ = blockIdx.x;
-  head_stage_rows<2 * C>(ws, w, 2 * C, tid);
-  if (tid < 2 * C) bsm[tid] = b[tid];
-  float num = 0.f, den = 0.f;
-  // the clip's frames are split over gridDim.y workgroups (whole 32-frame chunks each): one workgroup per clip left
-  // the chip at one 4-wave workgroup per CU with ~30 barriers in a row
-  const int S = gridDim.y, sp = blockIdx.y;
-  const int cps = ((T + HD_FR - 1) / HD_FR + S - 1) / S;
-  const int f_lo = sp * cps * HD_FR, f_hi = min(T, (sp + 1) * cps * HD_FR);
-  for (int f0 = f_lo; f0 < f_hi; f0 += HD_FR) {
-    __syncthreads();
-    head_stage_rows<HD_FR>(xs, x + ((size_t)b_ * T + f0) * HD_K, T - f0, tid);
-    __syncthreads();
-    head_logits<C>(xs, ws, bsm, lg, lgp, tid);   // (sS / sA of the previous chunk were consumed before the barrier above)
-    __syncthreads();
-    // sigmoid / softmax over the classes, one (frame, class) element per thread and round (one THREAD per frame walking
-    // its 20 classes -- 40 full-precision exponentials and 40 stores in a dependent chain on 32 of the 256 lanes -- was
-    // most of the kernel's time).  Same operations in the same order per element: max, exp, sum over c = 0..C-1, 1/sum.
-    float sv[(HD_FR * C + HD_THREADS - 1) / HD_THREADS];
-#pragma unroll
-    for (int u = 0; u < (HD_FR * C + HD_THREADS - 1) / HD_THREADS; ++u) {
-      const int e = tid + u * HD_THREADS;
-      if (e < HD_FR * C) {
-        const int f = e / C, c = e - f * C;
-        float mx = -3.0e38f;
-#pragma unroll
-        for (int cc = 0; cc < C; ++cc) mx = fmaxf(mx, lg[f * 2 * C + C + cc]);
-        exS[e] = expf(lg[f * 2 * C + C + c] - mx);
-        sv[u] = sigmoidf_(lg[f * 2 * C + c]);
-      }
-    }
-    __syncthreads();   // (also: every read of lgp's first half -- aliased by sS below -- is long done)
-#pragma unroll
-    for (int u = 0; u < (HD_FR * C + HD_THREADS - 1) / HD_THREADS; ++u) {
-      const int e = tid + u * HD_THREADS;
-      if (e < HD_FR * C) {
-        const int f = e / C;
-        const bool ok = f0 + f < T;
-        float se = 0.f;
-#pragma unroll
-        for (int cc = 0; cc < C; ++cc) se += exS[f * C + cc];
-        const float inv = 1.0f / se;
-        const float p = exS[e] * inv;
-        const float a = attention ? fminf(fmaxf(p, 1e-7f), 1.0f) : 1.0f;
-        sS[e] = ok ? sv[u] : 0.f;
-        sA[e] = ok ? a : 0.f;
-        if (ok) {
-          strong[((size_t)b_ * T + f0) * C + e] = sv[u];
-          sof_raw[((size_t)b_ * T + f0) * C + e] = p;
-        }
-      }
-    }
-    __syncthreads();
-    if (tid < C) {
-      for (int f = 0; f < HD_FR; ++f) {
-        num = fmaf(sS[f * C + tid], sA[f * C + tid], num);
-        den += sA[f * C + tid];
-      }
-    }
-  }
-  if (tid < C) {
-    if (S == 1) {
-      weak[(size_t)b_ * C + tid] = num / den;
-      den_out[(size_t)b_ * C + tid] = den;
-    } else {
-      part[(((size_t)b_ * S + sp) * 2 + 0) * C + tid] = num;
-      part[(((size_t)b_ * S + sp) * 2 + 1) * C + tid] = den;
-    }
-  }
-}
-
 // weak = sum_s num / sum_s den over the time splits of head_fwd_kernel (fixed order: repeatable)
 __global__ void head_weak_kernel(const float* __restrict__ part, float* __restrict__ weak, float* __restrict__ den_out,
                                  int B, int S, int C) {
@@ -203,33 +90,214 @@ __device__ __forceinline__ float bce_val(float s, float y) {
 }
 __device__ __forceinline__ float bce_grad(float s, float y) { return (s - y) / fmaxf((1.f - s) * s, 1e-12f); }
 
-template <int C>
-__global__ __launch_bounds__(HD_THREADS) void head_bwd_kernel(
+// ---------------------------------------------------------------------------------------------
+// One body per direction for every class count 1 .. BSED_HEAD_MAX_CLASSES ("Predictor head for any
+// class count"):
+//   CT  the class count where it is a compile-time constant (the 20 of the reference's bird list: head_fwd_kernel<20> and
+//       head_bwd_kernel<20>, whose loops over the classes unroll in full), else 0: C is then a kernel argument;
+//   NT  32-column MFMA tiles over the 2C logits, 32 (NT - 1) < 2C <= 32 NT: every register array is sized by CT or NT
+//       and indexed by unrolled loops only;
+//   WL  true: both heads' weights resident in LDS at pitch 257 (C <= 32, NT = 1, 2);
+//       false: C = 33 .. 64 (NT = 3, 4), where 2C rows of 257 floats no longer fit beside the frames (over 160 KB from
+//       C = 47): the weights stay in global memory (128 KB at C = 64, the same rows for every workgroup: L2-resident).
+// The arithmetic per element and its order are the same in every instance.
+// ---------------------------------------------------------------------------------------------
+// rows of HD_K floats, global -> LDS rows of HD_K + 1, for a run-time row count: four float4 loads in flight per thread
+__device__ __forceinline__ void head_stage_rows_n(float* dst, const float* __restrict__ src, int rows, int tid) {
+  const int nv = rows * (HD_K / 4);
+  for (int e0 = tid; e0 < nv; e0 += 4 * HD_THREADS) {
+    float4 v[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int e = e0 + u * HD_THREADS;
+      v[u] = e < nv ? *reinterpret_cast<const float4*>(src + (size_t)e * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int e = e0 + u * HD_THREADS;
+      if (e < nv) {
+        float* d = dst + (e / (HD_K / 4)) * (HD_K + 1) + 4 * (e % (HD_K / 4));
+        d[0] = v[u].x; d[1] = v[u].y; d[2] = v[u].z; d[3] = v[u].w;
+      }
+    }
+  }
+}
+
+// logits for a chunk of frames: lg[f][0..C) dense head, lg[f][C..2C) softmax head.
+// The (32 frames x 2C) x 256 contraction runs on v_mfma_f32_32x32x2_f32 (f32 operands, exact fp32 products and sums): with
+// scalar FMAs every multiply-add paid an LDS read of the weight (1.2 reads per FMA: the kernel was LDS-bound).  Wave w
+// takes the column tiles w & 1, (w & 1) + 2, .. below NT (classes 32 nt ..; columns beyond 2C compute on a clamped weight
+// row and are dropped) and the K half w >> 1; the two K halves meet in LDS.  Operands: one dword per lane and MFMA,
+// conflict-free (pitch 257).
+// WL = false: the weight operand comes from global memory, a tile's 32 rows x 128 K at a time in 64 registers per lane by
+// 16-byte loads; lane half lh of MFMA step 4 g + j then takes k = 8 g + 4 lh + j, and the frames follow that permutation.
+template <int CT, int NT, bool WL>
+__device__ __forceinline__ void head_logits(const float* xs /*[HD_FR][HD_K+1]*/,
+                                            const float* ws /*WL: LDS [2C][HD_K+1]; else global (2C,HD_K)*/,
+                                            const float* bs /*[2C]*/, float* lg /*[HD_FR][2C]*/,
+                                            float* lgp /*[2][HD_FR][2C] scratch*/, int c_rt, int tid) {
+  const int C = CT ? CT : c_rt;
+  const int wave = tid >> 6, lane = tid & 63, li = lane & 31, lh = lane >> 5;
+  const int kh = wave >> 1;
+#pragma unroll
+  for (int i = 0; i < (NT + 1) / 2; ++i) {
+    const int nt = (wave & 1) + 2 * i;
+    if (NT % 2 != 0 && nt >= NT) break;   // an odd tile count leaves the odd waves one tile short
+    const int n = 32 * nt + li;
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    if constexpr (WL) {
+      const float* ap = xs + li * (HD_K + 1) + (HD_K / 2) * kh + lh;
+      const float* bp = ws + min(n, 2 * C - 1) * (HD_K + 1) + (HD_K / 2) * kh + lh;
+#pragma unroll 8
+      for (int s = 0; s < HD_K / 4; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[2 * s], bp[2 * s], acc, 0, 0, 0);
+    } else {
+      const float* ap = xs + li * (HD_K + 1) + (HD_K / 2) * kh + 4 * lh;
+      const float* bp = ws + (size_t)min(n, 2 * C - 1) * HD_K + (HD_K / 2) * kh + 4 * lh;
+      f32x4 bv[HD_K / 16];
+#pragma unroll
+      for (int g = 0; g < HD_K / 16; ++g) bv[g] = *reinterpret_cast<const f32x4*>(bp + 8 * g);
+#pragma unroll
+      for (int g = 0; g < HD_K / 16; ++g)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[8 * g + j], bv[g][j], acc, 0, 0, 0);
+    }
+    if (n < 2 * C) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) lgp[(kh * HD_FR + hd_crow(r, lh)) * (2 * C) + n] = acc[r];
+    }
+  }
+  __syncthreads();
+  for (int e = tid; e < HD_FR * 2 * C; e += HD_THREADS) lg[e] = (lgp[e] + lgp[HD_FR * 2 * C + e]) + bs[e % (2 * C)];
+}
+
+template <int CT, int NT, bool WL>
+__device__ __forceinline__ void head_fwd_body(
+    const float* __restrict__ x, const float* __restrict__ w /*(2C,256): dense rows then softmax rows*/,
+    const float* __restrict__ b /*(2C)*/, float* __restrict__ strong, float* __restrict__ sof_raw,
+    float* __restrict__ weak, float* __restrict__ den_out, float* __restrict__ part /*(B,S,2,C), S = gridDim.y > 1*/,
+    int T, int c_rt, int attention) {
+  extern __shared__ __align__(16) float smem[];
+  const int C = CT ? CT : c_rt;
+  constexpr int UNR_C = CT ? CT : 4;   // loops over the classes: unrolled in full for a compile-time count
+  float* ws = smem;                                   // WL: [2C][257]
+  float* xs = ws + (WL ? 2 * C * (HD_K + 1) : 0);     // [32][257]
+  float* lg = xs + HD_FR * (HD_K + 1);                // [32][2C]
+  float* bsm = lg + HD_FR * 2 * C;                    // [2C]
+  float* sS = bsm + 2 * C;                            // [32][C]
+  float* sA = sS + HD_FR * C;                         // [32][C]
+  float* lgp = sS;                                    // [2][32][2C] K-half partials of head_logits: over sS | sA and 32*2C more
+  float* exS = sA + HD_FR * C;                        // [32][C] exp(logit - max): the second half of lgp (dead after head_logits)
+  const int tid = threadIdx.x, b_ = blockIdx.x;
+  if constexpr (WL) {
+    if constexpr (CT != 0) head_stage_rows<2 * CT>(ws, w, 2 * CT, tid);
+    else head_stage_rows_n(ws, w, 2 * C, tid);
+  }
+  if (tid < 2 * C) bsm[tid] = b[tid];
+  float num = 0.f, den = 0.f;
+  // the clip's frames are split over gridDim.y workgroups (whole 32-frame chunks each): one workgroup per clip left
+  // the chip at one 4-wave workgroup per CU with ~30 barriers in a row
+  const int S = gridDim.y, sp = blockIdx.y;
+  const int cps = ((T + HD_FR - 1) / HD_FR + S - 1) / S;
+  const int f_lo = sp * cps * HD_FR, f_hi = min(T, (sp + 1) * cps * HD_FR);
+  // (frame, class) elements per thread, 32 C <= 256 ROUNDS
+  constexpr int ROUNDS = CT ? (HD_FR * CT + HD_THREADS - 1) / HD_THREADS : HD_FR * 16 * NT / HD_THREADS;
+  for (int f0 = f_lo; f0 < f_hi; f0 += HD_FR) {
+    __syncthreads();
+    head_stage_rows<HD_FR>(xs, x + ((size_t)b_ * T + f0) * HD_K, T - f0, tid);
+    __syncthreads();
+    // (sS / sA of the previous chunk were consumed before the barrier above)
+    head_logits<CT, NT, WL>(xs, WL ? ws : w, bsm, lg, lgp, C, tid);
+    __syncthreads();
+    // sigmoid / softmax over the classes, one (frame, class) element per thread and round (one THREAD per frame walking
+    // its 20 classes -- 40 full-precision exponentials and 40 stores in a dependent chain on 32 of the 256 lanes -- was
+    // most of the kernel's time).  Same operations in the same order per element: max, exp, sum over c = 0..C-1, 1/sum.
+    float sv[ROUNDS];
+#pragma unroll
+    for (int u = 0; u < ROUNDS; ++u) {
+      const int e = tid + u * HD_THREADS;
+      if (e < HD_FR * C) {
+        const int f = e / C, c = e - f * C;
+        float mx = -3.0e38f;
+#pragma unroll UNR_C
+        for (int cc = 0; cc < C; ++cc) mx = fmaxf(mx, lg[f * 2 * C + C + cc]);
+        exS[e] = expf(lg[f * 2 * C + C + c] - mx);
+        sv[u] = sigmoidf_(lg[f * 2 * C + c]);
+      }
+    }
+    __syncthreads();   // (also: every read of lgp's first half -- aliased by sS below -- is long done)
+#pragma unroll
+    for (int u = 0; u < ROUNDS; ++u) {
+      const int e = tid + u * HD_THREADS;
+      if (e < HD_FR * C) {
+        const int f = e / C;
+        const bool ok = f0 + f < T;
+        float se = 0.f;
+#pragma unroll UNR_C
+        for (int cc = 0; cc < C; ++cc) se += exS[f * C + cc];
+        const float inv = 1.0f / se;
+        const float p = exS[e] * inv;
+        const float a = attention ? fminf(fmaxf(p, 1e-7f), 1.0f) : 1.0f;
+        sS[e] = ok ? sv[u] : 0.f;
+        sA[e] = ok ? a : 0.f;
+        if (ok) {
+          strong[((size_t)b_ * T + f0) * C + e] = sv[u];
+          sof_raw[((size_t)b_ * T + f0) * C + e] = p;
+        }
+      }
+    }
+    __syncthreads();
+    if (tid < C) {
+      for (int f = 0; f < HD_FR; ++f) {
+        num = fmaf(sS[f * C + tid], sA[f * C + tid], num);
+        den += sA[f * C + tid];
+      }
+    }
+  }
+  if (tid < C) {
+    if (S == 1) {
+      weak[(size_t)b_ * C + tid] = num / den;
+      den_out[(size_t)b_ * C + tid] = den;
+    } else {
+      part[(((size_t)b_ * S + sp) * 2 + 0) * C + tid] = num;
+      part[(((size_t)b_ * S + sp) * 2 + 1) * C + tid] = den;
+    }
+  }
+}
+
+template <int CT, int NT, bool WL>
+__device__ __forceinline__ void head_bwd_body(
     const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ strong,
     const float* __restrict__ sof_raw, const float* __restrict__ weak, const float* __restrict__ den,
     const float* __restrict__ y_strong, const float* __restrict__ y_weak, const float* __restrict__ ema_strong,
     const float* __restrict__ ema_weak, const float* __restrict__ ema_strong2, const float* __restrict__ g_strong_ext,
     const float* __restrict__ g_weak_ext, float w_strong, float w_weak, float w_cons_s, float w_cons_w,
     float w_cons_s2, float inv_n_strong, float inv_n_weak,
-    float* __restrict__ dx, float* __restrict__ dw_part /*(B,2C,256)*/, float* __restrict__ db_part /*(B,2C)*/,
-    float* __restrict__ loss_part /*(B,4)*/, int T, int attention) {
+    float* __restrict__ dx, float* __restrict__ dw_part /*(B*S,2C,256)*/, float* __restrict__ db_part /*(B*S,2C)*/,
+    float* __restrict__ loss_part /*(B*S,6)*/, int T, int c_rt, int attention) {
   extern __shared__ __align__(16) float smem[];
-  float* ws = smem;                          // [2C][257]
-  float* xs = ws + 2 * C * (HD_K + 1);       // [32][257]
-  float* dl = xs + HD_FR * (HD_K + 1);       // [32][2C]
-  float* gwk = dl + HD_FR * 2 * C;           // [C] d loss / d weak
-  float* wk = gwk + C;                       // [C]
-  float* dn = wk + C;                        // [C]
-  float* lred = dn + C;                      // [HD_THREADS]
-  float* gaS = lred + HD_THREADS;            // [32][C] attention-path gradient of the softmax output
-  float* paS = gaS + HD_FR * C;              // [32][C] softmax output
+  const int C = CT ? CT : c_rt;
+  constexpr int UNR_C = CT ? CT : 4;   // loops over the classes: unrolled in full for a compile-time count
+  float* ws = smem;                                   // WL: [2C][257]
+  float* xs = ws + (WL ? 2 * C * (HD_K + 1) : 0);     // [32][257]
+  float* dl = xs + HD_FR * (HD_K + 1);                // [32][2C]
+  float* gwk = dl + HD_FR * 2 * C;                    // [C] d loss / d weak
+  float* wk = gwk + C;                                // [C]
+  float* dn = wk + C;                                 // [C]
+  float* lred = dn + C;                               // [HD_THREADS]
+  float* gaS = lred + HD_THREADS;                     // [32][C]
+  float* paS = gaS + HD_FR * C;                       // [32][C]
   const int tid = threadIdx.x, b_ = blockIdx.x;
-  // time splits as in head_fwd_kernel; partial outputs (dW, db, losses) get one row per (clip, split)
+  // time splits as in head_fwd_body; partial outputs (dW, db, losses) get one row per (clip, split)
   const int S = gridDim.y, sp = blockIdx.y;
   const int cps = ((T + HD_FR - 1) / HD_FR + S - 1) / S;
   const int f_lo = sp * cps * HD_FR, f_hi = min(T, (sp + 1) * cps * HD_FR);
   const size_t prow = (size_t)b_ * S + sp;
-  head_stage_rows<2 * C>(ws, w, 2 * C, tid);
+  if constexpr (WL) {
+    if constexpr (CT != 0) head_stage_rows<2 * CT>(ws, w, 2 * CT, tid);
+    else head_stage_rows_n(ws, w, 2 * C, tid);
+  }
   float l_s = 0.f, l_w = 0.f, l_cs = 0.f, l_cw = 0.f, l_cs2 = 0.f;
   if (tid < C) {
     const float wv = weak[(size_t)b_ * C + tid];
@@ -251,13 +319,17 @@ __global__ __launch_bounds__(HD_THREADS) void head_bwd_kernel(
   }
   // The three contractions of the chunk loop run on v_mfma_f32_32x32x2_f32 (f32 operands: exact fp32, like the scalar
   // FMAs they replace, which paid one or two LDS reads per multiply-add).  Wave w owns columns 64 w .. 64 w + 63 of K:
-  //   dx[f][k]  = sum_c dl[f][c] W[c][k]        32 frames x 64 columns, 2C / 2 steps
-  //   dW[c][k] += sum_f dl[f][c] x[f][k]        2 x 32 class rows (rows >= 2C idle) x 64 columns, 16 steps;
-  //                                             the four 32 x 32 accumulators live across the chunks
+  //   dx[f][k]  = sum_c dl[f][c] W[c][k]        32 frames x 64 columns, 2C / 2 steps (WL = false: W rows from global
+  //                                             memory, read along K)
+  //   dW[c][k] += sum_f dl[f][c] x[f][k]        NT x 32 class rows (rows >= 2C idle) x 64 columns, 16 steps;
+  //                                             the 2 NT accumulators of 32 x 32 live across the chunks (128 registers
+  //                                             per lane at NT = 4, which one wave per SIMD has)
   const int wave = tid >> 6, lane = tid & 63, li = lane & 31, lh = lane >> 5;
-  f32x16 dwa[2][2];
+  constexpr int WP = WL ? HD_K + 1 : HD_K;             // pitch of the weight rows the dx contraction reads
+  const float* wsrc = WL ? ws : w;
+  f32x16 dwa[NT][2];
 #pragma unroll
-  for (int mt = 0; mt < 2; ++mt)
+  for (int mt = 0; mt < NT; ++mt)
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -309,21 +381,22 @@ __global__ __launch_bounds__(HD_THREADS) void head_bwd_kernel(
     for (int e = tid; e < HD_FR * C; e += HD_THREADS) {
       const int f = e / C;
       float dot = 0.f;
-#pragma unroll
+#pragma unroll UNR_C
       for (int cc = 0; cc < C; ++cc) dot = fmaf(gaS[f * C + cc], paS[f * C + cc], dot);
       dl[f * 2 * C + C + (e - f * C)] = paS[e] * (gaS[e] - dot);
     }
     __syncthreads();
     {
+      constexpr int UNR_DX = CT ? 4 : 1;   // (a run-time trip count around an MFMA is not unrolled: no remainder loop)
       f32x16 dxa[2];
 #pragma unroll
       for (int j = 0; j < 2; ++j)
 #pragma unroll
         for (int r = 0; r < 16; ++r) dxa[j][r] = 0.f;
-#pragma unroll 4
+#pragma unroll UNR_DX
       for (int st = 0; st < C; ++st) {   // class c = 2 st + lh
         const float av = dl[li * 2 * C + 2 * st + lh];
-        const float* wr = ws + (2 * st + lh) * (HD_K + 1) + 64 * wave + li;
+        const float* wr = wsrc + (2 * st + lh) * WP + 64 * wave + li;
         dxa[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, wr[0], dxa[0], 0, 0, 0);
         dxa[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, wr[32], dxa[1], 0, 0, 0);
       }
@@ -340,19 +413,22 @@ __global__ __launch_bounds__(HD_THREADS) void head_bwd_kernel(
 #pragma unroll 4
     for (int st = 0; st < HD_FR / 2; ++st) {   // frame f = 2 st + lh (frames past T hold dl = 0)
       const int f = 2 * st + lh;
-      const float a0 = dl[f * 2 * C + li], a1 = dl[f * 2 * C + min(32 + li, 2 * C - 1)];
+      float a[NT];   // class rows 32 mt + li; rows >= 2C compute on a clamped column and are dropped
+#pragma unroll
+      for (int mt = 0; mt < NT; ++mt) a[mt] = dl[f * 2 * C + min(32 * mt + li, 2 * C - 1)];
       const float* xr = xs + f * (HD_K + 1) + 64 * wave + li;
       const float b0 = xr[0], b1 = xr[32];
-      dwa[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, dwa[0][0], 0, 0, 0);
-      dwa[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, dwa[0][1], 0, 0, 0);
-      dwa[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, dwa[1][0], 0, 0, 0);
-      dwa[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, dwa[1][1], 0, 0, 0);
+#pragma unroll
+      for (int mt = 0; mt < NT; ++mt) {
+        dwa[mt][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[mt], b0, dwa[mt][0], 0, 0, 0);
+        dwa[mt][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[mt], b1, dwa[mt][1], 0, 0, 0);
+      }
     }
     if (tid < 2 * C)
       for (int f = 0; f < HD_FR; ++f) dbacc += dl[f * 2 * C + tid];
   }
 #pragma unroll
-  for (int mt = 0; mt < 2; ++mt)
+  for (int mt = 0; mt < NT; ++mt)
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -372,6 +448,43 @@ __global__ __launch_bounds__(HD_THREADS) void head_bwd_kernel(
   }
   __syncthreads();
   if (tid < 6) loss_part[prow * 6 + tid] = tid < 5 ? ((lred[tid] + lred[8 + tid]) + lred[16 + tid]) + lred[24 + tid] : 0.f;
+}
+
+// head_fwd_kernel<20> / head_bwd_kernel<20>: the class count of the reference's bird list at compile time, as before
+// the head took other counts; head_*_n_kernel<NT, WL>: every other count, C an argument.
+template <int C>
+__global__ __launch_bounds__(HD_THREADS) void head_fwd_kernel(
+    const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b, float* __restrict__ strong,
+    float* __restrict__ sof_raw, float* __restrict__ weak, float* __restrict__ den_out, float* __restrict__ part, int T,
+    int attention) {
+  head_fwd_body<C, (2 * C + 31) / 32, true>(x, w, b, strong, sof_raw, weak, den_out, part, T, C, attention);
+}
+template <int NT, bool WL>
+__global__ __launch_bounds__(HD_THREADS) void head_fwd_n_kernel(
+    const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b, float* __restrict__ strong,
+    float* __restrict__ sof_raw, float* __restrict__ weak, float* __restrict__ den_out, float* __restrict__ part, int T,
+    int C, int attention) {
+  head_fwd_body<0, NT, WL>(x, w, b, strong, sof_raw, weak, den_out, part, T, C, attention);
+}
+
+#define HD_BWD_PARAMS                                                                                                    \
+  const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ strong,                            \
+      const float* __restrict__ sof_raw, const float* __restrict__ weak, const float* __restrict__ den,                  \
+      const float* __restrict__ y_strong, const float* __restrict__ y_weak, const float* __restrict__ ema_strong,        \
+      const float* __restrict__ ema_weak, const float* __restrict__ ema_strong2, const float* __restrict__ g_strong_ext, \
+      const float* __restrict__ g_weak_ext, float w_strong, float w_weak, float w_cons_s, float w_cons_w,                \
+      float w_cons_s2, float inv_n_strong, float inv_n_weak, float* __restrict__ dx, float* __restrict__ dw_part,        \
+      float* __restrict__ db_part, float* __restrict__ loss_part
+#define HD_BWD_ARGS                                                                                                      \
+  x, w, strong, sof_raw, weak, den, y_strong, y_weak, ema_strong, ema_weak, ema_strong2, g_strong_ext, g_weak_ext,       \
+      w_strong, w_weak, w_cons_s, w_cons_w, w_cons_s2, inv_n_strong, inv_n_weak, dx, dw_part, db_part, loss_part
+template <int C>
+__global__ __launch_bounds__(HD_THREADS) void head_bwd_kernel(HD_BWD_PARAMS, int T, int attention) {
+  head_bwd_body<C, (2 * C + 31) / 32, true>(HD_BWD_ARGS, T, C, attention);
+}
+template <int NT, bool WL>
+__global__ __launch_bounds__(HD_THREADS) void head_bwd_n_kernel(HD_BWD_PARAMS, int T, int C, int attention) {
+  head_bwd_body<0, NT, WL>(HD_BWD_ARGS, T, C, attention);
 }
 
 // Event post-processing of get_predictions (reference src/evaluation_measures.py:188-205): binarise at `threshold`, then
@@ -484,19 +597,47 @@ extern "C" int bsed_head_splits(int B, int T) {
   return S;
 }
 
+// dynamic LDS of the launch for C classes (host only, no HIP call).  Up to HD_LDS_MAXC classes both heads' weights are
+// resident; above, the weight operand comes from global memory (WL = false)
+#define HD_LDS_MAXC 32
+extern "C" int bsed_head_lds_bytes(int C, int backward) {
+  if (C < 1 || C > BSED_HEAD_MAX_CLASSES) return -1;
+  const int resident = C <= HD_LDS_MAXC ? 2 * C * (HD_K + 1) : 0;
+  const int frames = HD_FR * (HD_K + 1) + HD_FR * 2 * C;    // xs, then lg (forward) or dl (backward)
+  return (resident + frames + (backward ? 3 * C + HD_THREADS + 2 * HD_FR * C : 2 * C + 2 * HD_FR * 2 * C)) * 4;
+}
+
+template <int NT, bool WL>
+static int head_fwd_n_launch(const float* x, const float* w, const float* b, float* strong, float* sof_raw, float* weak,
+                             float* den, float* part, int B, int S, int T, int C, int attention, hipStream_t stream) {
+  static BsedLdsOnce once;
+  BSED_HIP(bsed_max_lds(once, (const void*)head_fwd_n_kernel<NT, WL>));
+  hipLaunchKernelGGL((head_fwd_n_kernel<NT, WL>), dim3(B, S), dim3(HD_THREADS), (size_t)bsed_head_lds_bytes(C, 0), stream,
+                     x, w, b, strong, sof_raw, weak, den, part, T, C, attention);
+  return BSED_OK;
+}
+
 extern "C" int bsed_head_fwd(const float* x, const float* w, const float* b, float* strong, float* sof_raw,
                              float* weak, float* den, float* part, int B, int T, int K, int C, int attention,
                              void* stream) {
   BSED_CHECK_ARG(x && w && b && strong && sof_raw && weak && den, "bsed_head_fwd: null tensor");
+  BSED_CHECK_ARG(B > 0 && T > 0, "bsed_head_fwd: bad shape");
+  BSED_CHECK_ARG(K == HD_K && C >= 1 && C <= BSED_HEAD_MAX_CLASSES,
+                 "bsed_head_fwd: built for K=256 and 1 <= nclass <= %d (got K=%d, nclass=%d)", BSED_HEAD_MAX_CLASSES, K, C);
   const int S = bsed_head_splits(B, T);
   BSED_CHECK_ARG(S == 1 || part, "bsed_head_fwd: %d time splits need the (B,%d,2,C) scratch buffer", S, S);
-  BSED_CHECK_ARG(B > 0 && T > 0, "bsed_head_fwd: bad shape");
-  BSED_CHECK_ARG(K == HD_K && C == 20, "bsed_head_fwd: built for K=256, nclass=20 (got %d, %d)", K, C);
-  const size_t smem = (size_t)(2 * C * (HD_K + 1) + HD_FR * (HD_K + 1) + HD_FR * 2 * C + 2 * C + 2 * HD_FR * 2 * C) * 4;
-  static BsedLdsOnce once;
-  BSED_HIP(bsed_max_lds(once, (const void*)head_fwd_kernel<20>));
-  hipLaunchKernelGGL(head_fwd_kernel<20>, dim3(B, S), dim3(HD_THREADS), smem, (hipStream_t)stream, x, w, b, strong,
-                     sof_raw, weak, den, part, T, attention);
+  if (C == 20) {
+    static BsedLdsOnce once;
+    BSED_HIP(bsed_max_lds(once, (const void*)head_fwd_kernel<20>));
+    hipLaunchKernelGGL(head_fwd_kernel<20>, dim3(B, S), dim3(HD_THREADS), (size_t)bsed_head_lds_bytes(20, 0),
+                       (hipStream_t)stream, x, w, b, strong, sof_raw, weak, den, part, T, attention);
+  } else {
+    // two ranges: weights in LDS (one or two column tiles over 2C), weights from L2 (three or four)
+    const auto launch = C <= HD_LDS_MAXC ? (C <= 16 ? head_fwd_n_launch<1, true> : head_fwd_n_launch<2, true>)
+                                         : (C <= 48 ? head_fwd_n_launch<3, false> : head_fwd_n_launch<4, false>);
+    const int rc = launch(x, w, b, strong, sof_raw, weak, den, part, B, S, T, C, attention, (hipStream_t)stream);
+    if (rc != BSED_OK) return rc;
+  }
   if (S > 1)
     hipLaunchKernelGGL(head_weak_kernel, dim3((B * C + 255) / 256), dim3(256), 0, (hipStream_t)stream, part, weak, den, B,
                        S, C);
@@ -504,21 +645,42 @@ extern "C" int bsed_head_fwd(const float* x, const float* w, const float* b, flo
   return BSED_OK;
 }
 
+template <int NT, bool WL>
+static int head_bwd_n_launch(const BsedHeadBwdDesc* d, hipStream_t stream) {
+  static BsedLdsOnce once;
+  BSED_HIP(bsed_max_lds(once, (const void*)head_bwd_n_kernel<NT, WL>));
+  hipLaunchKernelGGL((head_bwd_n_kernel<NT, WL>), dim3(d->B, bsed_head_splits(d->B, d->T)), dim3(HD_THREADS),
+                     (size_t)bsed_head_lds_bytes(d->C, 1), stream, d->x, d->w, d->strong, d->sof_raw, d->weak, d->den,
+                     d->y_strong, d->y_weak, d->ema_strong, d->ema_weak, d->ema_strong2, d->g_strong_ext, d->g_weak_ext,
+                     d->w_strong, d->w_weak, d->w_cons_s, d->w_cons_w, d->w_cons_s2, d->inv_n_strong, d->inv_n_weak,
+                     d->dx, d->dw_part, d->db_part, d->loss_part, d->T, d->C, d->attention);
+  return BSED_OK;
+}
+
 extern "C" int bsed_head_bwd(const BsedHeadBwdDesc* d, void* stream) {
   BSED_CHECK_ARG(d, "bsed_head_bwd: null descriptor");
   BSED_CHECK_ARG(d->x && d->w && d->strong && d->sof_raw && d->weak && d->den && d->dx && d->dw_part && d->db_part &&
                      d->loss_part, "bsed_head_bwd: null tensor");
-  BSED_CHECK_ARG(d->B > 0 && d->T > 0 && d->K == HD_K && d->C == 20, "bsed_head_bwd: built for K=256, nclass=20");
-  const int C = 20;
-  const size_t smem = (size_t)(2 * C * (HD_K + 1) + HD_FR * (HD_K + 1) + HD_FR * 2 * C + 3 * C + HD_THREADS + 2 * HD_FR * C) * 4;
-  static BsedLdsOnce once;
-  BSED_HIP(bsed_max_lds(once, (const void*)head_bwd_kernel<20>));
-  hipLaunchKernelGGL(head_bwd_kernel<20>, dim3(d->B, bsed_head_splits(d->B, d->T)), dim3(HD_THREADS), smem,
-                     (hipStream_t)stream, d->x, d->w,
-                     d->strong, d->sof_raw, d->weak, d->den, d->y_strong, d->y_weak, d->ema_strong, d->ema_weak,
-                     d->ema_strong2, d->g_strong_ext, d->g_weak_ext, d->w_strong, d->w_weak, d->w_cons_s, d->w_cons_w,
-                     d->w_cons_s2, d->inv_n_strong, d->inv_n_weak, d->dx, d->dw_part, d->db_part, d->loss_part, d->T,
-                     d->attention);
+  BSED_CHECK_ARG(d->B > 0 && d->T > 0, "bsed_head_bwd: bad shape");
+  BSED_CHECK_ARG(d->K == HD_K && d->C >= 1 && d->C <= BSED_HEAD_MAX_CLASSES,
+                 "bsed_head_bwd: built for K=256 and 1 <= nclass <= %d (got K=%d, nclass=%d)", BSED_HEAD_MAX_CLASSES, d->K,
+                 d->C);
+  const int C = d->C;
+  if (C == 20) {
+    static BsedLdsOnce once;
+    BSED_HIP(bsed_max_lds(once, (const void*)head_bwd_kernel<20>));
+    hipLaunchKernelGGL(head_bwd_kernel<20>, dim3(d->B, bsed_head_splits(d->B, d->T)), dim3(HD_THREADS),
+                       (size_t)bsed_head_lds_bytes(20, 1), (hipStream_t)stream, d->x, d->w,
+                       d->strong, d->sof_raw, d->weak, d->den, d->y_strong, d->y_weak, d->ema_strong, d->ema_weak,
+                       d->ema_strong2, d->g_strong_ext, d->g_weak_ext, d->w_strong, d->w_weak, d->w_cons_s, d->w_cons_w,
+                       d->w_cons_s2, d->inv_n_strong, d->inv_n_weak, d->dx, d->dw_part, d->db_part, d->loss_part, d->T,
+                       d->attention);
+  } else {
+    const auto launch = C <= HD_LDS_MAXC ? (C <= 16 ? head_bwd_n_launch<1, true> : head_bwd_n_launch<2, true>)
+                                         : (C <= 48 ? head_bwd_n_launch<3, false> : head_bwd_n_launch<4, false>);
+    const int rc = launch(d, (hipStream_t)stream);
+    if (rc != BSED_OK) return rc;
+  }
   BSED_LAUNCH_CHECK();
   return BSED_OK;
 }

@@ -14,7 +14,8 @@ Differences that are deliberate:
   * dropout masks come from a counter RNG (Philox) keyed on ``(seed, layer)``: forward and backward
     regenerate them instead of storing them.  Call ``set_seed(step)`` per step.
 Only the hot-path configuration is built: GLU activation, 3x3/stride-1/pad-1 convs, BGRU with 128 cells
-and 2 layers, 20 classes; anything else raises NotImplementedError (no silent fallback).
+and 2 layers, 1 to 64 classes (``Predictor.MAX_CLASSES``, the library's BSED_HEAD_MAX_CLASSES); anything else raises
+NotImplementedError (no silent fallback).
 """
 import math
 import re
@@ -867,10 +868,13 @@ class _CRNNFunction(torch.autograd.Function):
 
 
 class Predictor(_FlatModule):
+    MAX_CLASSES = L.CONSTANTS["BSED_HEAD_MAX_CLASSES"]     # the species list: any length the head kernels are built for
+
     def __init__(self, nclass, attention=False, n_RNN_cell=64, device="cuda", **kwargs):
         super().__init__()
         L._require_gpu()
-        _check_cfg(nclass == 20 and n_RNN_cell == 128, "nclass=20, n_RNN_cell=128")
+        _check_cfg(1 <= nclass <= self.MAX_CLASSES and n_RNN_cell == 128,
+                   f"1 <= nclass <= {self.MAX_CLASSES} (got {nclass}), n_RNN_cell=128")
         self.attention, self.nclass, self.K = attention, nclass, 2 * n_RNN_cell
         # dense / dense_softmax rows are adjacent: one (2C, K) matrix for the fused head kernel
         pspecs = [("dense.weight", (nclass, self.K)), ("dense_softmax.weight", (nclass, self.K)),

@@ -895,6 +895,14 @@ def max_over_time(y):
     return out
 
 
+def _head_kernel(direction, C):
+    """the instance bsed_head_fwd / bsed_head_bwd launch for C classes (csrc/head.hip): the 20-class build, or NT tiles
+    of 32 columns over the 2C logits with the weights in LDS (C <= 32) or read from L2 (33..64)"""
+    if C == 20:
+        return f"head_{direction}_kernel<20>"
+    return f"head_{direction}_n_kernel<{(2 * C + 31) // 32},{'lds' if C <= 32 else 'l2'}>"
+
+
 def head_fwd(x, w, b, B, T, K, C, attention):
     dev = x.device
     strong = torch.empty((B, T, C), device=dev, dtype=torch.float32)
@@ -903,7 +911,7 @@ def head_fwd(x, w, b, B, T, K, C, attention):
     den = torch.empty((B, C), device=dev, dtype=torch.float32)
     S = L.lib().bsed_head_splits(B, T)
     part = torch.empty((B, S, 2, C), device=dev, dtype=torch.float32) if S > 1 else None
-    _note(f"head_fwd_kernel<{C}>", f"T{T}", 2.0 * B * T * K * 2 * C, 4.0 * B * T * (K + 2 * C))
+    _note(_head_kernel("fwd", C), f"T{T}", 2.0 * B * T * K * 2 * C, 4.0 * B * T * (K + 2 * C))
     L.call("bsed_head_fwd", L.ptr(x), _dp(w), _dp(b), L.ptr(strong), L.ptr(sof), L.ptr(weak), L.ptr(den), L.ptr(part),
            B, T, K, C, 1 if attention else 0, L.stream())
     return strong, sof, weak, den
@@ -929,7 +937,7 @@ def head_bwd(x, w, strong, sof, weak, den, B, T, K, C, attention, y_strong=None,
     d.inv_n_weak = 1.0 / (n_weak if n_weak else B * C)
     d.dx = _p(dx); d.dw_part = _p(dw_part); d.db_part = _p(db_part); d.loss_part = _p(loss_part)
     d.B, d.T, d.K, d.C, d.attention = B, T, K, C, 1 if attention else 0
-    _note(f"head_bwd_kernel<{C}>", f"T{T}", 3 * 2.0 * B * T * K * 2 * C, 4.0 * B * T * (2 * K + 4 * C))
+    _note(_head_kernel("bwd", C), f"T{T}", 3 * 2.0 * B * T * K * 2 * C, 4.0 * B * T * (2 * K + 4 * C))
     L.call("bsed_head_bwd", ctypes.byref(d), L.stream())
     return dx, dw_part, db_part, loss_part
 

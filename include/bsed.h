@@ -441,6 +441,11 @@ int bsed_max_over_time(const float* y, float* out, int B, int T, int C, void* st
  * (B,S,2,C) scratch buffer `part` when S > 1; bsed_head_bwd writes S rows per clip into its partial outputs
  * (dw_part (B*S,2C,K), db_part (B*S,2C), loss_part (B*S,6)): sum over the leading dimension as before. */
 int bsed_head_splits(int B, int T);
+/* K = 256 and 1 <= C <= BSED_HEAD_MAX_CLASSES (ABI 8; the width of the label set that bsed_tag_masks fixes): anything
+ * else is BSED_ERR_ARG before any HIP call, here and in bsed_head_bwd.  bsed_head_lds_bytes: the dynamic LDS in bytes
+ * that the forward (backward = 0) or backward launch for C classes requests, negative for an unsupported C; host only. */
+#define BSED_HEAD_MAX_CLASSES 64
+int bsed_head_lds_bytes(int C, int backward);
 int bsed_head_fwd(const float* x, const float* w, const float* b, float* strong, float* sof_raw, float* weak,
                   float* den, float* part, int B, int T, int K, int C, int attention, void* stream);
 
