@@ -233,72 +233,77 @@ __global__ __launch_bounds__(256) void s2d_bwd_kernel(const float* __restrict__ 
   }
 }
 
-// tail of the discriminator for one sample per thread: y5 (N,H5,W5,8) -> BN + LeakyReLU -> AdaptiveAvgPool over the
-// feature axis (W5 = 7 -> bins [0,4), [3,7)) and all of time -> Linear(16,1) -> sigmoid -> BCE(label_n), and back.
-__global__ void disc_head_kernel(const float* __restrict__ y5, const float* __restrict__ scale,
-                                 const float* __restrict__ shift, const float* __restrict__ wl, const float* __restrict__ bl,
-                                 int N, int Ns, int H5, int W5, int train, float* __restrict__ d_out,
-                                 float* __restrict__ g5, float* __restrict__ stats /*(N,2,8)*/,
-                                 float* __restrict__ dwl_part /*(N,2,16)*/, float* __restrict__ dbl_part /*(N,2,1)*/,
-                                 float* __restrict__ loss_part /*(N,2,1)*/) {
-  const int n = blockIdx.x * blockDim.x + threadIdx.x;
-  if (n >= N) return;
+// tail of the discriminator, one clip per 8 lanes (lane = channel): y5 (N,H5,W5,8) -> BN + LeakyReLU -> AdaptiveAvgPool
+// over the feature axis (W5 = 7 -> bins [0,4), [3,7)) and all of time -> Linear(16,1) -> sigmoid -> BCE(label_n), and back.
+// All arithmetic is double, each output rounded to fp32 once: in fp32 the logit's rounding alone (1.6 ulp of z = -3.7
+// is 4.9 ulp of d = 0.02) put single-clip outputs outside 4 ulp of a float64 evaluation
+// (tests/test_disc_kernels_gpu.py).  The kernel is latency-bound (H5*W5 values per lane); a lane per channel instead of
+// a thread per clip pays for the double arithmetic.  The LeakyReLU branch is unchanged by it: the fp32 product y*scale
+// is exact in double, and rounding y*scale + shift to double or (fmaf) to fp32 gives the same sign.
+__global__ __launch_bounds__(64) void disc_head_kernel(
+    const float* __restrict__ y5, const float* __restrict__ scale, const float* __restrict__ shift,
+    const float* __restrict__ wl, const float* __restrict__ bl, int N, int Ns, int H5, int W5, int train,
+    float* __restrict__ d_out, float* __restrict__ g5, float* __restrict__ stats /*(N,2,8)*/,
+    float* __restrict__ dwl_part /*(N,2,16)*/, float* __restrict__ dbl_part /*(N,2,1)*/,
+    float* __restrict__ loss_part /*(N,2,1)*/) {
   constexpr int C = 8;
-  const float* yn = y5 + (size_t)n * H5 * W5 * C;
+  constexpr double LEAKY_D = 0.2;
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int n = t >> 3, c = t & 7;
+  if (n >= N) return;   // whole groups of 8 lanes leave together: the shuffles below stay inside a group
+  const float* yn = y5 + (size_t)n * H5 * W5 * C + c;
   // adaptive bins over W5 (PyTorch: start = floor(i*W/2), end = ceil((i+1)*W/2))
   const int b0s = 0, b0e = (W5 + 1) / 2, b1s = W5 / 2, b1e = W5;
-  float pooled[C][2];
-  for (int c = 0; c < C; ++c) { pooled[c][0] = 0.f; pooled[c][1] = 0.f; }
+  const double sc = scale[c], sh = shift[c], w0 = wl[c * 2], w1 = wl[c * 2 + 1];
+  double p0 = 0., p1 = 0.;
   for (int h = 0; h < H5; ++h)
-    for (int w = 0; w < W5; ++w)
-      for (int c = 0; c < C; ++c) {
-        float a = fmaf(yn[(h * W5 + w) * C + c], scale[c], shift[c]);
-        a = a > 0.f ? a : LEAKY * a;
-        if (w >= b0s && w < b0e) pooled[c][0] += a;
-        if (w >= b1s && w < b1e) pooled[c][1] += a;
-      }
-  const float inv0 = 1.0f / (float)(H5 * (b0e - b0s)), inv1 = 1.0f / (float)(H5 * (b1e - b1s));
-  float z = bl[0];
-  for (int c = 0; c < C; ++c) {
-    pooled[c][0] *= inv0; pooled[c][1] *= inv1;
-    z = fmaf(wl[c * 2], pooled[c][0], z);
-    z = fmaf(wl[c * 2 + 1], pooled[c][1], z);
-  }
-  const float d = sigmoidf_(z);
-  d_out[n] = d;
+    for (int w = 0; w < W5; ++w) {
+      double a = (double)yn[(h * W5 + w) * C] * sc + sh;
+      a = a > 0. ? a : LEAKY_D * a;
+      if (w >= b0s && w < b0e) p0 += a;
+      if (w >= b1s && w < b1e) p1 += a;
+    }
+  const double inv0 = 1.0 / (double)(H5 * (b0e - b0s)), inv1 = 1.0 / (double)(H5 * (b1e - b1s));
+  p0 *= inv0; p1 *= inv1;
+  // z = bl + sum over the 8 channels: xor butterfly inside the group (the same value, bit for bit, in all 8 lanes)
+  double zs = w0 * p0 + w1 * p1;
+#pragma unroll
+  for (int o = 1; o < C; o <<= 1) zs += __shfl_xor(zs, o, 64);
+  const double z = (double)bl[0] + zs;
+  double dd = 1.0 / (1.0 + exp(-z)), omd = 1.0 / (1.0 + exp(z));   // d and 1 - d, neither by cancellation
+  const float d = (float)dd;
+  if (c == 0) d_out[n] = d;
   if (!train) return;
-  const float lab = n < Ns ? 1.f : 0.f;
-  loss_part[n * 2] = -(lab * fmaxf(logf(d), -100.f) + (1.f - lab) * fmaxf(logf(1.f - d), -100.f));
-  loss_part[n * 2 + 1] = 0.f;
-  const float dz = (d - lab) / fmaxf((1.f - d) * d, 1e-12f) / (float)N * d * (1.f - d);
-  dbl_part[n * 2] = dz; dbl_part[n * 2 + 1] = 0.f;
-  float dp[C][2];
-  for (int c = 0; c < C; ++c) {
-    dwl_part[(size_t)n * 32 + c * 2] = dz * pooled[c][0];
-    dwl_part[(size_t)n * 32 + c * 2 + 1] = dz * pooled[c][1];
-    dp[c][0] = dz * wl[c * 2] * inv0;
-    dp[c][1] = dz * wl[c * 2 + 1] * inv1;
+  // an output that saturates in fp32 is treated as torch treats it: BCE of d = 0 or 1 (the -100 clamp), zero gradient
+  if (d == 0.f || d == 1.f) { dd = d; omd = 1.0 - dd; }
+  const double lab = n < Ns ? 1. : 0.;
+  const double dz = (dd - lab) / fmax(omd * dd, 1e-12) / (double)N * dd * omd;
+  if (c == 0) {
+    loss_part[n * 2] = (float)-(lab * fmax(log(dd), -100.) + (1. - lab) * fmax(log(omd), -100.));
+    loss_part[n * 2 + 1] = 0.f;
+    dbl_part[n * 2] = (float)dz; dbl_part[n * 2 + 1] = 0.f;
   }
-  for (int j = 0; j < 16; ++j) dwl_part[(size_t)n * 32 + 16 + j] = 0.f;
-  float sg[C], sgy[C];
-  for (int c = 0; c < C; ++c) { sg[c] = 0.f; sgy[c] = 0.f; }
+  dwl_part[(size_t)n * 32 + c * 2] = (float)(dz * p0);
+  dwl_part[(size_t)n * 32 + c * 2 + 1] = (float)(dz * p1);
+  dwl_part[(size_t)n * 32 + 16 + c * 2] = 0.f;
+  dwl_part[(size_t)n * 32 + 16 + c * 2 + 1] = 0.f;
+  const double dp0 = dz * w0 * inv0, dp1 = dz * w1 * inv1;
+  double sg = 0., sgy = 0.;
+  float* gn = g5 + (size_t)n * H5 * W5 * C + c;
   for (int h = 0; h < H5; ++h)
-    for (int w = 0; w < W5; ++w)
-      for (int c = 0; c < C; ++c) {
-        const float yv = yn[(h * W5 + w) * C + c];
-        const float xn = fmaf(yv, scale[c], shift[c]);
-        float da = 0.f;
-        if (w >= b0s && w < b0e) da += dp[c][0];
-        if (w >= b1s && w < b1e) da += dp[c][1];
-        const float g = da * (xn > 0.f ? 1.f : LEAKY);
-        g5[((size_t)n * H5 * W5 + h * W5 + w) * C + c] = g;
-        sg[c] += g;
-        sgy[c] = fmaf(g, yv, sgy[c]);
-      }
-  for (int c = 0; c < C; ++c) {
-    stats[((size_t)n * 2 + 0) * C + c] = sg[c];
-    stats[((size_t)n * 2 + 1) * C + c] = sgy[c];
-  }
+    for (int w = 0; w < W5; ++w) {
+      const double yv = yn[(h * W5 + w) * C];
+      const double xn = yv * sc + sh;
+      double da = 0.;
+      if (w >= b0s && w < b0e) da += dp0;
+      if (w >= b1s && w < b1e) da += dp1;
+      const double g = da * (xn > 0. ? 1. : LEAKY_D);
+      gn[(h * W5 + w) * C] = (float)g;
+      sg += g;
+      sgy += g * yv;
+    }
+  stats[((size_t)n * 2 + 0) * C + c] = (float)sg;
+  stats[((size_t)n * 2 + 1) * C + c] = (float)sgy;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -496,8 +501,9 @@ extern "C" int bsed_disc_head(const float* y5, const float* scale, const float* 
   BSED_CHECK_ARG(y5 && scale && shift && wl && bl && d_out && N > 0 && Ns >= 0 && Ns <= N, "bsed_disc_head: bad argument");
   BSED_CHECK_ARG(C5 == 8 && H5 > 0 && W5 >= 2, "bsed_disc_head: built for the 8-channel last layer");
   BSED_CHECK_ARG(!train || (g5 && stats && dwl_part && dbl_part && loss_part), "bsed_disc_head: training needs the gradient buffers");
-  hipLaunchKernelGGL(disc_head_kernel, dim3(ceil_div(N, 64)), dim3(64), 0, (hipStream_t)stream, y5, scale, shift, wl, bl,
-                     N, Ns, H5, W5, train, d_out, g5, stats, dwl_part, dbl_part, loss_part);
+  BSED_CHECK_ARG(N <= (1 << 27), "bsed_disc_head: too many clips");
+  hipLaunchKernelGGL(disc_head_kernel, dim3(ceil_div((long)N * 8, 64)), dim3(64), 0, (hipStream_t)stream, y5, scale, shift,
+                     wl, bl, N, Ns, H5, W5, train, d_out, g5, stats, dwl_part, dbl_part, loss_part);
   BSED_LAUNCH_CHECK();
   return BSED_OK;
 }

@@ -249,52 +249,60 @@ class Clip_Discriminator(_FlatModule):
             bn = self.P(f"bn_{k}")
             ops.bn_bwd(stats, co, float(l["M"]), bn.weight, l["mean"], l["invstd"], bn.weight.grad, bn.bias.grad, g,
                        l["y"])
-            w = self.P(f"conv_{k}.weight")
-            p = lay[k - 2] if k > 1 else None
-            if l["direct"]:
-                Hp, Wp, K = l["Hp"], l["Wp"], 4 * cin
-                dy = g.view(N, Hp, Wp, co)
-                # the BatchNorm-backward map is affine: it left non-zero values on the grid's non-output row / column
-                dy[:, l["Ho"]:, :, :] = 0
-                dy[:, :, l["Wo"]:, :] = 0
-                part, G, KP, NP = ops.wgrad(l["xp"], dy, N, Hp, Wp, K, co, taps=TAPS2x2, mode="bf16x3")
-                tmp = torch.empty((4, K, co), device=dy.device, dtype=torch.float32)
-                ops.reduce_partials(part, G, 4, KP, NP, K, co, tmp, K * co, co, 1, accumulate=False, defer=False)
-                w.grad.add_(tmp.view(16, cin, co)[_S2D_SLOT].permute(2, 1, 0).reshape(co, cin, 3, 3))
-                flipped = [(-a, -b) for a, b in TAPS2x2]
-                wd3 = ops.pack_weight3(l["wfull"], 4, co, K, K * co, 1, co)
-                dxp, _ = ops.igemm3(dy, wd3, K, N, Hp, Wp, co, flipped)
-                g, stats = _s2d_bwd(dxp, p["y"], p["scale"], p["shift"], N, l["Ha_in"], l["Wa_in"], l["Hi"], l["Wi"], cin)
-                continue
-            dy = g.view(l["M"], co)
-            part, G, KP, NP = ops.wgrad(l["col"], dy, 1, l["M"], 1, l["K"], co, mode="bf16x3")
-            if cin == 1:
-                ops.reduce_partials(part, G, 1, KP, NP, 9, co, w.grad, 0, 1, 9)
-            else:
-                assert KP == 9 * l["CP"]
-                ops.reduce_partials(part, G, 9, l["CP"], NP, cin, co, w.grad, 1, 9, cin * 9)
-            wT, K, cop = self._bwd_weight(k, l["CP"])
-            if cop != co:  # the GEMM contracts over multiples of 16 channels: zero-pad dY of the last layer
-                dyp = torch.zeros((l["M"], cop), device=dy.device, dtype=torch.float32)
-                dyp[:, :co] = dy
-                dy = dyp
-            if cop % 32 == 0:
-                w3 = ops.pack_weight3(wT, 1, cop, K, 0, wT.shape[2], 1)
-                dcol, _ = ops.igemm3(dy, w3, K, 1, l["M"], 1, cop, ((0, 0),))
-            else:
-                dcol, _ = ops.igemm(dy, wT, K, 1, l["M"], 1, cop)
-            if k > 1:
-                # gradient on the compact (Hi, Wi) extent of the previous layer's output ...
-                yc = p["y"] if (p["Ha"], p["Wa"]) == (l["Hi"], l["Wi"]) else p["y"][:, :l["Hi"], :l["Wi"], :].contiguous()
-                gc, stats = _col2im(dcol, yc, p["scale"], p["shift"], N, l["Hi"], l["Wi"], cin, l["CP"])
-                if (p["Ha"], p["Wa"]) == (l["Hi"], l["Wi"]):
-                    g = gc
-                else:  # ... put back on that layer's allocated grid (zero on its non-output row / column)
-                    g = torch.zeros((N, p["Ha"], p["Wa"], cin), device=gc.device, dtype=torch.float32)
-                    g[:, :l["Hi"], :l["Wi"], :] = gc
-            else:
-                dfeat, _ = _col2im(dcol, None, None, None, N, l["Hi"], l["Wi"], 1, 1, out_scale=-float(grl_coeff))
-        return dfeat.view(N, ctx["T"], ctx["F"])
+            g, stats = self._conv_backward(k, l, lay[k - 2] if k > 1 else None, g, N, grl_coeff)
+        return g.view(N, ctx["T"], ctx["F"])
+
+    def _conv_backward(self, k, l, p, g, N, grl_coeff):
+        """Backward of conv_k given g = dL/d(its output) on layer k's allocated grid (l, p: the forward records of
+        layers k and k-1): accumulates conv_k.weight.grad and returns (g_prev, stats_prev) for layer k-1 -- the gradient
+        on that layer's BatchNorm output and its (sum g, sum g*y) partials -- or (dfeat, None) for k = 1, dfeat being
+        dL/d feat times -grl_coeff."""
+        co, cin = D_CH[k], D_CH[k - 1]
+        w = self.P(f"conv_{k}.weight")
+        if l["direct"]:
+            Hp, Wp, K = l["Hp"], l["Wp"], 4 * cin
+            dy = g.view(N, Hp, Wp, co)
+            # the BatchNorm-backward map is affine: it left non-zero values on the grid's non-output row / column
+            dy[:, l["Ho"]:, :, :] = 0
+            dy[:, :, l["Wo"]:, :] = 0
+            part, G, KP, NP = ops.wgrad(l["xp"], dy, N, Hp, Wp, K, co, taps=TAPS2x2, mode="bf16x3")
+            tmp = torch.empty((4, K, co), device=dy.device, dtype=torch.float32)
+            ops.reduce_partials(part, G, 4, KP, NP, K, co, tmp, K * co, co, 1, accumulate=False, defer=False)
+            w.grad.add_(tmp.view(16, cin, co)[_S2D_SLOT].permute(2, 1, 0).reshape(co, cin, 3, 3))
+            flipped = [(-a, -b) for a, b in TAPS2x2]
+            wd3 = ops.pack_weight3(l["wfull"], 4, co, K, K * co, 1, co)
+            dxp, _ = ops.igemm3(dy, wd3, K, N, Hp, Wp, co, flipped)
+            return _s2d_bwd(dxp, p["y"], p["scale"], p["shift"], N, l["Ha_in"], l["Wa_in"], l["Hi"], l["Wi"], cin)
+        dy = g.view(l["M"], co)
+        part, G, KP, NP = ops.wgrad(l["col"], dy, 1, l["M"], 1, l["K"], co, mode="bf16x3")
+        if cin == 1:
+            ops.reduce_partials(part, G, 1, KP, NP, 9, co, w.grad, 0, 1, 9)
+        else:
+            assert KP == 9 * l["CP"]
+            ops.reduce_partials(part, G, 9, l["CP"], NP, cin, co, w.grad, 1, 9, cin * 9)
+        wT, K, cop = self._bwd_weight(k, l["CP"])
+        if cop != co:  # the GEMM contracts over multiples of 16 channels: zero-pad dY of the last layer
+            dyp = torch.zeros((l["M"], cop), device=dy.device, dtype=torch.float32)
+            dyp[:, :co] = dy
+            dy = dyp
+        if cop % 32 == 0:
+            w3 = ops.pack_weight3(wT, 1, cop, K, 0, wT.shape[2], 1)
+            dcol, _ = ops.igemm3(dy, w3, K, 1, l["M"], 1, cop, ((0, 0),))
+        else:
+            dcol, _ = ops.igemm(dy, wT, K, 1, l["M"], 1, cop)
+        if k > 1:
+            # gradient on the compact (Hi, Wi) extent of the previous layer's output ...
+            yc = p["y"] if (p["Ha"], p["Wa"]) == (l["Hi"], l["Wi"]) else p["y"][:, :l["Hi"], :l["Wi"], :].contiguous()
+            gc, stats = _col2im(dcol, yc, p["scale"], p["shift"], N, l["Hi"], l["Wi"], cin, l["CP"])
+            if (p["Ha"], p["Wa"]) == (l["Hi"], l["Wi"]):
+                g = gc
+            else:  # ... put back on that layer's allocated grid (zero on its non-output row / column)
+                g = torch.zeros((N, p["Ha"], p["Wa"], cin), device=gc.device, dtype=torch.float32)
+                g[:, :l["Hi"], :l["Wi"], :] = gc
+        else:
+            dfeat, _ = _col2im(dcol, None, None, None, N, l["Hi"], l["Wi"], 1, 1, out_scale=-float(grl_coeff))
+            return dfeat, None
+        return g, stats
 
     def forward(self, x):
         d, _ = self.run_forward(x, save=False)
