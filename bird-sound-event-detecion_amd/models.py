@@ -179,7 +179,8 @@ class CRNN(_FlatModule):
         # summary of the default configuration describes the overlap for those rows.  BSED_RNN_OVERLAP=0: one stream.
         self.overlap_rnn = os.environ.get("BSED_RNN_OVERLAP", "1") != "0"
         # first block without its conv output / gradient tensors in HBM (csrc/block0.hip); 0 = the four-kernel form
-        # (conv0_fwd, glu16_fwd, glu16_bwd, conv0_wgrad), kept as the cross-check of the tests
+        # (conv0_fwd, the 16-channel GLU forward and backward of ops.glu_route, conv0_wgrad), kept as the cross-check of
+        # the tests
         self.block0_fused = True
         self._side_stream = None
         self.rnn_hook = None
@@ -188,14 +189,13 @@ class CRNN(_FlatModule):
         # "bf16x3" (default): the 3x3 conv forward / data-gradient contractions and the GRU projection GEMMs run on the
         # bf16 matrix cores with split-fp32 operands (csrc/igemm3.hip; measured 5.5e-6 on the logits of the reference
         # config, 18x inside the 1e-4 bar).  "fp32": exact fp32 matrix cores everywhere (9.6e-7 on the logits).
-        import os as _os
         # "bf16" (BASELINE configs[1-2], SURVEY.md section 0 D4 / 8(d): the THROUGHPUT mode, not the parity mode): the CNN's
         # activations -- conv outputs, pooled outputs and every gradient tensor of the same shapes -- are bf16 in HBM and
         # its contractions are ONE bf16 MFMA per product; accumulation, bias, BatchNorm statistics and their backward map,
         # GLU gate math, master weights, weight gradients and the optimizer stay fp32.  The GRU and the head keep fp32
         # tensors and split-fp32 contractions (their tensors are 2 % of the step's bytes).  tests/test_bf16_mode_gpu.py
         # states its tolerance against the fp32 oracle.
-        self.conv_mode = _os.environ.get("BSED_CONV_MODE", "bf16x3")
+        self.conv_mode = os.environ.get("BSED_CONV_MODE", "bf16x3")
         if self.conv_mode not in ("fp32", "bf16x3", "bf16"):
             raise L.BsedError(f"BSED_CONV_MODE must be fp32, bf16x3 or bf16, got {self.conv_mode!r}")
         pspecs, bspecs = [], []
@@ -284,9 +284,11 @@ class CRNN(_FlatModule):
         """storage type of the CNN's activation / gradient tensors"""
         return torch.bfloat16 if self.conv_mode == "bf16" else torch.float32
 
+    _HAS_BF16_MODE = True  # False: conv_mode="bf16" is refused (a subclass with layers that have no bf16-mode path)
+
     def _check_bf16_mode(self):
         if self.conv_mode == "bf16" and not (ops.igemm3_nsplit() and self.block0_fused and self.fused_glu_bwd
-                                             and not any(c.__name__ == "CRNN_fpn" for c in type(self).__mro__)
+                                             and self._HAS_BF16_MODE
                                              and self.nb_filters[0] == 16 and all(f >= 32 for f in self.nb_filters[1:])):
             raise L.BsedError("conv_mode='bf16' is built for the plain CRNN / CRNN_pred path (fused first block with 16 "
                               "filters, N-split conv kernel, bf16-core GLU kernels); FPN variant and A/B switches: use bf16x3")
@@ -353,18 +355,8 @@ class CRNN(_FlatModule):
             mean = invstd = None
             scale, shift = bn_pre or ops.bn_eval(co, BN_EPS, bn.weight, bn.bias, bn.running_mean, bn.running_var)
         glu = self.P(names[2])
-        if co == 16:
-            # 4 FLOP/B: HBM-bound streaming kernel instead of the MFMA tile kernel (csrc/glu_small.hip)
-            pooled = ops.glu16_fwd(y, scale, shift, glu.weight, glu.bias, B, Hh, Ww, (ph, pw), drop, rng_stream,
-                                   self.seed)
-        elif self._mfma3 and ops.glu_fwd3_supported(Ww, co, (ph, pw)):
-            pooled = ops.glu_fwd3(y, scale, shift, glu.weight, glu.bias, B, Hh, Ww, co, (ph, pw), drop, rng_stream,
-                                  self.seed)
-        else:
-            wg = ops.pack_weight(glu.weight, 1, co, co, 0, 1, co)
-            pooled, _ = ops.igemm(y, wg, co, B, Hh, Ww, co, bias=glu.bias, epilogue=ops.EPI_GLU_POOL,
-                                  a_scale=scale, a_shift=shift, e_src=y, e_scale=scale, e_shift=shift,
-                                  pool=(ph, pw), drop_p=drop, rng_stream=rng_stream, seed=self.seed)
+        pooled = ops.glu_forward(y, scale, shift, glu.weight, glu.bias, B, Hh, Ww, co, (ph, pw), drop, rng_stream,
+                                 self.seed, mode=self.conv_mode)
         blk = dict(inp=a, y=y, mean=mean, invstd=invstd, scale=scale, shift=shift, H=Hh, W=Ww, cin=cin, co=co,
                    pool=(ph, pw), names=names, drop=drop, rng=rng_stream, first=first)
         return pooled, blk
@@ -387,6 +379,21 @@ class CRNN(_FlatModule):
         blk = dict(inp=a, y=None, xr64=xr64, mean=mean, invstd=invstd, scale=scale, shift=shift, H=Hh, W=Ww, cin=1,
                    co=16, pool=pool, names=names, drop=drop, rng=rng_stream, first=True)
         return pooled, blk
+
+    def _block0_backward(self, blk, dpool, B, seed):
+        """backward of _block0_forward: y recomputed from x, g consumed in registers (BatchNorm-backward sums, Gx = sum g
+        x_tap); conv0's weight gradient is assembled from Gx and the input's tap correlations (csrc/block0.hip)"""
+        Hh, Ww, co = blk["H"], blk["W"], blk["co"]
+        conv_n, bn_n, glu_n = blk["names"]
+        glu, bn = self.P(glu_n), self.P(bn_n)
+        cw, cb = self.P(conv_n + ".weight"), self.P(conv_n + ".bias")
+        pdw, pdb, st2, pgx, G = ops.block0_bwd(blk["inp"], cw, cb, blk["scale"], blk["shift"], glu.weight, glu.bias,
+                                               dpool.contiguous(), B, Hh, Ww, blk["pool"], blk["drop"], blk["rng"], seed)
+        ops.reduce_partials(pdw, G, 1, 16, 16, 16, 16, glu.weight.grad, 0, 16, 1)
+        ops.stats_to_grad(pdb, co, 0, glu.bias.grad)
+        coef = ops.bn_bwd(st2, co, float(B * Hh * Ww), bn.weight, blk["mean"], blk["invstd"], bn.weight.grad,
+                          bn.bias.grad, None, blk["inp"], apply=False)
+        ops.block0_wgrad_finish(pgx, G, blk["xr64"], coef, blk["mean"], cw, cb, cw.grad)
 
     @staticmethod
     def _conv_taps(cw, Ww):
@@ -465,69 +472,15 @@ class CRNN(_FlatModule):
 
     def _block_backward(self, blk, dpool, B, seed, need_dgrad=True):
         """backward of one conv/BN/GLU/dropout/pool block; returns dL/d(block input) or None for the first block"""
+        if blk["first"] and blk["y"] is None:
+            return self._block0_backward(blk, dpool, B, seed)
         Hh, Ww, cin, co = blk["H"], blk["W"], blk["cin"], blk["co"]
-        ph, pw = blk["pool"]
         y = blk["y"]
         conv_n, bn_n, glu_n = blk["names"]
         glu, bn = self.P(glu_n), self.P(bn_n)
-        drop_b, rng = blk["drop"], blk["rng"]
-        if blk["first"] and y is None:
-            # fused first block: y recomputed from x, g consumed in registers (BatchNorm-backward sums, Gx = sum g x_tap);
-            # conv0's weight gradient is assembled from Gx and the input's tap correlations (csrc/block0.hip)
-            cw, cb = self.P(conv_n + ".weight"), self.P(conv_n + ".bias")
-            pdw, pdb, st2, pgx, G = ops.block0_bwd(blk["inp"], cw, cb, blk["scale"], blk["shift"], glu.weight,
-                                                   glu.bias, dpool.contiguous(), B, Hh, Ww, (ph, pw), drop_b, rng, seed)
-            ops.reduce_partials(pdw, G, 1, 16, 16, 16, 16, glu.weight.grad, 0, 16, 1)
-            ops.stats_to_grad(pdb, co, 0, glu.bias.grad)
-            coef = ops.bn_bwd(st2, co, float(B * Hh * Ww), bn.weight, blk["mean"], blk["invstd"], bn.weight.grad,
-                              bn.bias.grad, None, blk["inp"], apply=False)
-            ops.block0_wgrad_finish(pgx, G, blk["xr64"], coef, blk["mean"], cw, cb, cw.grad)
-            return None
-        if co == 16:
-            # one streaming pass: y, d_pooled -> g + partials of dW_glu, db_glu and the BN-backward sums
-            g, pdw, pdb, st2, G = ops.glu16_bwd(y, blk["scale"], blk["shift"], glu.weight, glu.bias,
-                                                dpool.contiguous(), B, Hh, Ww, (ph, pw), drop_b, rng, seed)
-            ops.reduce_partials(pdw, G, 1, 16, 16, 16, 16, glu.weight.grad, 0, 16, 1)
-            ops.stats_to_grad(pdb, co, 0, glu.bias.grad)
-        elif co in (32, 64) and self.fused_glu_bwd and self._mfma3:
-            # all three contractions on the bf16 cores, operands fetched in MFMA register layout (csrc/glu3.hip)
-            g, pdw, pdb, st2, G, slabs = ops.glu_bwd3(y, blk["scale"], blk["shift"], glu.weight, glu.bias,
-                                                      dpool.contiguous(), B, Hh, Ww, co, (ph, pw), drop_b, rng, seed)
-            ops.reduce_partials(pdw, G * slabs, 1, co, co, co, co, glu.weight.grad, 0, co, 1)
-            ops.stats_to_grad(pdb, co, 0, glu.bias.grad)
-        elif co == 128 and self.fused_glu_bwd and self._mfma3:
-            # lin recompute + g on the bf16 cores; d_lin goes through HBM to a 1-tap weight-gradient contraction
-            g, dlin, pdb, st2, G = ops.glu_bwd3n(y, blk["scale"], blk["shift"], glu.weight, glu.bias,
-                                                 dpool.contiguous(), B, Hh, Ww, co, (ph, pw), drop_b, rng, seed)
-            ops.stats_to_grad(pdb, co, 0, glu.bias.grad)
-            part, Gw, KP, NP = ops.wgrad(y, dlin, B, Hh, Ww, co, co, a_scale=blk["scale"], a_shift=blk["shift"],
-                                         mode=self.conv_mode)
-            ops.reduce_partials(part, Gw, 1, KP, NP, co, co, glu.weight.grad, 0, 1, co)
-            del dlin
-        elif co in (32, 64, 128) and self.fused_glu_bwd:
-            # three chained MFMA contractions per tile, y read once, g written once (csrc/glu_bwd.hip)
-            wfwd = ops.pack_weight(glu.weight, 1, co, co, 0, 1, co)
-            g, pdw, pdb, st2, G, slabs = ops.glu_bwd_fused(y, blk["scale"], blk["shift"], wfwd, glu.weight,
-                                                           glu.bias, dpool.contiguous(), B, Hh, Ww, co, (ph, pw),
-                                                           drop_b, rng, seed)
-            ops.reduce_partials(pdw, G * slabs, 1, co, co, co, co, glu.weight.grad, 0, co, 1)
-            ops.stats_to_grad(pdb, co, 0, glu.bias.grad)
-        else:
-            # (1) recompute lin, form d_lin and the gate-branch term
-            wg = ops.pack_weight(glu.weight, 1, co, co, 0, 1, co)
-            tt = torch.empty_like(y)
-            dlin, st = ops.igemm(y, wg, co, B, Hh, Ww, co, bias=glu.bias, epilogue=ops.EPI_GLU_BWD,
-                                 a_scale=blk["scale"], a_shift=blk["shift"], e_src=y, e_scale=blk["scale"],
-                                 e_shift=blk["shift"], e_dpool=dpool, out2=tt, pool=(ph, pw), drop_p=drop_b,
-                                 rng_stream=rng, seed=seed)
-            ops.stats_to_grad(st, co, 0, glu.bias.grad)
-            # (2) dW_glu = d_lin^T @ bn(y)
-            part, G, KP, NP = ops.wgrad(y, dlin, B, Hh, Ww, co, co, a_scale=blk["scale"], a_shift=blk["shift"],
-                                         mode=self.conv_mode)
-            ops.reduce_partials(part, G, 1, KP, NP, co, co, glu.weight.grad, 0, 1, co)
-            # (3) g = d_lin @ W_glu + gate term  (gradient w.r.t. the BatchNorm output), with BN-backward sums
-            wgT = ops.pack_weight(glu.weight, 1, co, co, 0, co, 1)
-            g, st2 = ops.igemm(dlin, wgT, co, B, Hh, Ww, co, epilogue=ops.EPI_ADD_STATS2, out=tt, out2=tt, e_src=y)
+        g, st2 = ops.glu_backward(y, blk["scale"], blk["shift"], glu.weight, glu.bias, dpool, B, Hh, Ww, co, blk["pool"],
+                                  blk["drop"], blk["rng"], seed, mode=self.conv_mode, fused=self.fused_glu_bwd,
+                                  dw=glu.weight.grad, db=glu.bias.grad)
         cw = self.P(conv_n + ".weight")
         # conv bias feeds a train-mode BatchNorm: its gradient is exactly zero (DESIGN.md), leave it
         if blk["first"]:
@@ -606,16 +559,23 @@ class CRNN(_FlatModule):
                     on_early_grads()   # every gradient outside the first TAIL_BLOCKS blocks has been enqueued
             dpool = self._block_backward(ctx["blocks"][i], dpool, ctx["B"], ctx["seed"])
 
+    def _forward_preamble(self, x, save):
+        """head of every run_forward: checks x (B,1,T,F) and the mode; returns (x as contiguous fp32, ctx or None)"""
+        if x.dim() != 4 or x.shape[1] != 1:
+            raise L.BsedError(f"{type(self).__name__} expects (B,1,T,F), got {tuple(x.shape)}")
+        x = x.contiguous().float()
+        ctx = None
+        if save:
+            ctx = {"B": x.shape[0], "blocks": [], "train": self.training, "seed": self.seed, "x": x}
+        self._check_bf16_mode()
+        return x, ctx
+
     def run_forward(self, x, save=True):
         """x: (B,1,T,F) fp32 GPU tensor.  Returns (enc (B,T',256), ctx for run_backward or None)."""
-        if x.dim() != 4 or x.shape[1] != 1:
-            raise L.BsedError(f"CRNN expects (B,1,T,F), got {tuple(x.shape)}")
-        x = x.contiguous().float()
+        x, ctx = self._forward_preamble(x, save)
         B = x.shape[0]
         train = self.training
         drop = self.dropout_p if train else 0.0
-        ctx = {"B": B, "blocks": [], "train": train, "seed": self.seed, "x": x} if save else None
-        self._check_bf16_mode()
         with ops.pack_cache(None if train else self._eval_plan):
             a, T = self._cnn_forward(x, ctx)
             if a.dtype != torch.float32:
@@ -668,6 +628,7 @@ class CRNN_fpn(CRNN):
     because it owns state-dict entries (its gradient stays zero)."""
 
     FPN_DROPOUT = 0.5
+    _HAS_BF16_MODE = False   # the pyramid's fuse layers and GRU inputs have no bf16-mode path: conv_mode="bf16" is refused
 
     def _extra_specs(self):
         H = self.n_hidden
@@ -727,14 +688,11 @@ class CRNN_fpn(CRNN):
         return d_cat.view(B, T, 512)
 
     def run_forward(self, x, save=True):
-        if x.dim() != 4 or x.shape[1] != 1:
-            raise L.BsedError(f"CRNN_fpn expects (B,1,T,F), got {tuple(x.shape)}")
-        x = x.contiguous().float()
+        x, ctx = self._forward_preamble(x, save)
         B = x.shape[0]
         train = self.training
         drop = self.dropout_p if train else 0.0
         dropf = self.FPN_DROPOUT if train else 0.0
-        ctx = {"B": B, "blocks": [], "train": train, "seed": self.seed, "x": x} if save else None
         a, T = self._cnn_forward(x, ctx)
         T2, T4 = T // 2, (T // 2) // 2
         if T4 < 1:
@@ -826,12 +784,9 @@ class CRNN_pred(CRNN):
         return [("dense_softmax", "linear")] + super()._init_roles()
 
     def run_forward(self, x, save=False):
-        if x.dim() != 4 or x.shape[1] != 1:
-            raise L.BsedError(f"CRNN_pred expects (B,1,T,F), got {tuple(x.shape)}")
-        x = x.contiguous().float()
+        x, _ = self._forward_preamble(x, False)
         B = x.shape[0]
         with ops.pack_cache(None if self.training else self._eval_plan):
-            self._check_bf16_mode()
             a, T = self._cnn_forward(x, None)
             C = self.nclass
             feats = (a if a.dtype == torch.float32 else a.float()).view(B, T, C)   # bf16 mode: the head stays fp32

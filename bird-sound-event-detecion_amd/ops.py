@@ -132,6 +132,12 @@ def tile_for(W):
     return 128 // tw, tw
 
 
+def _map_tiles(NB, H, W):
+    """(TH, TW, tile count) of an (NB, H, W) map cut into tile_for(W) tiles"""
+    TH, TW = tile_for(W)
+    return TH, TW, NB * ((H + TH - 1) // TH) * (W // TW)
+
+
 def _p(t):
     return L.ptr(t).value if t is not None else None
 
@@ -169,13 +175,13 @@ def pack_weight(src, ntaps, K, N, s_tap, s_k, s_n, src_offset=0):
 
 def _tile_taps(d, H, W, taps):
     """Tile, taps and halo of an IgemmDesc / WgradDesc; returns the tile count of one (H, W) image."""
-    TH, TW = d.TH, d.TW = tile_for(W)
+    d.TH, d.TW, ntiles = _map_tiles(1, H, W)
     hh = hw = 0
     for i, (a, b) in enumerate(taps):
         d.dh[i], d.dw[i] = a, b
         hh, hw = max(hh, abs(a)), max(hw, abs(b))
     d.hh, d.hw, d.ntaps = hh, hw, len(taps)
-    return ((H + TH - 1) // TH) * (W // TW)
+    return ntiles
 
 
 def _igemm_desc(NB, H, W, CIN, N, NP, taps, epilogue, valid=None):
@@ -604,6 +610,13 @@ def conv0_wgrad(x, dy, NB, H, W, CO, y=None, coef=None, mean=None):
     return part, G
 
 
+def _glu_partials(G, rows, C, dev):
+    """partial sums of a GLU backward on G workgroups: (part_dw (rows,C,C), part_db (G,2,C), part_st (G,2,C))"""
+    return (torch.empty((rows, C, C), device=dev, dtype=torch.float32),
+            torch.empty((G, 2, C), device=dev, dtype=torch.float32),
+            torch.empty((G, 2, C), device=dev, dtype=torch.float32))
+
+
 def glu16_fwd(y, scale, shift, wg, bg, B, H, W, pool, drop_p, rng_stream, seed):
     ph, pw = pool
     out = torch.empty((B, H // ph, W // pw, 16), device=y.device, dtype=torch.float32)
@@ -619,9 +632,7 @@ def glu16_bwd(y, scale, shift, wg, bg, dpool, B, H, W, pool, drop_p, rng_stream,
     dev = y.device
     G = int(min(2048, B * H))
     g = torch.empty_like(y)
-    part_dw = torch.empty((G, 16, 16), device=dev, dtype=torch.float32)
-    part_db = torch.empty((G, 2, 16), device=dev, dtype=torch.float32)
-    part_st = torch.empty((G, 2, 16), device=dev, dtype=torch.float32)
+    part_dw, part_db, part_st = _glu_partials(G, G, 16, dev)
     _note("glu16_bwd_kernel", f"{H}x{W}", 3 * 2.0 * B * H * W * 256, 4.0 * B * H * W * 16 * (2.0 + 1.0 / (ph * pw)))
     L.call("bsed_glu16_bwd", L.ptr(y), L.ptr(scale), L.ptr(shift), _dp(wg), _dp(bg), L.ptr(dpool), L.ptr(g),
            L.ptr(part_dw), L.ptr(part_db), L.ptr(part_st), G, B, H, W, 16, ph, pw, drop_p, rng_stream, seed, L.stream())
@@ -659,9 +670,7 @@ def block0_bwd(x, cw, cb, scale, shift, wg, bg, dpool, B, H, W, pool, drop_p, rn
     ph, pw = pool
     dev = x.device
     G = int(min(8192, B * (H // ph)))   # 2048 / 4096 / 8192 workgroups: 0.983 / 0.966 / 0.957 ms
-    part_dw = torch.empty((G, 16, 16), device=dev, dtype=torch.float32)
-    part_db = torch.empty((G, 2, 16), device=dev, dtype=torch.float32)
-    part_st = torch.empty((G, 2, 16), device=dev, dtype=torch.float32)
+    part_dw, part_db, part_st = _glu_partials(G, G, 16, dev)
     part_gx = torch.empty((G, 9, 16), device=dev, dtype=torch.float32)
     ab = _abf(dpool)
     _note(f"b0_bwd_kernel<{ph}, {'true' if B * H * W < (1 << 28) else 'false'}, {ab}>", f"{H}x{W}", 2.0 * B * H * W * (2 * 9 * 16 + 3 * 256),
@@ -682,14 +691,11 @@ def glu_bwd_fused(y, scale, shift, wfwd, w, bias, dpool, B, H, W, C, pool, drop_
     """returns (g, part_dw (G*slabs,C,C), part_db (G,2,C), part_st (G,2,C), G, slabs)"""
     ph, pw = pool
     dev = y.device
-    TH, TW = tile_for(W)
-    ntiles = B * ((H + TH - 1) // TH) * (W // TW)
+    TH, TW, ntiles = _map_tiles(B, H, W)
     G = int(min(ntiles, 256 * (1 if C == 128 else (2 if C == 64 else 3))))
     slabs = L.lib().bsed_glu_bwd_slabs(C)
     g = torch.empty_like(y)
-    part_dw = torch.empty((G * slabs, C, C), device=dev, dtype=torch.float32)
-    part_db = torch.empty((G, 2, C), device=dev, dtype=torch.float32)
-    part_st = torch.empty((G, 2, C), device=dev, dtype=torch.float32)
+    part_dw, part_db, part_st = _glu_partials(G, G * slabs, C, dev)
     flops = 3 * 2.0 * B * H * W * C * C
     nbytes = 4.0 * B * H * W * C * (2.0 + 1.0 / (ph * pw))  # y, g, d_pooled
     _launch((f"glu_bwd_fused_kernel<{C}, {8 if C == 128 else 4}>", 1, C, C, H, W), flops,
@@ -708,8 +714,7 @@ def glu_fwd3_supported(W, C, pool):
 def glu_fwd3(y, scale, shift, w, bias, B, H, W, C, pool, drop_p, rng_stream, seed):
     """split-fp32 GLU forward: BN-apply -> Linear -> gate -> dropout -> avg-pool in one pass over y"""
     ph, pw = pool
-    TH, TW = tile_for(W)
-    ntiles = B * ((H + TH - 1) // TH) * (W // TW)
+    TH, TW, ntiles = _map_tiles(B, H, W)
     G = int(min(ntiles, L.lib().bsed_glu_fwd3_auto_g(C)))
     out = torch.empty((B, H // ph, W // pw, C), device=y.device, dtype=y.dtype)
     ab = _abf(y)
@@ -724,14 +729,11 @@ def glu_bwd3(y, scale, shift, w, bias, dpool, B, H, W, C, pool, drop_p, rng_stre
     """split-fp32 fused GLU backward (C in {32,64}); returns like glu_bwd_fused"""
     ph, pw = pool
     dev = y.device
-    TH, TW = tile_for(W)
-    ntiles = B * ((H + TH - 1) // TH) * (W // TW)
+    TH, TW, ntiles = _map_tiles(B, H, W)
     G = int(min(ntiles, L.lib().bsed_glu_bwd3_auto_g(C)))
     slabs = L.lib().bsed_glu_bwd3_slabs(C)
     g = torch.empty_like(y)
-    part_dw = torch.empty((G * slabs, C, C), device=dev, dtype=torch.float32)
-    part_db = torch.empty((G, 2, C), device=dev, dtype=torch.float32)
-    part_st = torch.empty((G, 2, C), device=dev, dtype=torch.float32)
+    part_dw, part_db, part_st = _glu_partials(G, G * slabs, C, dev)
     flops = 3 * 2.0 * B * H * W * C * C
     ab = _abf(y, dpool)
     _launch((f"glu_bwd3_kernel<{C}, {4 if TW == 16 else -1}, {ab}>", 1, C, C, H, W), flops,
@@ -749,8 +751,7 @@ def glu_bwd3n(y, scale, shift, w, bias, dpool, B, H, W, C, pool, drop_p, rng_str
     """split-fp32 GLU backward for C = 128 without the weight gradient: returns (g, d_lin, part_db, part_st, G)"""
     ph, pw = pool
     dev = y.device
-    TH, TW = tile_for(W)
-    ntiles = B * ((H + TH - 1) // TH) * (W // TW)
+    TH, TW, ntiles = _map_tiles(B, H, W)
     G = int(min((ntiles + 1) // 2, 256))  # 8-wave workgroups take two tiles at a time
     tb = _frag_tables.get(str(dev))
     if tb is None:
@@ -766,6 +767,76 @@ def glu_bwd3n(y, scale, shift, w, bias, dpool, B, H, W, C, pool, drop_p, rng_str
                            tb.data_ptr(), G, B, H, W, C, TH, TW, ph, pw, drop_p, rng_stream, seed, ab, L.stream()),
             _esz(y) * B * H * W * C * (3.0 + 1.0 / (ph * pw)))  # y, g, d_lin, d_pooled
     return g, dlin, part_db, part_st, G
+
+
+def glu_route(direction, C, W, pool, mode, fused=True):
+    """Name of the kernel route that runs the GLU half of a CNN block (BN-apply -> Linear -> gate -> dropout -> avg-pool)
+    with C channels on a width-W map.  The only place that compares C, W, pool, mode (the caller's conv_mode) and fused
+    (False: the unfused backward chain, a cross-check); glu_forward / glu_backward switch on the name, and a new GLU
+    kernel is wired in here.  The fused first block (block0_*) is a whole block, not a route of this table."""
+    if mode not in ("fp32", "bf16x3", "bf16"):
+        raise L.BsedError(f"glu_route: unknown mode {mode!r}")
+    if direction not in ("forward", "backward"):
+        raise L.BsedError(f"glu_route: unknown direction {direction!r}")
+    if C == 16:
+        return "glu16"        # 4 FLOP/B: one HBM-bound streaming pass instead of MFMA tiles (csrc/glu_small.hip)
+    if direction == "forward":
+        if mode != "fp32" and glu_fwd3_supported(W, C, pool):
+            return "glu3"     # the bf16 cores, operands fetched in MFMA register layout (csrc/glu3.hip)
+        return "igemm"        # the fp32-core contraction with the GLU_POOL epilogue (csrc/igemm.hip)
+    if C in (32, 64) and fused and mode != "fp32":
+        return "glu3"         # all three contractions on the bf16 cores (csrc/glu3.hip)
+    if C == 128 and fused and mode != "fp32":
+        return "glu3n"        # lin recompute + g on the bf16 cores; d_lin goes through HBM to a 1-tap weight gradient
+    if C in (32, 64, 128) and fused:
+        return "fused_fp32"   # three chained MFMA contractions per tile, y read once, g written once (csrc/glu_bwd.hip)
+    return "unfused"          # igemm GLU_BWD (d_lin, gate term) -> 1-tap weight gradient -> igemm ADD_STATS2 (g)
+
+
+def glu_forward(y, scale, shift, w, bias, B, H, W, C, pool, drop_p, rng_stream, seed, *, mode):
+    """GLU half of a block on the conv output y (B,H,W,C) with BatchNorm's scale / shift; returns the pooled output"""
+    route = glu_route("forward", C, W, pool, mode)
+    if route == "glu16":
+        return glu16_fwd(y, scale, shift, w, bias, B, H, W, pool, drop_p, rng_stream, seed)
+    if route == "glu3":
+        return glu_fwd3(y, scale, shift, w, bias, B, H, W, C, pool, drop_p, rng_stream, seed)
+    wg = pack_weight(w, 1, C, C, 0, 1, C)
+    return igemm(y, wg, C, B, H, W, C, bias=bias, epilogue=EPI_GLU_POOL, a_scale=scale, a_shift=shift, e_src=y,
+                 e_scale=scale, e_shift=shift, pool=pool, drop_p=drop_p, rng_stream=rng_stream, seed=seed)[0]
+
+
+def glu_backward(y, scale, shift, w, bias, dpool, B, H, W, C, pool, drop_p, rng_stream, seed, *, mode, fused, dw, db):
+    """Backward of glu_forward: accumulates the GLU linear's gradients into dw / db; returns (g, st2) = dL/d(BatchNorm
+    output) and the BatchNorm-backward partial sums"""
+    route = glu_route("backward", C, W, pool, mode, fused)
+    dpool = dpool.contiguous()
+    tail = (pool, drop_p, rng_stream, seed)
+    if route in ("glu3n", "unfused"):   # d_lin goes through HBM: dW_glu = d_lin^T @ bn(y) is a 1-tap weight gradient
+        if route == "glu3n":
+            g, dlin, pdb, st2, _ = glu_bwd3n(y, scale, shift, w, bias, dpool, B, H, W, C, *tail)
+        else:                           # (1) recompute lin, form d_lin and the gate-branch term (into tt)
+            tt = torch.empty_like(y)
+            dlin, pdb = igemm(y, pack_weight(w, 1, C, C, 0, 1, C), C, B, H, W, C, bias=bias, epilogue=EPI_GLU_BWD,
+                              a_scale=scale, a_shift=shift, e_src=y, e_scale=scale, e_shift=shift, e_dpool=dpool,
+                              out2=tt, pool=pool, drop_p=drop_p, rng_stream=rng_stream, seed=seed)
+        stats_to_grad(pdb, C, 0, db)
+        part, G, KP, NP = wgrad(y, dlin, B, H, W, C, C, a_scale=scale, a_shift=shift, mode=mode)
+        reduce_partials(part, G, 1, KP, NP, C, C, dw, 0, 1, C)
+        if route == "unfused":          # (3) g = d_lin @ W_glu + gate term, with the BatchNorm-backward sums
+            g, st2 = igemm(dlin, pack_weight(w, 1, C, C, 0, C, 1), C, B, H, W, C, epilogue=EPI_ADD_STATS2, out=tt,
+                           out2=tt, e_src=y)
+        return g, st2
+    if route == "glu16":
+        g, pdw, pdb, st2, G = glu16_bwd(y, scale, shift, w, bias, dpool, B, H, W, *tail)
+        slabs = 1
+    elif route == "glu3":
+        g, pdw, pdb, st2, G, slabs = glu_bwd3(y, scale, shift, w, bias, dpool, B, H, W, C, *tail)
+    else:
+        wfwd = pack_weight(w, 1, C, C, 0, 1, C)
+        g, pdw, pdb, st2, G, slabs = glu_bwd_fused(y, scale, shift, wfwd, w, bias, dpool, B, H, W, C, *tail)
+    reduce_partials(pdw, G * slabs, 1, C, C, C, C, dw, 0, C, 1)
+    stats_to_grad(pdb, C, 0, db)
+    return g, st2
 
 
 def bn_finalize(stats, C, count, eps, momentum, gamma, beta, rmean, rvar, nbt):

@@ -101,6 +101,25 @@ def test_fpn_train_step_with_predictor_and_dropout_runs_and_is_repeatable():
     assert torch.equal(grads[0], grads[1])
 
 
+def test_fpn_refuses_the_bf16_mode_before_launching_anything(monkeypatch):
+    """conv_mode="bf16" has no path through the pyramid's fuse layers and GRU inputs: run_forward says so up front
+    instead of running the CNN and both levels in bf16 and failing on a dtype inside the first GRU"""
+    from bsed_amd._lib import BsedError
+    from bsed_amd.models import CRNN_fpn
+    from test_graph_step_gpu import _recorded_launches
+    monkeypatch.setenv("BSED_CONV_MODE", "bf16")
+    mine = CRNN_fpn(**co.CRNN_KWARGS)
+    monkeypatch.undo()
+    assert mine.conv_mode == "bf16"
+    mine.train()
+    x = torch.from_numpy(seeded.db_like_input(5, 2, 16)).cuda()
+    assert x.shape == (2, 1, 16, 128)
+    with _recorded_launches() as names:
+        with pytest.raises(BsedError, match="conv_mode='bf16'"):
+            mine.run_forward(x)
+    assert names == set()
+
+
 @pytest.mark.parametrize("B,T_in,T_out,C", [(2, 78, 156, 256), (3, 156, 313, 256), (1, 5, 11, 8), (2, 7, 7, 4)])
 def test_time_upsample_matches_torch_bilinear_align_corners(B, T_in, T_out, C):
     from bsed_amd import ops
