@@ -9,6 +9,7 @@ re-layout (a 3x3 / stride-2 convolution is a 2x2 / stride-1 one over 4C channels
 channels) keep the im2col lowering (csrc/disc.hip, csrc/igemm.hip, csrc/igemm3.hip).
 """
 import math
+import os
 
 import numpy as np
 import torch
@@ -19,6 +20,11 @@ from . import ops
 from .models import _FlatModule
 
 D_EPS, D_MOM = 1e-5, 0.1
+# Mode of the discriminators' weight gradients and of Clip_Discriminator's data gradients, whatever BSED_DISC_MODE says.
+# The mask sensitivity that makes fp32 the forward default (Clip_Discriminator.__init__) is a property of the FORWARD
+# contractions only (the masks are functions of the forward pre-activations): the backward pass contracts given operands,
+# where split-fp32 costs its usual 2^-16 and nothing is amplified: -2 ms per adversarial step at B = 128 + 128.
+GRAD_MODE = "bf16x3"
 D_CH = [1, 128, 64, 32, 16, 8]
 
 
@@ -84,7 +90,6 @@ class Clip_Discriminator(_FlatModule):
             pspecs += [(f"bn_{k}.weight", (D_CH[k],)), (f"bn_{k}.bias", (D_CH[k],))]
             bspecs += [(f"bn_{k}.running_mean", (D_CH[k],)), (f"bn_{k}.running_var", (D_CH[k],))]
         self._build(pspecs, bspecs, device)
-        import os
         # GEMM family of the convolutions: "fp32" (fp32 matrix cores, the default) or "bf16x3" (split-fp32 operands on
         # the bf16 cores, ~4 % faster adversarial step).  Unlike the CRNN (smooth GLU gates) this network has LeakyReLU
         # between its layers: a forward rounding error eps flips the sign of ~eps of the pre-activations, each flip
@@ -92,10 +97,6 @@ class Clip_Discriminator(_FlatModule):
         # oracle at 24 x 216 x 256: 6e-4 with fp32 GEMMs (what any fp32 implementation gets), 8e-3 with split-fp32.
         # Loss and outputs agree to 3e-7 either way; parity of the gradients is why fp32 is the default here.
         self.conv_mode = os.environ.get("BSED_DISC_MODE", "fp32")
-        # The mask sensitivity is a property of the FORWARD contractions only (the masks are functions of the forward
-        # pre-activations): the data-gradient GEMMs of the backward pass contract given operands, where split-fp32 costs
-        # its usual 2^-16 and nothing is amplified.  They therefore run on the bf16 cores by default (the weight
-        # gradients always did): -2 ms per adversarial step at B = 128 + 128.
         self.nbt = torch.zeros(5, device=device, dtype=torch.int64)
         for k in range(1, 6):
             self.P(f"bn_{k}").register_buffer("num_batches_tracked", self.nbt[k - 1])
@@ -153,12 +154,13 @@ class Clip_Discriminator(_FlatModule):
         return full, K, cop
 
     def _s2d_weight(self, k):
-        """(4 taps, 4*cin, co) weight of the space-to-depth form of conv_k: slot (dp,dq,a,b) = W[2dq+b][2dp+a] or zero"""
+        """view of the (4 taps, 4*cin, co) weight of the space-to-depth form of conv_k: slot (dp,dq,a,b) = W[2dq+b][2dp+a]
+        or zero"""
         co, cin = D_CH[k], D_CH[k - 1]
         w = self.P(f"conv_{k}.weight").detach()
         full = torch.zeros((16, cin, co), device=w.device, dtype=torch.float32)
         full[_S2D_SLOT] = w.permute(2, 3, 1, 0).reshape(9, cin, co)
-        return full.view(4, 4 * cin, co)
+        return ops.WeightView(full, 0, tuple(TAPS2x2), 4 * cin, co, 4 * cin * co, co, 1)
 
     def run_forward(self, feat, n_source=None, save=True):
         """feat (N,T,256) -> (d (N,), ctx).  In train mode (and with n_source) also prepares the BCE backward."""
@@ -180,11 +182,9 @@ class Clip_Discriminator(_FlatModule):
             if k in DIRECT_LAYERS:
                 xp, Hp, Wp = _s2d_fwd(act, scale, shift, N, Ha, Wa, Hi, Wi, cin)
                 assert (Hp - 1, Wp - 1) == (Ho, Wo)
-                wfull = self._s2d_weight(k)
-                K = 4 * cin
-                y, stats = ops.contract(xp, wfull, co, N, Hp, Wp, K, TAPS2x2, K * co, co, 1, mode=self.conv_mode,
-                                        bias=bias, epilogue=epi, valid=(Ho, Wo))
-                rec = dict(direct=True, xp=xp, wfull=wfull, Hp=Hp, Wp=Wp)
+                wv = self._s2d_weight(k)
+                y, stats = ops.contract(xp, wv, N, Hp, Wp, mode=self.conv_mode, bias=bias, epilogue=epi, valid=(Ho, Wo))
+                rec = dict(direct=True, xp=xp, wv=wv, Hp=Hp, Wp=Wp)
                 nHa, nWa = Hp, Wp
             else:
                 if (Ha, Wa) != (Hi, Wi):  # compact copy of the valid extent for the im2col gather (small layers only)
@@ -260,21 +260,18 @@ class Clip_Discriminator(_FlatModule):
         co, cin = D_CH[k], D_CH[k - 1]
         w = self.P(f"conv_{k}.weight")
         if l["direct"]:
-            Hp, Wp, K = l["Hp"], l["Wp"], 4 * cin
+            Hp, Wp, wv = l["Hp"], l["Wp"], l["wv"]
             dy = g.view(N, Hp, Wp, co)
             # the BatchNorm-backward map is affine: it left non-zero values on the grid's non-output row / column
             dy[:, l["Ho"]:, :, :] = 0
             dy[:, :, l["Wo"]:, :] = 0
-            part, G, KP, NP = ops.wgrad(l["xp"], dy, N, Hp, Wp, K, co, taps=TAPS2x2, mode="bf16x3")
-            tmp = torch.empty((4, K, co), device=dy.device, dtype=torch.float32)
-            ops.reduce_partials(part, G, 4, KP, NP, K, co, tmp, K * co, co, 1, accumulate=False, defer=False)
-            w.grad.add_(tmp.view(16, cin, co)[_S2D_SLOT].permute(2, 1, 0).reshape(co, cin, 3, 3))
-            flipped = [(-a, -b) for a, b in TAPS2x2]
-            wd3 = ops.pack_weight3(l["wfull"], 4, co, K, K * co, 1, co)
-            dxp, _ = ops.igemm3(dy, wd3, K, N, Hp, Wp, co, flipped)
+            tmp = torch.empty_like(wv.tensor)
+            ops.weight_grad(l["xp"], dy, wv.over(tmp), N, Hp, Wp, mode=GRAD_MODE, accumulate=False, defer=False)
+            w.grad.add_(tmp[_S2D_SLOT].permute(2, 1, 0).reshape(co, cin, 3, 3))
+            dxp, _ = ops.contract(dy, wv, N, Hp, Wp, mode=GRAD_MODE, direction="dgrad")
             return _s2d_bwd(dxp, p["y"], p["scale"], p["shift"], N, l["Ha_in"], l["Wa_in"], l["Hi"], l["Wi"], cin)
         dy = g.view(l["M"], co)
-        part, G, KP, NP = ops.wgrad(l["col"], dy, 1, l["M"], 1, l["K"], co, mode="bf16x3")
+        part, G, KP, NP = ops.wgrad(l["col"], dy, 1, l["M"], 1, l["K"], co, mode=GRAD_MODE)
         if cin == 1:
             ops.reduce_partials(part, G, 1, KP, NP, 9, co, w.grad, 0, 1, 9)
         else:
@@ -324,7 +321,6 @@ class Frame_Discriminator(_FlatModule):
         L._require_gpu()
         self.dropout_p = float(dropout)
         self.seed = 0
-        import os
         self.conv_mode = os.environ.get("BSED_DISC_MODE", "fp32")
         pspecs = [("dense_d_1.weight", (128, 256)), ("dense_d_1.bias", (128,)),
                   ("dense_d_2.weight", (32, 128)), ("dense_d_2.bias", (32,)),
@@ -343,17 +339,17 @@ class Frame_Discriminator(_FlatModule):
     def set_seed(self, seed):
         self.seed = int(seed)
 
-    def _linear(self, x, name, M, K, N):
+    def _linear(self, x, name, M):
         w, b = self.P(name + ".weight"), self.P(name + ".bias")
-        return ops.contract(x, w, N, 1, M, 1, K, ops.TAP1, 0, 1, K, mode=self.conv_mode, bias=b)[0]
+        return ops.contract(x, ops.linear_weight(w), 1, M, 1, mode=self.conv_mode, bias=b)[0]
 
-    def _linear_bwd(self, x, dy, name, M, K, N):
+    def _linear_bwd(self, x, dy, name, M):
         """accumulates dW, db of y = x W^T + b; returns dL/dx (M,K)"""
         w, b = self.P(name + ".weight"), self.P(name + ".bias")
-        ops.colsum(dy, M, N, N, b.grad)
-        part, G, KP, NP = ops.wgrad(x, dy, 1, M, 1, K, N, mode="bf16x3")
-        ops.reduce_partials(part, G, 1, KP, NP, K, N, w.grad, 0, 1, K)
-        return ops.contract(dy, w, K, 1, M, 1, N, ops.TAP1, 0, K, 1, mode=self.conv_mode)[0]
+        wv = ops.linear_weight(w)
+        ops.colsum(dy, M, wv.N, wv.N, b.grad)
+        ops.weight_grad(x, dy, wv.over(w.grad), 1, M, 1, mode=GRAD_MODE)
+        return ops.contract(dy, wv, 1, M, 1, mode=self.conv_mode, direction="dgrad")[0]
 
     def _act(self, a, stream_id, drop):
         out = torch.empty_like(a)
@@ -375,9 +371,9 @@ class Frame_Discriminator(_FlatModule):
         M = N * T
         drop = self.dropout_p if self.training else 0.0
         x2d = x.view(M, 256)
-        a1 = self._linear(x2d, "dense_d_1", M, 256, 128).view(M, 128)
+        a1 = self._linear(x2d, "dense_d_1", M).view(M, 128)
         h1 = self._act(a1, 401, drop)
-        a2 = self._linear(h1, "dense_d_2", M, 128, 32).view(M, 32)
+        a2 = self._linear(h1, "dense_d_2", M).view(M, 32)
         h2 = self._act(a2, 402, drop)
         d = torch.empty((M,), device=x.device, dtype=torch.float32)
         w3, b3 = self.P("dense_d_3.weight"), self.P("dense_d_3.bias")
@@ -400,9 +396,9 @@ class Frame_Discriminator(_FlatModule):
         ops.stats_to_grad(part, 32, 1, tmp)
         ops.axpy(b3.grad, tmp[:1])
         da2 = self._act_bwd(dh2, ctx["a2"], 402, ctx["drop"], ctx["seed"])
-        dh1 = self._linear_bwd(ctx["h1"], da2, "dense_d_2", M, 128, 32).view(M, 128)
+        dh1 = self._linear_bwd(ctx["h1"], da2, "dense_d_2", M).view(M, 128)
         da1 = self._act_bwd(dh1, ctx["a1"], 401, ctx["drop"], ctx["seed"])
-        dx = self._linear_bwd(ctx["x"], da1, "dense_d_1", M, 256, 128)
+        dx = self._linear_bwd(ctx["x"], da1, "dense_d_1", M)
         N, T = ctx["shape"]
         return dx.view(N, T, 256)
 

@@ -309,26 +309,13 @@ class CRNN(_FlatModule):
         return torch.nn.modules.module._IncompatibleKeys(missing, unexpected)
 
     # ------------------------------------------------------------------ forward
-    def _rnn_views(self, l, prefix="rnn"):
+    def _rnn_views(self, arena, l, prefix="rnn"):
+        """(nin, w_ih, w_hh, b_ih, b_hh) of GRU layer l as slices of `arena` (flat or flat_grad), each covering both
+        directions"""
         H = self.n_hidden
         nin = self.nb_filters[-1] if l == 0 else 2 * H
-        o = self._poff
-        base = f"{prefix}.rnn."
-        w_ih = self.flat[o[f"{base}weight_ih_l{l}"]:o[f"{base}weight_ih_l{l}"] + 6 * H * nin]
-        w_hh = self.flat[o[f"{base}weight_hh_l{l}"]:o[f"{base}weight_hh_l{l}"] + 6 * H * H]
-        b_ih = self.flat[o[f"{base}bias_ih_l{l}"]:o[f"{base}bias_ih_l{l}"] + 6 * H]
-        b_hh = self.flat[o[f"{base}bias_hh_l{l}"]:o[f"{base}bias_hh_l{l}"] + 6 * H]
-        return nin, w_ih, w_hh, b_ih, b_hh
-
-    def _rnn_grads(self, l, prefix="rnn"):
-        H = self.n_hidden
-        nin = self.nb_filters[-1] if l == 0 else 2 * H
-        o, g = self._poff, self.flat_grad
-        base = f"{prefix}.rnn."
-        return (g[o[f"{base}weight_ih_l{l}"]:o[f"{base}weight_ih_l{l}"] + 6 * H * nin],
-                g[o[f"{base}weight_hh_l{l}"]:o[f"{base}weight_hh_l{l}"] + 6 * H * H],
-                g[o[f"{base}bias_ih_l{l}"]:o[f"{base}bias_ih_l{l}"] + 6 * H],
-                g[o[f"{base}bias_hh_l{l}"]:o[f"{base}bias_hh_l{l}"] + 6 * H])
+        off = [self._poff[f"{prefix}.rnn.{kind}_l{l}"] for kind in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
+        return (nin,) + tuple(arena[o:o + 6 * H * n] for o, n in zip(off, (nin, H, 1, 1)))
 
     # ------------------------------------------------------------------ building blocks
     def _block_forward(self, a, B, Hh, Ww, cin, co, pool, names, drop, rng_stream, nbt, train, first=False, bn_pre=None):
@@ -336,7 +323,6 @@ class CRNN(_FlatModule):
         glu-linear) parameter prefixes.  Returns (pooled, saved-for-backward dict)."""
         ph, pw = pool
         cw, cb = self.P(names[0] + ".weight"), self.P(names[0] + ".bias")
-        taps, wsrc, s_tap = self._conv_taps(cw, Ww)
         if first and co == 16 and self.block0_fused and 1 < Ww <= 256 and B * Hh * Ww < (1 << 31):
             return self._block0_forward(a, B, Hh, Ww, pool, names, drop, rng_stream, nbt, train, bn_pre)
         if self.conv_mode == "bf16" and (first or a.dtype != torch.bfloat16):
@@ -345,8 +331,7 @@ class CRNN(_FlatModule):
             y, stats = ops.conv0_fwd(a, cw, cb, B, Hh, Ww, co, want_stats=train)
         else:
             epi = ops.EPI_STATS if train else ops.EPI_PLAIN
-            y, stats = ops.contract(a, wsrc, co, B, Hh, Ww, cin, taps, s_tap, 9, cin * 9, mode=self.conv_mode, bias=cb,
-                                    epilogue=epi, resident=cin == 16 and ops.igemm3s_supported(Ww, cin))
+            y, stats = ops.contract(a, ops.conv3x3_weight(cw, Ww), B, Hh, Ww, mode=self.conv_mode, bias=cb, epilogue=epi)
         bn = self.P(names[1])
         if train:
             mean, invstd, scale, shift = ops.bn_finalize(stats, co, float(B * Hh * Ww), BN_EPS, BN_MOMENTUM,
@@ -395,20 +380,12 @@ class CRNN(_FlatModule):
                           bn.bias.grad, None, blk["inp"], apply=False)
         ops.block0_wgrad_finish(pgx, G, blk["xr64"], coef, blk["mean"], cw, cb, cw.grad)
 
-    @staticmethod
-    def _conv_taps(cw, Ww):
-        """taps of a 3x3 / pad 1 convolution and how to find their weights.  On a width-1 map (the FPN levels) the six
-        taps with dw != 0 only ever see zero padding: the convolution is exactly its centre column, a 3x1 stencil."""
-        if Ww > 1:
-            return ops.TAPS3x3, cw, 1
-        return ((-1, 0), (0, 0), (1, 0)), cw.view(-1)[1:], 3   # weight[co][ci][kh][1]: element offset 1, tap stride 3
-
     def _gru_forward(self, seq, B, T, prefix, save):
         """2-layer BiGRU (reference src/models/RNN.py:7-16): input projections as one GEMM, then the recurrence"""
         layers = []
         for l in range(2):
-            nin, w_ih, w_hh, b_ih, b_hh = self._rnn_views(l, prefix)
-            xp, _ = ops.contract(seq, w_ih, 768, 1, B * T, 1, nin, ops.TAP1, 0, 1, nin, mode=self.conv_mode, bias=b_ih)
+            nin, w_ih, w_hh, b_ih, b_hh = self._rnn_views(self.flat, l, prefix)
+            xp, _ = ops.contract(seq, ops.linear_weight(w_ih, 768, nin), 1, B * T, 1, mode=self.conv_mode, bias=b_ih)
             if l == 0 and self.rnn_hook is not None:
                 # one-shot: independent work for the chip's idle half while the recurrences run (SEDTrainer enqueues
                 # the next batch's mel transform on its feature stream here)
@@ -431,21 +408,19 @@ class CRNN(_FlatModule):
 
     def _gru_param_grads(self, lay, l, prefix, dxp, dgh, pih, phh, B, T):
         """bias and weight gradients of GRU layer l from its recurrence outputs (no consumer inside the backward pass)"""
-        nin, w_ih, w_hh, b_ih, b_hh = self._rnn_views(l, prefix)
-        g_wih, g_whh, g_bih, g_bhh = self._rnn_grads(l, prefix)
+        nin, g_wih, g_whh, g_bih, g_bhh = self._rnn_views(self.flat_grad, l, prefix)
         if pih is not None:  # the recurrence kernel already summed the bias gradients over time per batch row
             ops.colsum(pih, pih.shape[0], 768, 768, g_bih)
             ops.colsum(phh, phh.shape[0], 768, 768, g_bhh)
         else:
             ops.colsum(dxp, B * T, 768, 768, g_bih)
             ops.colsum(dgh, B * T, 768, 768, g_bhh)
-        part, G, KP, NP = ops.wgrad(lay["inp"], dxp, 1, B * T, 1, nin, 768, mode=self.conv_mode)
-        ops.reduce_partials(part, G, 1, KP, NP, nin, 768, g_wih, 0, 1, nin)
+        ops.weight_grad(lay["inp"], dxp, ops.linear_weight(g_wih, 768, nin), 1, B * T, 1, mode=self.conv_mode)
         for dr in range(2):
-            part, G, KP, NP = ops.wgrad(lay["out"], dgh, B, T, 1, 128, 384, taps=((-1 if dr == 0 else 1, 0),),
-                                        in_pitch=256, dy_pitch=768, in_offset=dr * 128, dy_offset=dr * 384,
-                                        mode=self.conv_mode)
-            ops.reduce_partials(part, G, 1, KP, NP, 128, 384, g_whh, 0, 1, 128, dst_offset=dr * 384 * 128)
+            # direction dr's (384, 128) half of w_hh contracts h[t - 1] (forward) or h[t + 1] (reverse): one tap, a time shift
+            gv = ops.WeightView(g_whh, dr * 384 * 128, ((-1 if dr == 0 else 1, 0),), 128, 384, 0, 1, 128)
+            ops.weight_grad(lay["out"], dgh, gv, B, T, 1, mode=self.conv_mode, in_pitch=256, dy_pitch=768,
+                            in_offset=dr * 128, dy_offset=dr * 384)
 
     def _gru_backward(self, layers, d, B, T, prefix):
         """returns dL/d(input sequence) (B,T,nin of layer 0); parameter gradients accumulate into flat_grad.  The
@@ -453,7 +428,7 @@ class CRNN(_FlatModule):
         downstream needs a layer's WEIGHT gradients: they are enqueued on a side stream, where they run beside the next
         layer's recurrence (and, for layer 0, beside the head of the CNN backward).  `_join_side` closes the fork."""
         for l in (1, 0):
-            nin, w_ih, w_hh, b_ih, b_hh = self._rnn_views(l, prefix)
+            nin, w_ih, w_hh, b_ih, b_hh = self._rnn_views(self.flat, l, prefix)
             lay = layers[l]
             dxp, dgh, pih, phh = ops.gru_bwd(d, lay["out"], lay["gates"], w_hh, B, T, mode=self._rnn_mode)
             if self.overlap_rnn:
@@ -466,7 +441,8 @@ class CRNN(_FlatModule):
                         t.record_stream(side)               # the allocator must not recycle them under the side stream
             else:
                 self._gru_param_grads(lay, l, prefix, dxp, dgh, pih, phh, B, T)
-            d, _ = ops.contract(dxp, w_ih, nin, 1, B * T, 1, 768, ops.TAP1, 0, nin, 1, mode=self.conv_mode)
+            d, _ = ops.contract(dxp, ops.linear_weight(w_ih, 768, nin), 1, B * T, 1, mode=self.conv_mode,
+                                direction="dgrad")
             d = d.view(B, T, nin)
         return d
 
@@ -474,7 +450,7 @@ class CRNN(_FlatModule):
         """backward of one conv/BN/GLU/dropout/pool block; returns dL/d(block input) or None for the first block"""
         if blk["first"] and blk["y"] is None:
             return self._block0_backward(blk, dpool, B, seed)
-        Hh, Ww, cin, co = blk["H"], blk["W"], blk["cin"], blk["co"]
+        Hh, Ww, co = blk["H"], blk["W"], blk["co"]
         y = blk["y"]
         conv_n, bn_n, glu_n = blk["names"]
         glu, bn = self.P(glu_n), self.P(bn_n)
@@ -491,30 +467,24 @@ class CRNN(_FlatModule):
             part, G = ops.conv0_wgrad(blk["inp"], g, B, Hh, Ww, co, y=y, coef=coef, mean=blk["mean"])
             ops.reduce_partials(part, G, 9, 1, co, 1, co, cw.grad, 1, 9, 9)
             return None
-        taps, wsrc, s_tap = self._conv_taps(cw, Ww)
+        wv = ops.conv3x3_weight(cw, Ww)
         if self._mfma3:
             # (4) BatchNorm backward applied on load inside the weight-gradient kernel (d_y = A g + B (y - mean) + C),
             # which also writes d_y once for the data gradient: the separate apply pass over g and y is gone
             coef = ops.bn_bwd(st2, co, float(B * Hh * Ww), bn.weight, blk["mean"], blk["invstd"], bn.weight.grad,
                               bn.bias.grad, g, y, apply=False)
             dy = torch.empty_like(g) if need_dgrad else None
-            part, G, KP, NP = ops.wgrad(blk["inp"], g, B, Hh, Ww, cin, co, taps=taps, mode=self.conv_mode, bn_y=y,
-                                        bn_coef=coef, bn_mean=blk["mean"], dy_out=dy)
+            ops.weight_grad(blk["inp"], g, wv.over(cw.grad), B, Hh, Ww, mode=self.conv_mode, bn_y=y, bn_coef=coef,
+                            bn_mean=blk["mean"], dy_out=dy)
         else:
             # (4) BatchNorm backward -> d_y in place
             ops.bn_bwd(st2, co, float(B * Hh * Ww), bn.weight, blk["mean"], blk["invstd"], bn.weight.grad,
                        bn.bias.grad, g, y)
             dy = g
-            part, G, KP, NP = ops.wgrad(blk["inp"], dy, B, Hh, Ww, cin, co, taps=taps, mode=self.conv_mode)
-        ops.reduce_partials(part, G, len(taps), KP, NP, cin, co, cw.grad, s_tap, 9, cin * 9,
-                            dst_offset=0 if Ww > 1 else 1)
+            ops.weight_grad(blk["inp"], dy, wv.over(cw.grad), B, Hh, Ww, mode=self.conv_mode)
         if not need_dgrad:
             return None
-        flipped = [(-a, -b) for a, b in taps]
-        # data gradient of a 32-channel layer: all taps' weights resident in LDS (csrc/igemm3.hip, igemm3s)
-        d_in, _ = ops.contract(dy, wsrc, cin, B, Hh, Ww, co, flipped, s_tap, cin * 9, 9, mode=self.conv_mode,
-                               resident=co == 32 and cin <= 32 and ops.igemm3s_supported(Ww, co))
-        return d_in
+        return ops.contract(dy, wv, B, Hh, Ww, mode=self.conv_mode, direction="dgrad")[0]
 
     def _cnn_forward(self, x, ctx):
         """the seven conv/BN/GLU/dropout/pool blocks; returns (a (B,T',1,C), T')"""
@@ -675,16 +645,16 @@ class CRNN_fpn(CRNN):
     # 1x1 convolution over channels of a (B,T,512) sequence == GEMM with the (256,512) weight
     def _fuse(self, cat, name, B, T):
         w, b = self.P(name + ".weight"), self.P(name + ".bias")
-        out, _ = ops.contract(cat, w, 256, 1, B * T, 1, 512, ops.TAP1, 0, 1, 512, mode=self._fuse_mode, bias=b)
+        out, _ = ops.contract(cat, ops.linear_weight(w, 256, 512), 1, B * T, 1, mode=self._fuse_mode, bias=b)
         return out.view(B, T, 256)
 
     def _fuse_backward(self, cat, d_out, name, B, T):
         """accumulates dW, db of the 1x1 convolution; returns dL/d(cat) (B,T,512)"""
         w, b = self.P(name + ".weight"), self.P(name + ".bias")
         ops.colsum(d_out, B * T, 256, 256, b.grad)
-        part, G, KP, NP = ops.wgrad(cat, d_out, 1, B * T, 1, 512, 256, mode=self.conv_mode)
-        ops.reduce_partials(part, G, 1, KP, NP, 512, 256, w.grad, 0, 1, 512)
-        d_cat, _ = ops.contract(d_out, w, 512, 1, B * T, 1, 256, ops.TAP1, 0, 512, 1, mode=self._fuse_mode)
+        wv = ops.linear_weight(w, 256, 512)
+        ops.weight_grad(cat, d_out, wv.over(w.grad), 1, B * T, 1, mode=self.conv_mode)
+        d_cat, _ = ops.contract(d_out, wv, 1, B * T, 1, mode=self._fuse_mode, direction="dgrad")
         return d_cat.view(B, T, 512)
 
     def run_forward(self, x, save=True):
@@ -791,7 +761,7 @@ class CRNN_pred(CRNN):
             C = self.nclass
             feats = (a if a.dtype == torch.float32 else a.float()).view(B, T, C)   # bf16 mode: the head stays fp32
             w, b = self.P("dense_softmax.weight"), self.P("dense_softmax.bias")
-            logits, _ = ops.contract(feats, w, C, 1, B * T, 1, C, ops.TAP1, 0, 1, C, mode=self.conv_mode, bias=b)
+            logits, _ = ops.contract(feats, ops.linear_weight(w), 1, B * T, 1, mode=self.conv_mode, bias=b)
         return ops.tag_head_fwd(feats, logits.view(B, T, C))
 
     def run_backward(self, ctx, d):

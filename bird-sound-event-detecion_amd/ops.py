@@ -2,6 +2,8 @@
 function fills a descriptor with device pointers / shapes and launches HIP kernels on the current
 stream.  Activations are NHWC fp32 tensors."""
 import ctypes
+import os
+from typing import NamedTuple
 
 import torch
 
@@ -18,6 +20,50 @@ IgemmDesc, WgradDesc, HeadBwdDesc, PackJob, ReduceJob, BnEvalJob = (L.STRUCTS["B
 
 TAPS3x3 = [(kh - 1, kw - 1) for kh in range(3) for kw in range(3)]
 TAP1 = ((0, 0),)   # a plain GEMM: (positions, CIN) x (CIN, N)
+
+
+class WeightView(NamedTuple):
+    """A weight as a contraction reads it: w[tap][k][n] = tensor.view(-1)[offset + tap * s_tap + k * s_k + n * s_n] for
+    the `taps` (dh, dw) input offsets, k < K input and n < N output channels.  conv3x3_weight and linear_weight build the
+    views of torch's layouts; contract and weight_grad take nothing else for a weight or its gradient."""
+    tensor: torch.Tensor
+    offset: int
+    taps: tuple
+    K: int
+    N: int
+    s_tap: int
+    s_k: int
+    s_n: int
+
+    def dgrad(self):
+        """the view the data gradient contracts with: the transposed weight at the mirrored taps"""
+        return self._replace(taps=tuple((-a, -b) for a, b in self.taps), K=self.N, N=self.K, s_k=self.s_n, s_n=self.s_k)
+
+    def over(self, tensor):
+        """the same geometry over another tensor of the same layout (the weight's gradient)"""
+        return self._replace(tensor=tensor)
+
+    def source(self):
+        """the tensor from `offset` on: what the pack kernels read"""
+        return self.tensor.view(-1)[self.offset:] if self.offset else self.tensor
+
+
+def conv3x3_weight(w, W):
+    """View of a (co, cin, 3, 3) weight for the 3x3 / pad 1 convolution of a width-W map.  On a width-1 map (the FPN
+    levels) the six taps with dw != 0 only ever see zero padding: the convolution is exactly its centre column, a 3x1
+    stencil over weight[co][ci][kh][1] (element offset 1, tap stride 3)."""
+    co, cin = w.shape[:2]
+    if W > 1:
+        return WeightView(w, 0, tuple(TAPS3x3), cin, co, 1, 9, cin * 9)
+    return WeightView(w, 1, ((-1, 0), (0, 0), (1, 0)), cin, co, 3, 9, cin * 9)
+
+
+def linear_weight(w, N=None, K=None):
+    """View of an (N, K) matrix of y = x W^T, or -- with N and K given -- of a flat slice holding one (the GRU's (768, nin)
+    double-direction slices of the arena, a (N, K, 1, 1) convolution weight)"""
+    if N is None:
+        N, K = w.shape
+    return WeightView(w, 0, TAP1, K, N, 0, 1, K)
 
 
 class KernelTimer:
@@ -335,7 +381,6 @@ def igemm3_nsplit():
     """True: ops.igemm3 runs the round-3 kernel (csrc/igemm3n.hip: a wave owns 32 output channels, weight fragments
     straight from global memory, one barrier per 32-channel chunk) and pack_weight3 emits its fragment-order table;
     BSED_IGEMM3N=0 = the slab kernel of rounds 1-2 (csrc/igemm3.hip)."""
-    import os
     return os.environ.get("BSED_IGEMM3N", "1") != "0"
 
 
@@ -400,7 +445,7 @@ def igemm3(inp, w3, N, NB, H, W, CIN, taps, bias=None, epilogue=EPI_PLAIN, valid
     if w3.dim() == 6:
         return _igemm3n(inp, w3, N, NB, H, W, CIN, taps, bias, epilogue, valid)
     if inp.dtype != torch.float32:
-        raise L.BsedError("bf16 activations need the N-split kernel (BSED_IGEMM3N=1)")
+        raise L.BsedError("bf16 activations need the N-split route of igemm3 (igemm3_nsplit()), not the slab kernel")
     NP = w3.shape[2]
     d, ntiles = _igemm_desc(NB, H, W, CIN, N, NP, taps, epilogue, valid)
     bn = 128 if NP % 128 == 0 else (64 if NP % 64 == 0 else 32)
@@ -448,22 +493,40 @@ def _igemm3n(inp, wtab, N, NB, H, W, CIN, taps, bias, epilogue, valid):
     return out, stats
 
 
-def contract(inp, wsrc, N, NB, H, W, CIN, taps, s_tap, s_k, s_n, *, mode, bias=None, epilogue=EPI_PLAIN, valid=None,
-             resident=False):
-    """Pack the weights wsrc[tap * s_tap + k * s_k + n * s_n] (k < CIN, n < N) and run the PLAIN / STATS contraction
-    with them.  Returns (out, stats or None).  mode: the caller's conv_mode.  "fp32" = the fp32-core kernel (igemm);
-    "bf16x3" / "bf16" = the bf16 cores: igemm3s where the caller says its table may stay `resident` in LDS
-    (igemm3s_supported and the layer's own condition), igemm3 (slab or N-split, as igemm3_nsplit() says) for CIN a
-    multiple of 32, and the fp32-core kernel for the channel counts neither is built for."""
+def contract_route(direction, CIN, N, W, ntaps, mode):
+    """Name of the kernel that runs the PLAIN / STATS contraction of CIN input with N output channels over ntaps taps on a
+    width-W map, in the contraction's own terms (a data gradient has the layer's CIN and N swapped).  The only place that
+    compares them with mode (the caller's conv_mode); contract switches on the name, and a new contraction kernel is
+    wired in here."""
     if mode not in ("fp32", "bf16x3", "bf16"):
-        raise L.BsedError(f"contract: unknown mode {mode!r}")
-    if mode != "fp32" and resident:
-        wtab = pack_weight3s(wsrc, len(taps), N, s_tap, s_k, s_n, K=CIN)
+        raise L.BsedError(f"contract_route: unknown mode {mode!r}")
+    if direction not in ("forward", "dgrad"):
+        raise L.BsedError(f"contract_route: unknown direction {direction!r}")
+    if mode == "fp32":
+        return "igemm"        # the fp32-core kernel (csrc/igemm.hip)
+    if ntaps == 9 and (CIN == 16 and igemm3s_supported(W, 16) if direction == "forward" else
+                       CIN == 32 and N <= 32 and igemm3s_supported(W, 32)):
+        return "igemm3s"      # the bf16 cores, all taps' weights resident in LDS (csrc/igemm3.hip)
+    if CIN % 32 == 0:
+        return "igemm3"       # the bf16 cores: slab or N-split kernel, as igemm3_nsplit() says
+    return "igemm"            # channel counts neither bf16-core kernel is built for
+
+
+def contract(inp, wv, NB, H, W, *, mode, direction="forward", bias=None, epilogue=EPI_PLAIN, valid=None):
+    """Pack the weights of the WeightView wv and run the PLAIN / STATS contraction with them on the kernel contract_route
+    names.  direction="dgrad": wv is the layer's forward view and inp the gradient of its output; the contraction runs
+    over wv.dgrad().  Returns (out, stats or None).  mode: the caller's conv_mode."""
+    if direction == "dgrad":
+        wv = wv.dgrad()
+    src, taps, CIN, N, strides = wv.source(), wv.taps, wv.K, wv.N, wv[5:]
+    route = contract_route(direction, CIN, N, W, len(taps), mode)
+    if route == "igemm3s":
+        wtab = pack_weight3s(src, len(taps), N, *strides, K=CIN)
         return igemm3s(inp, wtab, N, NB, H, W, taps, bias=bias, epilogue=epilogue)
-    if mode != "fp32" and CIN % 32 == 0:
-        w3 = pack_weight3(wsrc, len(taps), CIN, N, s_tap, s_k, s_n)
+    if route == "igemm3":
+        w3 = pack_weight3(src, len(taps), CIN, N, *strides)
         return igemm3(inp, w3, N, NB, H, W, CIN, taps, bias=bias, epilogue=epilogue, valid=valid)
-    wpk = pack_weight(wsrc, len(taps), CIN, N, s_tap, s_k, s_n)
+    wpk = pack_weight(src, len(taps), CIN, N, *strides)
     return igemm(inp, wpk, N, NB, H, W, CIN, taps=taps, bias=bias, epilogue=epilogue, valid=valid)
 
 
@@ -573,6 +636,15 @@ def reduce_partials(part, G, ntaps, KP, NP, K, N, dst, s_tap, s_k, s_n, accumula
     _note("reduce_partials_kernel", f"G{G}", float(part.numel()), 4.0 * part.numel())
     L.call("bsed_reduce_partials", L.ptr(part), G, ntaps, KP, NP, K, N, _dp(dst, dst_offset), s_tap, s_k, s_n,
            1 if accumulate else 0, L.stream())
+
+
+def weight_grad(inp, dy, gv, NB, H, W, *, mode, accumulate=True, defer=True, **kw):
+    """dW of the contraction whose forward weight view has gv's geometry, from its input and the gradient dy of its
+    output, reduced into gv (a view .over() the gradient tensor).  **kw: wgrad's pitches, offsets, a_scale / a_shift and
+    bn_* / dy_out fusion arguments."""
+    part, G, KP, NP = wgrad(inp, dy, NB, H, W, gv.K, gv.N, taps=gv.taps, mode=mode, **kw)
+    reduce_partials(part, G, len(gv.taps), KP, NP, gv.K, gv.N, gv.tensor, gv.s_tap, gv.s_k, gv.s_n, accumulate=accumulate,
+                    dst_offset=gv.offset, defer=defer)
 
 
 _scratch = {}
@@ -820,8 +892,7 @@ def glu_backward(y, scale, shift, w, bias, dpool, B, H, W, C, pool, drop_p, rng_
                               a_scale=scale, a_shift=shift, e_src=y, e_scale=scale, e_shift=shift, e_dpool=dpool,
                               out2=tt, pool=pool, drop_p=drop_p, rng_stream=rng_stream, seed=seed)
         stats_to_grad(pdb, C, 0, db)
-        part, G, KP, NP = wgrad(y, dlin, B, H, W, C, C, a_scale=scale, a_shift=shift, mode=mode)
-        reduce_partials(part, G, 1, KP, NP, C, C, dw, 0, 1, C)
+        weight_grad(y, dlin, linear_weight(dw), B, H, W, a_scale=scale, a_shift=shift, mode=mode)
         if route == "unfused":          # (3) g = d_lin @ W_glu + gate term, with the BatchNorm-backward sums
             g, st2 = igemm(dlin, pack_weight(w, 1, C, C, 0, C, 1), C, B, H, W, C, epilogue=EPI_ADD_STATS2, out=tt,
                            out2=tt, e_src=y)
