@@ -1150,3 +1150,34 @@ def upsample_time_bwd(dout, T_in, C, in_offset=0):
     din = torch.empty((B, T_in, C), device=dout.device, dtype=torch.float32)
     L.call("bsed_upsample_time_bwd", _dp(dout, in_offset), L.ptr(din), B, T_in, T_out, C, P, C, L.stream())
     return din
+
+
+def synth_mix(bank, bg_off, bg_len, bg_phase, bg_gain, n_ev, src, on, length, g, inv_fade, B, n, K, coverage=0.0, out=None):
+    """``bsed_synth_mix``: B clips of n samples mixed from the flat fp32 ``bank`` (include/bsed.h states the arithmetic).
+    The tables are device tensors: bg_off / bg_len / bg_phase (B) and src / on / length (B, K) int64, bg_gain (B) and
+    g / inv_fade (B, K) float32, n_ev (B) int32.  coverage: the mean number of events over an output sample (for the
+    work announcement alone) -> (B, n) float32."""
+    if out is None:
+        out = torch.empty((B, n), device=bank.device, dtype=torch.float32)
+    elif tuple(out.shape) != (B, n):
+        raise L.BsedError(f"synth_mix: out must be ({B}, {n}), got {tuple(out.shape)}")
+    i64 = torch.int64
+    # bytes: the output, the background and `coverage` snippet samples per output sample; flops: a multiply for the
+    # background, two multiplies for the fade, the fade product and the multiply-add per covered sample
+    _note("synth_mix_kernel", f"n{n} K{K}", B * n * (1.0 + 5.0 * coverage), 4.0 * B * n * (2.0 + coverage))
+    L.call("bsed_synth_mix", L.ptr(bank), bank.numel(), L.ptr(bg_off, i64), L.ptr(bg_len, i64), L.ptr(bg_phase, i64),
+           L.ptr(bg_gain), L.ptr(n_ev, torch.int32), L.ptr(src, i64), L.ptr(on, i64), L.ptr(length, i64), L.ptr(g),
+           L.ptr(inv_fade), B, n, K, L.ptr(out), L.stream())
+    return out
+
+
+def synth_targets(n_ev, cls, on_f, off_f, B, K, T, C):
+    """``bsed_synth_targets``: int32 device tables n_ev (B) and cls / on_f / off_f (B, K) -> (strong (B, T, C),
+    weak (B, C)) float32, every element written by the one launch."""
+    strong = torch.empty((B, T, C), device=n_ev.device, dtype=torch.float32)
+    weak = torch.empty((B, C), device=n_ev.device, dtype=torch.float32)
+    i32 = torch.int32
+    _note("synth_targets_kernel", f"T{T} C{C}", 0.0, 4.0 * B * C * (T + 1))
+    L.call("bsed_synth_targets", L.ptr(n_ev, i32), L.ptr(cls, i32), L.ptr(on_f, i32), L.ptr(off_f, i32), B, K, T, C,
+           L.ptr(strong), L.ptr(weak), L.stream())
+    return strong, weak

@@ -590,6 +590,40 @@ int bsed_tag_masks(const float* scores, int T_scores, const float* class_thresho
 int bsed_resample_poly(const void* in, int format, long n_in, int channels, const float* table, int up, int down,
                        int half_len, float* out, long n_out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Soundscape synthesis (csrc/synth.hip).  stands in for the reference's offline desed / scaper generation of the SYN set
+ * (src/synth_data/synth_data_preprocess.py:116-188): strongly labelled clips are mixed on the device from a resident bank
+ * of event snippets and backgrounds.  The sampling and the loudness model are this project's own (synth.py): no parity
+ * with scaper's LUFS levels or desed's draws is claimed.
+ * ---------------------------------------------------------------------------------------------- */
+#define BSED_SYNTH_MAX_EVENTS 16
+/* bank: (bank_len) float32, every snippet and background back to back -> out (B, n) float32.  Clip b has a background
+ * (bg_off[b], bg_len[b], bg_phase[b]: int64, bank offset / length / start phase in samples; bg_gain[b]: float32) and
+ * n_ev[b] (int32, clamped to 0..K) events; event k of clip b is row-major entry [b * K + k] of src (int64: bank offset of
+ * its first sample), on (int64: clip sample of its first sample), len (int64: samples), g and inv_fade (float32).
+ * Sample j of clip b, in fp32 and in exactly this order:
+ *   acc = bank[bg_off + (bg_phase + j) % bg_len] * bg_gain                          (0 when bg_len <= 0: silence)
+ *   for k = 0 .. n_ev - 1, if on <= j < on + len, with i = j - on:
+ *     w   = fminf(fminf(1, (float)(i + 1) * inv_fade), fminf(1, (float)(len - i) * inv_fade))
+ *     acc = fmaf(bank[src + i] * w, g, acc)
+ *   out[b][j] = acc
+ * one fp32 sum per output in a fixed order, no atomics, independent of the launch partition and of B, bitwise
+ * repeatable.  (% is the non-negative remainder.)  The tables are device memory and are not validated (synth.py validates
+ * a plan before it uploads it); whatever they hold, no bank index outside 0 .. bank_len - 1 is dereferenced -- such a
+ * sample reads as 0 -- and nothing outside out is written.
+ * Refused before any launch: null pointers; B < 1; n < 1; K outside 0..BSED_SYNTH_MAX_EVENTS; bank_len < 1; out not
+ * 16-byte aligned; a table not aligned to its element size. */
+int bsed_synth_mix(const float* bank, long bank_len, const long* bg_off, const long* bg_len, const long* bg_phase,
+                   const float* bg_gain, const int* n_ev, const long* src, const long* on, const long* len,
+                   const float* g, const float* inv_fade, int B, long n, int K, float* out, void* stream);
+/* the targets of such a batch.  n_ev (B) and cls, on_f, off_f (B, K), all int32: class, first frame and end frame of
+ * every event -> strong (B, T, C): 1 where some event k < n_ev[b] of class c has on_f <= t < off_f, else 0; weak (B, C):
+ * the maximum of strong over t.  Every element is written, in one launch.  An event with off_f <= on_f, or with a class
+ * outside 0..C-1, contributes nothing; frames outside 0..T-1 are clipped.
+ * Refused before any launch: null pointers; B, T or C < 1; K outside 0..BSED_SYNTH_MAX_EVENTS; misaligned pointers. */
+int bsed_synth_targets(const int* n_ev, const int* cls, const int* on_f, const int* off_f, int B, int K, int T, int C,
+                       float* strong, float* weak, void* stream);
+
 typedef struct BsedHeadBwdDesc {
   const float* x;            /* (B,T,K) encoder output */
   const float* w;            /* (2C,K) */
