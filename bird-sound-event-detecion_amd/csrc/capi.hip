@@ -15,7 +15,7 @@ void bsed_set_error(const char* fmt, ...) {
 extern "C" const char* bsed_last_error(void) { return g_err; }
 extern "C" const char* bsed_build_info(void) { return "libbsed gfx950: fp32 storage/accumulation, split-fp32 (bf16x3) contractions on v_mfma_f32_32x32x16_bf16 by default, "
          "exact-fp32 v_mfma_f32_32x32x2_f32 kernels selectable (hand-written HIP)"; }
-extern "C" int bsed_abi_version(void) { return 9; }   // 9: soundscape synthesis (csrc/synth.hip); 8: Predictor head for 1..64 classes + bsed_head_lds_bytes (csrc/head.hip); 7: clip-level tagging counts + pseudo-label masks (csrc/tagging.hip); 6: threshold sweep + event F1 counts (csrc/metrics.hip); 5: resampling (csrc/resample.hip); 4: recording-level detection (csrc/detect.hip)
+extern "C" int bsed_abi_version(void) { return 10; }   // 10: dataset scaler statistics + normalised dB kernels (csrc/scaler.hip, csrc/mel.hip); 9: soundscape synthesis (csrc/synth.hip); 8: Predictor head for 1..64 classes + bsed_head_lds_bytes (csrc/head.hip); 7: clip-level tagging counts + pseudo-label masks (csrc/tagging.hip); 6: threshold sweep + event F1 counts (csrc/metrics.hip); 5: resampling (csrc/resample.hip); 4: recording-level detection (csrc/detect.hip)
 
 // ----------------------------------------------------------------------------------------------
 // Device-resident step state (HIP-graph replays of a train step, engine.SEDTrainer.capture_step): a captured launch

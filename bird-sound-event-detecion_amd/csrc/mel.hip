@@ -24,6 +24,7 @@
 //   mel_noise_kernel: x + N(0, std_bin) with Philox/Box-Muller (or injected unit noise).
 //   mel_db_kernel   : 10*log10(max(1e-10, x^2)) clamped to (clip max - 80 dB), zero pad/trunc.
 //   mel_db_views_kernel : the same plus the ISP step's time-rolled and frequency-rolled views, one read, three writes.
+//   Both dB kernels have a NORM instance whose epilogue applies the dataset scaler (scaler_norm; statistics: scaler.hip).
 #include "bsed_common.h"
 #include "../../include/bsed.h"
 #include <math.h>
@@ -717,9 +718,18 @@ __global__ __launch_bounds__(256) void mel_stats_kernel(const float* __restrict_
   if (tid == 0) clip_max[b] = red[0];
 }
 
+// The dataset scaler's normalisation (Normalize(scaler), the last transform: Transforms.py:230-250), as the epilogue of
+// the dB kernels: float32((float64(v) - mean[m]) / std[m]) with v bitwise the unnormalised kernel's value (the 0 of a
+// pad row included) -- Scaler.normalize's numpy float64 arithmetic followed by the cast of torch.Tensor(...).
+__device__ __forceinline__ float scaler_norm(float v, double mean, double sd) {
+  return (float)__ddiv_rn(__dsub_rn((double)v, mean), sd);
+}
+
 // dB + top_db clamp + pad/trunc of the time axis (pad value 0 dB, Transforms.py:89-109)
+template <bool NORM>
 __global__ void mel_db_kernel(const float* __restrict__ x, const float* __restrict__ clip_max,
-                              float* __restrict__ out, int T, int T_out, int n_mels, float top_db) {
+                              float* __restrict__ out, int T, int T_out, int n_mels, float top_db,
+                              const double* __restrict__ mean, const double* __restrict__ sd) {
   const int b = blockIdx.y;
   const float mx = clip_max[b];
   const float floor_db = 10.0f * log10f(fmaxf(1e-10f, mx * mx)) - top_db;
@@ -730,6 +740,10 @@ __global__ void mel_db_kernel(const float* __restrict__ x, const float* __restri
     if (t < T) {
       const float a = x[(size_t)b * T * n_mels + i];
       v = fmaxf(10.0f * log10f(fmaxf(1e-10f, a * a)), floor_db);
+    }
+    if (NORM) {
+      const int m = (int)(i - (size_t)t * n_mels);
+      v = scaler_norm(v, mean[m], sd[m]);
     }
     out[(size_t)b * per_out + i] = v;
   }
@@ -750,10 +764,14 @@ __global__ void mel_db_kernel(const float* __restrict__ x, const float* __restri
 #define MV_ROWS 32
 #define MV_PASSES (MV_ROWS / (2 * MV_THREADS / 64))
 
+// NORM: every value is normalised (scaler_norm, band 4 l + j of the lane) BEFORE the rolls, as the reference rolls the
+// already normalised batch: the frequency-rolled view carries each source band's statistics with it.
+template <bool NORM>
 __global__ __launch_bounds__(MV_THREADS) void mel_db_views_kernel(const float* __restrict__ x, const float* __restrict__ clip_max,
                                                                   const int* __restrict__ sh, const int* __restrict__ sw,
                                                                   float* __restrict__ out, float* __restrict__ out_t,
-                                                                  float* __restrict__ out_f, int T, int T_out, float top_db) {
+                                                                  float* __restrict__ out_f, int T, int T_out, float top_db,
+                                                                  const double* __restrict__ mean, const double* __restrict__ sd) {
   const int n_mels = 128;
   const int b = blockIdx.y;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, l = lane & 31, hb = lane & 32;
@@ -767,6 +785,11 @@ __global__ __launch_bounds__(MV_THREADS) void mel_db_views_kernel(const float* _
   const float* xb = x + (size_t)b * T * n_mels + 4 * l;
   const size_t ob = (size_t)b * T_out * n_mels + 4 * l;
   const int t0 = blockIdx.x * MV_ROWS + 2 * wv + (lane >> 5);
+  double mu[4] = {0.0, 0.0, 0.0, 0.0}, sg[4] = {1.0, 1.0, 1.0, 1.0};
+  if (NORM) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { mu[j] = mean[4 * l + j]; sg[j] = sd[4 * l + j]; }
+  }
   float4 a4[MV_PASSES];
 #pragma unroll
   for (int k = 0; k < MV_PASSES; ++k) {
@@ -783,6 +806,7 @@ __global__ __launch_bounds__(MV_THREADS) void mel_db_views_kernel(const float* _
       const float a = e[j];
       const float v = fmaxf(10.0f * log10f(fmaxf(1e-10f, a * a)), floor_db);
       e[j] = t < T ? v : 0.f;           // pad rows: 0 dB (a select, not a branch around the logarithm)
+      if (NORM) e[j] = scaler_norm(e[j], mu[j], sg[j]);
     }
     const float4 v4 = make_float4(e[0], e[1], e[2], e[3]);
     // own float4 rotated by r in two select stages: g[j] = e[(j - r) & 3]; the pulls below run with every lane active
@@ -1008,8 +1032,43 @@ extern "C" int bsed_mel_db(const float* mel_lin, const float* clip_max, int B, i
   BSED_CHECK_ARG(B > 0 && B <= 65535 && T > 0 && T_out > 0 && n_mels > 0, "bsed_mel_db: bad shape");
   const size_t per = (size_t)T_out * n_mels;
   dim3 grid((unsigned)std::min<size_t>(ceil_div(per, 256), 64), B);
-  hipLaunchKernelGGL(mel_db_kernel, grid, dim3(256), 0, (hipStream_t)stream, mel_lin, clip_max, out_db, T,
-                     T_out, n_mels, top_db);
+  hipLaunchKernelGGL(mel_db_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, mel_lin, clip_max, out_db, T,
+                     T_out, n_mels, top_db, (const double*)nullptr, (const double*)nullptr);
+  BSED_LAUNCH_CHECK();
+  return BSED_OK;
+}
+
+extern "C" int bsed_mel_db_norm(const float* mel_lin, const float* clip_max, int B, int T, int T_out, int n_mels,
+                                float top_db, const double* mean, const double* stdev, float* out_db, void* stream) {
+  BSED_CHECK_ARG(mel_lin && clip_max && mean && stdev && out_db, "bsed_mel_db_norm: null argument");
+  BSED_CHECK_ARG(B > 0 && B <= 65535 && T > 0 && T_out > 0 && n_mels > 0, "bsed_mel_db_norm: bad shape");
+  const size_t per = (size_t)T_out * n_mels;
+  dim3 grid((unsigned)std::min<size_t>(ceil_div(per, 256), 64), B);
+  hipLaunchKernelGGL(mel_db_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, mel_lin, clip_max, out_db, T,
+                     T_out, n_mels, top_db, mean, stdev);
+  BSED_LAUNCH_CHECK();
+  return BSED_OK;
+}
+
+// mean == stdev == null: the unnormalised kernel
+static int mel_db_views(const char* who, const float* mel_lin, const float* clip_max, int B, int T, int T_out, int n_mels,
+                        float top_db, const int* shift_frames, const int* shift_bins, const double* mean,
+                        const double* stdev, float* out_db, float* out_db_tshift, float* out_db_fshift, void* stream) {
+  BSED_CHECK_ARG(mel_lin && clip_max && shift_frames && shift_bins && out_db && out_db_tshift && out_db_fshift,
+                 "%s: null argument", who);
+  BSED_CHECK_ARG(B > 0 && B <= 65535 && T > 0 && T_out > 0 && n_mels > 0, "%s: bad shape", who);
+  BSED_CHECK_ARG(out_db != out_db_tshift && out_db != out_db_fshift && out_db_tshift != out_db_fshift,
+                 "%s: the three outputs must be distinct buffers", who);
+  BSED_CHECK_ARG(n_mels == 128, "%s: built for n_mels = 128 (a row is 32 lanes x float4), got %d", who, n_mels);
+  const uintptr_t align = (uintptr_t)mel_lin | (uintptr_t)out_db | (uintptr_t)out_db_tshift | (uintptr_t)out_db_fshift;
+  BSED_CHECK_ARG((align & 15) == 0, "%s: mel_lin and the outputs must be 16-byte aligned", who);
+  const dim3 grid(ceil_div(T_out, MV_ROWS), B);
+  if (mean)
+    hipLaunchKernelGGL(mel_db_views_kernel<true>, grid, dim3(MV_THREADS), 0, (hipStream_t)stream, mel_lin, clip_max,
+                       shift_frames, shift_bins, out_db, out_db_tshift, out_db_fshift, T, T_out, top_db, mean, stdev);
+  else
+    hipLaunchKernelGGL(mel_db_views_kernel<false>, grid, dim3(MV_THREADS), 0, (hipStream_t)stream, mel_lin, clip_max,
+                       shift_frames, shift_bins, out_db, out_db_tshift, out_db_fshift, T, T_out, top_db, mean, stdev);
   BSED_LAUNCH_CHECK();
   return BSED_OK;
 }
@@ -1017,16 +1076,15 @@ extern "C" int bsed_mel_db(const float* mel_lin, const float* clip_max, int B, i
 extern "C" int bsed_mel_db_views(const float* mel_lin, const float* clip_max, int B, int T, int T_out, int n_mels,
                                  float top_db, const int* shift_frames, const int* shift_bins, float* out_db,
                                  float* out_db_tshift, float* out_db_fshift, void* stream) {
-  BSED_CHECK_ARG(mel_lin && clip_max && shift_frames && shift_bins && out_db && out_db_tshift && out_db_fshift,
-                 "bsed_mel_db_views: null argument");
-  BSED_CHECK_ARG(B > 0 && B <= 65535 && T > 0 && T_out > 0 && n_mels > 0, "bsed_mel_db_views: bad shape");
-  BSED_CHECK_ARG(out_db != out_db_tshift && out_db != out_db_fshift && out_db_tshift != out_db_fshift,
-                 "bsed_mel_db_views: the three outputs must be distinct buffers");
-  BSED_CHECK_ARG(n_mels == 128, "bsed_mel_db_views: built for n_mels = 128 (a row is 32 lanes x float4), got %d", n_mels);
-  const uintptr_t align = (uintptr_t)mel_lin | (uintptr_t)out_db | (uintptr_t)out_db_tshift | (uintptr_t)out_db_fshift;
-  BSED_CHECK_ARG((align & 15) == 0, "bsed_mel_db_views: mel_lin and the outputs must be 16-byte aligned");
-  hipLaunchKernelGGL(mel_db_views_kernel, dim3(ceil_div(T_out, MV_ROWS), B), dim3(MV_THREADS), 0, (hipStream_t)stream,
-                     mel_lin, clip_max, shift_frames, shift_bins, out_db, out_db_tshift, out_db_fshift, T, T_out, top_db);
-  BSED_LAUNCH_CHECK();
-  return BSED_OK;
+  return mel_db_views("bsed_mel_db_views", mel_lin, clip_max, B, T, T_out, n_mels, top_db, shift_frames, shift_bins, nullptr,
+                      nullptr, out_db, out_db_tshift, out_db_fshift, stream);
+}
+
+extern "C" int bsed_mel_db_views_norm(const float* mel_lin, const float* clip_max, int B, int T, int T_out, int n_mels,
+                                      float top_db, const int* shift_frames, const int* shift_bins, const double* mean,
+                                      const double* stdev, float* out_db, float* out_db_tshift, float* out_db_fshift,
+                                      void* stream) {
+  BSED_CHECK_ARG(mean && stdev, "bsed_mel_db_views_norm: null argument");
+  return mel_db_views("bsed_mel_db_views_norm", mel_lin, clip_max, B, T, T_out, n_mels, top_db, shift_frames, shift_bins, mean,
+                      stdev, out_db, out_db_tshift, out_db_fshift, stream);
 }

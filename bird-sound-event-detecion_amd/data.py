@@ -123,7 +123,9 @@ ENA_Dataset_unlabeled = PseudoWeakDataset
 
 class GpuCollate:
     """collate_fn: list of ((linear_mel (T,128), target), path) -> (((x, x_noisy), target), paths) with
-    x, x_noisy = (B,1,max_frames,128) dB-mel on the GPU (clean / SNR-noise view), target float32 on the GPU."""
+    x, x_noisy = (B,1,max_frames,128) dB-mel on the GPU (clean / SNR-noise view), target float32 on the GPU.
+    Both views go through ``frontend.to_db``: a front end with a ``Scaler`` attached (``MelFrontEnd.set_scaler``) gives
+    normalised tensors, each clip still with its own top_db clamp; no argument of this class is involved."""
 
     def __init__(self, frontend, max_frames=None, noisy=True, seed=0):
         self.fe, self.max_frames, self.noisy, self.seed = frontend, max_frames, noisy, seed

@@ -207,7 +207,9 @@ class FlatSGD:
 # ----------------------------------------------------------------------------- the train step
 class SEDTrainer:
     """One object = the state of a training run on ONE GPU (rank).  ``train_step`` is one iteration of the
-    reference's ``train_mt`` loop body."""
+    reference's ``train_mt`` loop body.  The dataset scaler needs no argument here: every ``from_wave`` input (prefetched
+    ones and captured steps included) comes from ``frontend.transform``, so a ``MelFrontEnd`` with a ``Scaler`` attached
+    feeds normalised features, as the reference's ``Normalize(scaler)`` transform does."""
 
     def __init__(self, crnn, predictor, ema_crnn=None, ema_predictor=None, optimizer=None, frontend=None,
                  max_consistency_cost=1.0, ema_alpha=0.999, process_group=None, seed=2023, domain_loss=None,

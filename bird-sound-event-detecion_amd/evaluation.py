@@ -420,7 +420,7 @@ def detect_recording(model, wave, decoder, predictor=None, fpn=False, *, mel=Non
     float32, (n,) or (n, channels), at ``sr`` Hz, which ``features.Resampler(sr, mel.cfg.sr, **resample_quality)`` first
     mixes to mono and resamples in one launch (a "resample" stage in ``stage_events``; mono float32 with
     ``sr == mel.cfg.sr`` needs none and takes the ``sr=None`` route).  The resampling filter is this package's own, not
-    librosa's.  ``mel``: the ``MelFrontEnd`` the model was trained with (default: the reference configuration); ``decoder``: ``ManyHotEncoder.decode_strong`` as for ``get_predictions``.  Returns a DataFrame with
+    librosa's.  ``mel``: the ``MelFrontEnd`` the model was trained with (default: the reference configuration), its ``Scaler`` attached if the model was trained on normalised features (``checkpoint.load_models(...)["scaler"]`` -> ``MelFrontEnd.set_scaler``): the windows follow the front end, there is no separate argument; ``decoder``: ``ManyHotEncoder.decode_strong`` as for ``get_predictions``.  Returns a DataFrame with
     the columns of ``get_predictions`` (event_label / onset / offset / filename; seconds from the start of the
     recording, clipped to its duration), or a list of them, one per threshold; with ``return_probabilities`` the tuple
     (that, stitched (T_total, C) GPU probabilities, per-window (W, Tp, C) GPU probabilities).

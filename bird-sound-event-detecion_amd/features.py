@@ -40,15 +40,33 @@ class MelConfig:
 
 
 class MelFrontEnd:
-    def __init__(self, cfg=None):
+    """``scaler``: a ``scaler.Scaler`` with statistics (the reference's ``Normalize(scaler)``, the last transform of
+    ``get_transforms``).  With one attached, ``to_db``, ``to_db_views`` and ``transform`` return normalised features from
+    the same single launch (the dB kernels' NORM epilogue); ``linear``, ``stats``, ``add_noise`` and the module-level
+    ``preprocess`` are untouched by it."""
+
+    def __init__(self, cfg=None, scaler=None):
         L._require_gpu()
         self.cfg = cfg or MelConfig()
+        self.scaler, self._norm = None, None
         c = L.STRUCTS["BsedMelCfg"](self.cfg.sr, self.cfg.n_window, self.cfg.hop_size, self.cfg.n_mels,
                                     self.cfg.mel_f_min, self.cfg.mel_f_max)
         self._plan = ctypes.c_void_p()
         L.call("bsed_mel_plan_create", ctypes.byref(c), ctypes.byref(self._plan))
         self.nnz = int(L.lib().bsed_mel_plan_nnz(self._plan))
         self.frames_per_wave = int(L.lib().bsed_mel_plan_frames_per_wave(self._plan))   # 2: stft_mel2_kernel
+        self.set_scaler(scaler)
+
+    def set_scaler(self, scaler):
+        """attach a ``Scaler`` (or detach with None).  Its statistics are checked (BsedError names unusable bands) and the
+        float64 device vectors are uploaded HERE, never inside ``to_db``: a captured training step contains no
+        host-to-device copy.  Statistics changed later reach the front end through another ``set_scaler``."""
+        if scaler is None:
+            self.scaler, self._norm = None, None
+            return
+        scaler.check(self.cfg.n_mels, who="attach")
+        mean, std = scaler.device_vectors(torch.device("cuda", torch.cuda.current_device()))
+        self.scaler, self._norm = scaler, (L.ptr(mean, torch.float64), L.ptr(std, torch.float64), mean, std)
 
     def __del__(self):
         try:
@@ -89,9 +107,17 @@ class MelFrontEnd:
         return cmax, sumsq
 
     def to_db(self, mel_lin, clip_max, max_frames=None):
+        """linear mel -> dB with the per-clip top_db clamp, zero-padded / truncated to ``max_frames`` (0 dB pad rows);
+        with a scaler attached every element is then ``float32((float64(v) - mean_) / std_)`` (a pad row: -mean_/std_)"""
         B, T, M = mel_lin.shape
         T_out = T if max_frames is None else max_frames
         out = torch.empty((B, 1, T_out, M), device=mel_lin.device, dtype=torch.float32)
+        if self._norm is not None:
+            # the same traffic plus the two float64 vectors; ~40 float64 operations per element for the division
+            ops._note("mel_db_kernel<norm>", f"T{T_out}", 44.0 * B * T_out * M, 4.0 * B * M * (min(T, T_out) + T_out) + 16.0 * M)
+            L.call("bsed_mel_db_norm", L.ptr(mel_lin), L.ptr(clip_max), B, T, T_out, M, self.cfg.top_db,
+                   self._norm[0], self._norm[1], L.ptr(out), L.stream())
+            return out
         ops._note("mel_db_kernel", f"T{T_out}", 4.0 * B * T_out * M, 4.0 * B * M * (T + T_out))
         L.call("bsed_mel_db", L.ptr(mel_lin), L.ptr(clip_max), B, T, T_out, M, self.cfg.top_db,
                L.ptr(out), L.stream())
@@ -114,6 +140,13 @@ class MelFrontEnd:
         T_out = T if max_frames is None else max_frames
         sh, sw = self._shifts(shift_frames, B, mel_lin.device), self._shifts(shift_bins, B, mel_lin.device)
         outs = tuple(torch.empty((B, 1, T_out, M), device=mel_lin.device, dtype=torch.float32) for _ in range(3))
+        if self._norm is not None:
+            ops._note("mel_db_views_kernel<norm>", f"T{T_out}", 44.0 * B * T_out * M,
+                      4.0 * B * M * (min(T, T_out) + 3 * T_out) + 16.0 * M)
+            L.call("bsed_mel_db_views_norm", L.ptr(mel_lin), L.ptr(clip_max), B, T, T_out, M, self.cfg.top_db,
+                   L.ptr(sh, torch.int32), L.ptr(sw, torch.int32), self._norm[0], self._norm[1], L.ptr(outs[0]),
+                   L.ptr(outs[1]), L.ptr(outs[2]), L.stream())
+            return outs
         ops._note("mel_db_views_kernel", f"T{T_out}", 4.0 * B * T_out * M, 4.0 * B * M * (T + 3 * T_out))
         L.call("bsed_mel_db_views", L.ptr(mel_lin), L.ptr(clip_max), B, T, T_out, M, self.cfg.top_db,
                L.ptr(sh, torch.int32), L.ptr(sw, torch.int32), L.ptr(outs[0]), L.ptr(outs[1]), L.ptr(outs[2]), L.stream())
@@ -151,7 +184,8 @@ _default = {}
 
 def preprocess(audio, compute_log=False, cfg=None):
     """Drop-in for the reference ``preprocess``: one waveform (numpy or tensor) -> (T, n_mels) float32
-    numpy array of LINEAR mel amplitude (dB if compute_log)."""
+    numpy array of LINEAR mel amplitude (dB if compute_log).  Never normalised: the reference's ``preprocess`` runs
+    before any ``Scaler`` exists, and its cached front ends carry none."""
     import numpy as np
     cfg = cfg or MelConfig()
     key = (cfg.sr, cfg.n_window, cfg.hop_size, cfg.n_mels, cfg.mel_f_min, cfg.mel_f_max)

@@ -75,6 +75,37 @@ int bsed_mel_db_views(const float* mel_lin, const float* clip_max, int B, int T,
                       float* out_db_tshift, float* out_db_fshift, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Dataset scaler (ABI 10; csrc/scaler.hip, csrc/mel.hip).   replaces Scaler.means / Scaler.normalize
+ * (reference src/utilities/Scaler.py:38-110) and the Normalize(scaler) transform (src/data/Transforms.py:230-250).
+ * ---------------------------------------------------------------------------------------------- */
+/* acc (2, n_mels) float64 += per-band [sum of x, sum of x^2] of a batch, x being the dB feature bsed_mel_db would write
+ * for T_out frames per clip, computed on the fly from LINEAR mel (B, T, n_mels) and clip_max (B): no dB tensor is
+ * written.  Frames T <= t < T_out are 0 dB pad rows (they add nothing), frames t >= T_out are dropped.  x^2 is a float32
+ * product, widened (the reference squares a float32 array); both sums accumulate in float64.  Every workgroup writes a
+ * partial into scratch (bsed_scaler_scratch_doubles doubles) and a second kernel adds them to acc in a fixed order: no
+ * floating-point atomics, bitwise repeatable.  n_mels 1..256 (full-width loads at 128), B <= 65535. */
+long bsed_scaler_scratch_doubles(int B, int T, int T_out, int n_mels);
+int bsed_scaler_accum(const float* mel_lin, const float* clip_max, int B, int T, int T_out, int n_mels,
+                      float top_db, double* acc, double* scratch, void* stream);
+/* the same from a dB tensor (B, T_out, n_mels) (features that are already transformed); scratch as for T = T_out */
+int bsed_scaler_accum_db(const float* x_db, int B, int T_out, int n_mels, double* acc, double* scratch,
+                         void* stream);
+/* out = float32((float64(x) - mean[m]) / stdev[m]) over n_rows rows of n_mels bands: Scaler.normalize followed by
+ * torch.Tensor(...).  mean, stdev: (n_mels) float64.  out may be x. */
+int bsed_scaler_normalize(const float* x_db, long long n_rows, int n_mels, const double* mean, const double* stdev,
+                          float* out, void* stream);
+/* bsed_mel_db / bsed_mel_db_views with that normalisation as the epilogue: every element is
+ * float32((float64(v) - mean[m]) / stdev[m]) with v bitwise what the unnormalised entry point writes (a pad row becomes
+ * -mean / stdev).  In the views form the values are normalised BEFORE the rolls, as the reference rolls the normalised
+ * batch: the frequency-rolled view carries each source band's statistics with it. */
+int bsed_mel_db_norm(const float* mel_lin, const float* clip_max, int B, int T, int T_out, int n_mels,
+                     float top_db, const double* mean, const double* stdev, float* out_db, void* stream);
+int bsed_mel_db_views_norm(const float* mel_lin, const float* clip_max, int B, int T, int T_out, int n_mels,
+                           float top_db, const int* shift_frames, const int* shift_bins, const double* mean,
+                           const double* stdev, float* out_db, float* out_db_tshift, float* out_db_fshift,
+                           void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Implicit-GEMM contraction on the fp32 matrix cores (v_mfma_f32_32x32x2_f32).
  *   out[p][n] = sum_{tap,k} in[p + (dh,dw)(tap)][k] * w[tap][k][n]      zero padding outside (H,W)
  * One body, selected by `epilogue`, replaces the stock ATen/cuDNN ops the reference reaches through
