@@ -653,52 +653,53 @@ extern "C" int bsed_block0_stats(const float* x, const float* cw_t, const float*
   return BSED_OK;
 }
 
-extern "C" int bsed_block0_fwd(const float* x, const float* cw, const float* cb, const float* scale, const float* shift,
-                               const float* wg, const float* bg, float* out, int B, int H, int W, int CO, int ph, int pw,
-                               float drop_p, uint32_t rng_stream, uint64_t seed, int act_bf16, void* stream) {
-  BSED_CHECK_ARG(x && cw && cb && scale && shift && wg && bg && out, "bsed_block0_fwd: null tensor");
-  BSED_CHECK_ARG(CO == B0_C, "bsed_block0_fwd: built for 16 first-layer channels (got %d)", CO);
-  BSED_CHECK_ARG(B > 0 && H > 0 && W > 0 && (ph == 1 || ph == 2) && (pw == 1 || pw == 2) && W % pw == 0 && H >= ph &&
-                     (long)B * H * W < (1L << 31), "bsed_block0_fwd: bad shape");
-  const long items = (long)B * (H / ph) * ((W + B0F_THREADS / 4 - 1) / (B0F_THREADS / 4));
-  const dim3 grid((unsigned)std::min<long>(items, 8192));
-  hipStream_t s = (hipStream_t)stream;
-  // SMALL: fewer than 2^28 positions (every tensor below 4 GB, element counters below 2^32): 32-bit offsets
-  const bool small = (long)B * H * W < (1L << 28);
-#define B0_LAUNCH_FWD(PH_, SM_, AB_)                                                                                 \
-  hipLaunchKernelGGL((b0_fwd_kernel<PH_, SM_, AB_>), grid, dim3(B0F_THREADS), 0, s, x, cw, cb, scale, shift, wg, bg, out, B, \
-                     H, W, pw, drop_p, rng_stream, seed, bsed_seed_add_ptr())
-  if (act_bf16) { if (ph == 2) B0_LAUNCH_FWD(2, false, 1); else B0_LAUNCH_FWD(1, false, 1); }
-  else if (ph == 2) { if (small) B0_LAUNCH_FWD(2, true, 0); else B0_LAUNCH_FWD(2, false, 0); }
-  else { if (small) B0_LAUNCH_FWD(1, true, 0); else B0_LAUNCH_FWD(1, false, 0); }
+// PH, SMALL and ABF of the two launches below come from the plan's variant (PH | SMALL << 4) and desc->act_bf16
+#define B0_PICK(LAUNCH, PH_, SM_, AB_) \
+  if (ph == PH_ && small == SM_ && d.act_bf16 == AB_) { LAUNCH(PH_, SM_, AB_); BSED_LAUNCH_CHECK(); return BSED_OK; }
+
+extern "C" int bsed_block0_fwd(const BsedGluDesc* desc, void* stream) {
+  BsedGluPlan plan;
+  const uint64_t* seed_add;
+  const int rc = bsed_glu_args(desc, BSED_GLU_BLOCK0_FWD, GLU_X | GLU_CONV | GLU_LIN | GLU_POOLED, plan, seed_add);
+  if (rc) return rc;
+  const BsedGluDesc& d = *desc;
+  const int ph = plan.variant & 15;
+  const bool small = plan.variant >> 4;
+#define B0_LAUNCH_FWD(PH_, SM_, AB_)                                                                                  \
+  hipLaunchKernelGGL((b0_fwd_kernel<PH_, SM_, AB_>), dim3(d.G), dim3(B0F_THREADS), 0, (hipStream_t)stream, d.x, d.cw, \
+                     d.cb, d.scale, d.shift, d.w, d.bias, d.pooled, d.NB, d.H, d.W, d.pw, d.drop_p, d.rng_stream,     \
+                     d.seed, seed_add)
+  B0_PICK(B0_LAUNCH_FWD, 2, false, 1) B0_PICK(B0_LAUNCH_FWD, 1, false, 1)
+  B0_PICK(B0_LAUNCH_FWD, 2, true, 0) B0_PICK(B0_LAUNCH_FWD, 2, false, 0)
+  B0_PICK(B0_LAUNCH_FWD, 1, true, 0) B0_PICK(B0_LAUNCH_FWD, 1, false, 0)
 #undef B0_LAUNCH_FWD
-  BSED_LAUNCH_CHECK();
-  return BSED_OK;
+  bsed_set_error("bsed_block0_fwd: internal: b0_fwd_kernel<%d, %d, %d> is not built", ph, (int)small, d.act_bf16);
+  return BSED_ERR_STATE;
 }
 
-extern "C" int bsed_block0_bwd(const float* x, const float* cw, const float* cb, const float* scale, const float* shift,
-                               const float* wg, const float* bg, const float* dpool, float* part_dw, float* part_db,
-                               float* part_st, float* part_gx, int G, int B, int H, int W, int CO, int ph, int pw,
-                               float drop_p, uint32_t rng_stream, uint64_t seed, int act_bf16, void* stream) {
-  BSED_CHECK_ARG(x && cw && cb && scale && shift && wg && bg && dpool && part_dw && part_db && part_st && part_gx,
-                 "bsed_block0_bwd: null tensor");
-  BSED_CHECK_ARG(CO == B0_C, "bsed_block0_bwd: built for 16 first-layer channels (got %d)", CO);
-  BSED_CHECK_ARG(B > 0 && H > 0 && W > 0 && G > 0 && (ph == 1 || ph == 2) && (pw == 1 || pw == 2) && W % pw == 0 &&
-                     H >= ph, "bsed_block0_bwd: bad shape");
-  BSED_CHECK_ARG((long)B * H * W < (1L << 31), "bsed_block0_bwd: too many positions");
-  hipStream_t s = (hipStream_t)stream;
-  const bool small = (long)B * H * W < (1L << 28);
+extern "C" int bsed_block0_bwd(const BsedGluDesc* desc, void* stream) {
+  BsedGluPlan plan;
+  const uint64_t* seed_add;
+  const int rc = bsed_glu_args(desc, BSED_GLU_BLOCK0_BWD,
+                               GLU_X | GLU_CONV | GLU_LIN | GLU_DPOOL | GLU_PART_DW | GLU_PART_B | GLU_PART_GX, plan,
+                               seed_add);
+  if (rc) return rc;
+  const BsedGluDesc& d = *desc;
+  const int ph = plan.variant & 15;
+  const bool small = plan.variant >> 4;
 #define B0_LAUNCH_BWD(PH_, SM_, AB_)                                                                                  \
-  hipLaunchKernelGGL((b0_bwd_kernel<PH_, SM_, AB_>), dim3(G), dim3(B0B_THREADS), 0, s, x, cw, cb, scale, shift, wg, bg, dpool, \
-                     part_dw, part_db, part_st, part_gx, B, H, W, pw, drop_p, rng_stream, seed, bsed_seed_add_ptr())
-  if (act_bf16) { if (ph == 2) { if (small) B0_LAUNCH_BWD(2, true, 1); else B0_LAUNCH_BWD(2, false, 1); }
-                  else { if (small) B0_LAUNCH_BWD(1, true, 1); else B0_LAUNCH_BWD(1, false, 1); } }
-  else if (ph == 2) { if (small) B0_LAUNCH_BWD(2, true, 0); else B0_LAUNCH_BWD(2, false, 0); }
-  else { if (small) B0_LAUNCH_BWD(1, true, 0); else B0_LAUNCH_BWD(1, false, 0); }
+  hipLaunchKernelGGL((b0_bwd_kernel<PH_, SM_, AB_>), dim3(d.G), dim3(B0B_THREADS), 0, (hipStream_t)stream, d.x, d.cw, \
+                     d.cb, d.scale, d.shift, d.w, d.bias, d.dpool, d.part_dw, d.part_db, d.part_st, d.part_gx, d.NB,  \
+                     d.H, d.W, d.pw, d.drop_p, d.rng_stream, d.seed, seed_add)
+  B0_PICK(B0_LAUNCH_BWD, 2, true, 1) B0_PICK(B0_LAUNCH_BWD, 2, false, 1)
+  B0_PICK(B0_LAUNCH_BWD, 1, true, 1) B0_PICK(B0_LAUNCH_BWD, 1, false, 1)
+  B0_PICK(B0_LAUNCH_BWD, 2, true, 0) B0_PICK(B0_LAUNCH_BWD, 2, false, 0)
+  B0_PICK(B0_LAUNCH_BWD, 1, true, 0) B0_PICK(B0_LAUNCH_BWD, 1, false, 0)
 #undef B0_LAUNCH_BWD
-  BSED_LAUNCH_CHECK();
-  return BSED_OK;
+  bsed_set_error("bsed_block0_bwd: internal: b0_bwd_kernel<%d, %d, %d> is not built", ph, (int)small, d.act_bf16);
+  return BSED_ERR_STATE;
 }
+#undef B0_PICK
 
 extern "C" int bsed_block0_wgrad_finish(const float* part_gx, int G, const double* xr64, const float* coef,
                                         const float* mean, const float* cw, const float* cb, float* dst, int accumulate,

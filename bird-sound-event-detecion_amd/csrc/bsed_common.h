@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <algorithm>
+#include "../../include/bsed.h"
 
 #define BSED_OK 0
 #define BSED_ERR_ARG (-1)
@@ -178,6 +180,141 @@ static int bsed_tile_geometry(Params& P, const char* who, int cin_mult, int pitc
   const long ntiles = (long)d.NB * d.tilesH * d.tilesW;
   BSED_CHECK_ARG(ntiles < (1L << 31), "%s: too many tiles", who);
   return (int)ntiles;
+}
+
+// ----------------------------------------------------------------------------------------------
+// Host side of the eight GLU / first-block entry points (BsedGluDesc, include/bsed.h).  No HIP call is made here.
+// ----------------------------------------------------------------------------------------------
+// What bsed_glu_plan answers, for the entry point `kernel` (BSED_GLU_*) and the shape fields of d: every shape check of
+// the family (the stricter one where the former per-file copies differed) and every grid size, slab count and template
+// choice, with the measurements behind them.  The entry points launch what this returns.
+static inline const char* bsed_glu_name(int kernel) {   // the entry point of a BSED_GLU_* id, for the messages
+  static const char* const names[] = {"bsed_glu16_fwd", "bsed_glu16_bwd", "bsed_block0_fwd", "bsed_block0_bwd",
+                                      "bsed_glu_bwd_fused", "bsed_glu_fwd3", "bsed_glu_bwd3", "bsed_glu_bwd3n"};
+  return kernel >= 0 && kernel < 8 ? names[kernel] : nullptr;
+}
+static inline int bsed_glu_plan_for(const BsedGluDesc& d, int kernel, BsedGluPlan& p) {
+  const char* who = bsed_glu_name(kernel);
+  BSED_CHECK_ARG(who, "bsed_glu_plan: unknown kernel %d", kernel);
+  const bool tiled = kernel >= BSED_GLU_BWD_FUSED, glu3 = kernel >= BSED_GLU_FWD3;
+  const bool block0 = kernel == BSED_GLU_BLOCK0_FWD || kernel == BSED_GLU_BLOCK0_BWD;
+  const int C = d.C;
+  BSED_CHECK_ARG(d.NB > 0 && d.H > 0 && d.W > 0, "%s: bad shape", who);
+  BSED_CHECK_ARG((d.ph == 1 || d.ph == 2) && (d.pw == 1 || d.pw == 2), "%s: pooling windows must be 1 or 2", who);
+  BSED_CHECK_ARG(d.act_bf16 == 0 || (d.act_bf16 == 1 && (glu3 || block0)), "%s: no bf16 activations (act_bf16 = %d)",
+                 who, d.act_bf16);
+  if (!tiled) BSED_CHECK_ARG(C == 16, "%s: built for 16 channels (got %d)", who, C);
+  else if (kernel == BSED_GLU_BWD3) BSED_CHECK_ARG(C == 32 || C == 64, "%s: built for C in {32,64} (got %d)", who, C);
+  else if (kernel == BSED_GLU_BWD3N) BSED_CHECK_ARG(C == 128, "%s: built for C = 128 (got %d)", who, C);
+  else BSED_CHECK_ARG(C == 32 || C == 64 || C == 128, "%s: built for C in {32,64,128} (got %d)", who, C);
+  const long positions = (long)d.NB * d.H * d.W;
+  p.dw_rows = 0; p.variant = 0; p.table_bytes = 0;
+  if (!tiled) {
+    BSED_CHECK_ARG(d.TH == 0 && d.TW == 0, "%s: a streaming kernel without a tile: TH = TW = 0 (got %dx%d)", who, d.TH,
+                   d.TW);
+    BSED_CHECK_ARG(d.W % d.pw == 0 && d.H >= d.ph, "%s: bad shape (W %% pw == 0, H >= ph)", who);
+    BSED_CHECK_ARG(!block0 || positions < (1L << 31), "%s: too many positions", who);
+    const long rows = (long)d.NB * (d.H / d.ph);   // pooled rows: the work items of the forward kernels
+    long items = rows, g = std::min<long>(rows, 8192);
+    if (kernel == BSED_GLU_16_BWD) {               // items: (row, 64-column chunk)
+      items = (long)d.NB * d.H * ((d.W + 63) / 64);
+      g = std::min<long>(2048, (long)d.NB * d.H);
+    } else if (kernel == BSED_GLU_BLOCK0_FWD) {    // items: (pooled row, 128-column chunk)
+      items = rows * ((d.W + 127) / 128);
+      g = std::min<long>(items, 8192);
+    } else if (kernel == BSED_GLU_BLOCK0_BWD) {    // items: (pooled row, 64-column chunk)
+      items = rows * ((d.W + 63) / 64);
+      g = std::min<long>(8192, rows);              // 2048 / 4096 / 8192 workgroups: 0.983 / 0.966 / 0.957 ms
+    }
+    BSED_CHECK_ARG(items < (1L << 30), "%s: too many rows", who);   // item + G stays an int in the prefetching loops
+    p.G = (int)g; p.max_G = (int)items;
+    if (kernel == BSED_GLU_16_BWD || kernel == BSED_GLU_BLOCK0_BWD) p.dw_rows = p.G;
+    // block0 SMALL: fewer than 2^28 positions (every tensor below 4 GB, element counters below 2^32): 32-bit offsets;
+    // the bf16 forward is built without it
+    if (block0) p.variant = d.ph | (positions < (1L << 28) && !(d.act_bf16 && kernel == BSED_GLU_BLOCK0_FWD) ? 16 : 0);
+    return BSED_OK;
+  }
+  BSED_CHECK_ARG(d.TH * d.TW == 128, "%s: TH*TW must be 128 (got %dx%d)", who, d.TH, d.TW);
+  const int lgTW = ilog2_exact(d.TW);
+  BSED_CHECK_ARG(lgTW >= 0, "%s: TW must be a power of two", who);
+  BSED_CHECK_ARG(d.W % d.TW == 0, "%s: TW must divide W", who);
+  const long ntiles = (long)d.NB * ceil_div(d.H, d.TH) * (d.W / d.TW);
+  BSED_CHECK_ARG(ntiles < (1L << 31), "%s: too many tiles", who);
+  BSED_CHECK_ARG(!glu3 || positions * C < (1L << 32),
+                 "%s: activation tensor beyond the 32-bit element offsets of this kernel", who);
+  // persistent kernels: G = the workgroups of one resident round (LDS- and register-limited occupancy x 256 CUs)
+  int round = 0, slabs = 0;
+  if (kernel == BSED_GLU_BWD_FUSED) {
+    round = C == 128 ? 256 : (C == 64 ? 512 : 768);
+    slabs = C == 128 ? 1 : (C == 64 ? 2 : 4);      // waves that share one dW row-tile split the positions (KSPLIT)
+    p.variant = C == 128 ? 8 : 4;                  // NW
+  } else if (kernel == BSED_GLU_FWD3) {
+    // measured (B = 256): C = 32: 512 / 768 / 1024 / 1536 workgroups 0.447 / 0.367 / 0.412 / 0.350 ms; C = 64: 0.180 / 0.160 / 0.167 / 0.155;
+    // C = 128 (64 KB of weight fragments in LDS, two per CU): 256 / 512 / 768 / 1024 0.514 / 0.422 / 0.454 / 0.435
+    round = C == 128 ? 512 : 1536;
+  } else if (kernel == BSED_GLU_BWD3) {
+    round = C == 32 ? 768 : 512;
+    slabs = 4;                                     // one per wave
+  } else {
+    round = 256;                                   // 8-wave workgroups take two tiles at a time
+    p.table_bytes = (size_t)2 * 4 * 8 * 2 * 64 * 16;   // both weight operands pre-split into fragment order
+  }
+  p.max_G = (int)(kernel == BSED_GLU_BWD3N ? (ntiles + 1) / 2 : ntiles);
+  p.G = std::min(p.max_G, round);
+  p.dw_rows = p.G * slabs;
+  // glu_fwd3 / glu_bwd3 are also built with the tile width of the wide maps (16) as a compile-time constant
+  if (kernel == BSED_GLU_FWD3 || kernel == BSED_GLU_BWD3) p.variant = lgTW == 4 ? 4 : -1;
+  return BSED_OK;
+}
+
+// The argument check of an entry point: the plan's shape checks, then `reads` = the pointer fields it wants (bit i =
+// the i-th pointer of BsedGluDesc in declaration order; every other one must be null) and G in 1..max_G.  seed_add
+// receives the device-resident seed addend of the step state (capi.hip) -- the family's one read of it.
+static inline int bsed_glu_args(const BsedGluDesc* desc, int kernel, unsigned reads, BsedGluPlan& plan,
+                                const uint64_t*& seed_add) {
+  const char* who = bsed_glu_name(kernel);
+  BSED_CHECK_ARG(desc, "%s: null descriptor", who);
+  const BsedGluDesc& d = *desc;
+  const int rc = bsed_glu_plan_for(d, kernel, plan);
+  if (rc) return rc;
+  static const char* const names[] = {"x", "y", "cw", "cb", "scale", "shift", "w", "wfwd", "bias", "dpool", "pooled", "g",
+                                      "dlin", "part_dw", "part_db", "part_st", "part_gx", "frag_table"};
+  const void* const ptrs[] = {d.x, d.y, d.cw, d.cb, d.scale, d.shift, d.w, d.wfwd, d.bias, d.dpool, d.pooled, d.g,
+                              d.dlin, d.part_dw, d.part_db, d.part_st, d.part_gx, d.frag_table};
+  for (int i = 0; i < 18; ++i) {
+    const bool wants = (reads >> i) & 1;
+    BSED_CHECK_ARG(wants == (ptrs[i] != nullptr), wants ? "%s: null tensor %s" : "%s: does not read %s: it must be null",
+                   who, names[i]);
+  }
+  BSED_CHECK_ARG(d.G > 0 && d.G <= plan.max_G, "%s: G must be in 1..%d (got %d)", who, plan.max_G, d.G);
+  seed_add = bsed_seed_add_ptr();
+  return BSED_OK;
+}
+enum : unsigned {   // `reads` of bsed_glu_args
+  GLU_X = 1u << 0, GLU_Y = 1u << 1, GLU_CONV = 3u << 2 /* cw, cb */, GLU_BN = 3u << 4 /* scale, shift */, GLU_W = 1u << 6,
+  GLU_WFWD = 1u << 7, GLU_BIAS = 1u << 8, GLU_DPOOL = 1u << 9, GLU_POOLED = 1u << 10, GLU_G = 1u << 11,
+  GLU_DLIN = 1u << 12, GLU_PART_DW = 1u << 13, GLU_PART_B = 3u << 14 /* part_db, part_st */, GLU_PART_GX = 1u << 16,
+  GLU_FRAG = 1u << 17,
+  GLU_LIN = GLU_BN | GLU_W | GLU_BIAS   // BatchNorm apply + the Linear layer
+};
+
+// bsed_glu_args for the tiled kernels (glu3.hip, glu_bwd.hip), then the fields Glu3Params and GluBwdParams share by
+// name: the descriptor's tensors, the tile geometry, the pooled extent, the dropout fields and the seed addend.  The
+// caller sets the tensors only one of the structs has.
+template <class Params>
+static int bsed_glu_geometry(Params& P, const BsedGluDesc* desc, int kernel, unsigned reads, BsedGluPlan& plan) {
+  const int rc = bsed_glu_args(desc, kernel, reads, plan, P.seed_add);
+  if (rc) return rc;
+  const BsedGluDesc& d = *desc;
+  P.y = d.y; P.scale = d.scale; P.shift = d.shift; P.bias = d.bias; P.dpool = d.dpool;
+  P.g = d.g; P.part_dw = d.part_dw; P.part_db = d.part_db; P.part_st = d.part_st;
+  P.NB = d.NB; P.H = d.H; P.W = d.W; P.TH = d.TH; P.TW = d.TW;
+  P.lgTW = ilog2_exact(d.TW);
+  P.tilesH = ceil_div(d.H, d.TH); P.tilesW = d.W / d.TW;
+  P.ntiles = d.NB * P.tilesH * P.tilesW;
+  P.ph = d.ph; P.pw = d.pw; P.Hp = d.H / d.ph; P.Wp = d.W / d.pw;
+  P.drop_p = d.drop_p; P.rng_stream = d.rng_stream; P.seed = d.seed;
+  return BSED_OK;
 }
 
 #if defined(__HIPCC__)

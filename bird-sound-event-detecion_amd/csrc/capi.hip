@@ -15,16 +15,22 @@ void bsed_set_error(const char* fmt, ...) {
 extern "C" const char* bsed_last_error(void) { return g_err; }
 extern "C" const char* bsed_build_info(void) { return "libbsed gfx950: fp32 storage/accumulation, split-fp32 (bf16x3) contractions on v_mfma_f32_32x32x16_bf16 by default, "
          "exact-fp32 v_mfma_f32_32x32x2_f32 kernels selectable (hand-written HIP)"; }
-extern "C" int bsed_abi_version(void) { return 10; }   // 10: dataset scaler statistics + normalised dB kernels (csrc/scaler.hip, csrc/mel.hip); 9: soundscape synthesis (csrc/synth.hip); 8: Predictor head for 1..64 classes + bsed_head_lds_bytes (csrc/head.hip); 7: clip-level tagging counts + pseudo-label masks (csrc/tagging.hip); 6: threshold sweep + event F1 counts (csrc/metrics.hip); 5: resampling (csrc/resample.hip); 4: recording-level detection (csrc/detect.hip)
+extern "C" int bsed_abi_version(void) { return 11; }   // 11: BsedGluDesc + bsed_glu_plan for the GLU / first-block entry points (csrc/glu*.hip, csrc/block0.hip); 10: dataset scaler statistics + normalised dB kernels (csrc/scaler.hip, csrc/mel.hip); 9: soundscape synthesis (csrc/synth.hip); 8: Predictor head for 1..64 classes + bsed_head_lds_bytes (csrc/head.hip); 7: clip-level tagging counts + pseudo-label masks (csrc/tagging.hip); 6: threshold sweep + event F1 counts (csrc/metrics.hip); 5: resampling (csrc/resample.hip); 4: recording-level detection (csrc/detect.hip)
+
+// the plan of a GLU / first-block entry point (bsed_common.h): the query the callers size their buffers with
+extern "C" int bsed_glu_plan(const BsedGluDesc* desc, int kernel, BsedGluPlan* out) {
+  BSED_CHECK_ARG(desc && out, "bsed_glu_plan: null argument");
+  return bsed_glu_plan_for(*desc, kernel, *out);
+}
 
 // ----------------------------------------------------------------------------------------------
 // Device-resident step state (HIP-graph replays of a train step, engine.SEDTrainer.capture_step): a captured launch
 // bakes its scalar arguments, so what changes from step to step -- the dropout seed, the optimizer's step count and the
 // learning rate -- is ALSO read from device memory.  For a launch made while the pointers are set,
-//   - the dropout kernels of the plain train step add *seed_add to their seed: bsed_dropout, bsed_block0_fwd / _bwd,
-//     bsed_glu_fwd3 / bsed_glu_bwd3 / bsed_glu_bwd3n, bsed_glu16_fwd / _bwd, bsed_glu_bwd_fused and the GLU_POOL /
-//     GLU_BWD epilogues of bsed_igemm.  bsed_leaky_dropout_fwd / _bwd (discriminator) and bsed_mel_noise (mean teacher)
-//     do NOT: no step that can be captured reaches them;
+//   - the dropout kernels of the plain train step add *seed_add to their seed: bsed_dropout, the eight BsedGluDesc
+//     entry points (bsed_glu16_*, bsed_block0_fwd / _bwd, bsed_glu_bwd_fused, bsed_glu_fwd3 / _bwd3 / _bwd3n: one read,
+//     in bsed_glu_args of bsed_common.h) and the GLU_POOL / GLU_BWD epilogues of bsed_igemm.  bsed_leaky_dropout_fwd /
+//     _bwd (discriminator) and bsed_mel_noise (mean teacher) do NOT: no step that can be captured reaches them;
 //   - bsed_adam_step adds *step_add to its step count and takes *lr instead of its lr argument;
 //   - bsed_step_state_advance (a node of the graph) bumps the two addends.
 // Null pointers = eager mode (the default): the host scalars alone, the same arithmetic, the same bits.  The pointers

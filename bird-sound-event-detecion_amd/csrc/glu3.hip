@@ -47,8 +47,6 @@ struct Glu3Params {
   const uint64_t* seed_add;   // device-resident addend of the seed (HIP-graph replays), or null
 };
 
-static bool glu3_const_tw(const Glu3Params& P) { return P.lgTW == 4; }
-
 // Orders this wave's LDS writes before its later LDS reads.  The hardware executes one wave's LDS instructions in
 // issue order, but the COMPILER may move a 16-byte fragment load above the 2-byte element stores that produce it (type
 // based alias analysis sees unrelated types; __builtin_amdgcn_wave_barrier() does not order memory operations).
@@ -859,12 +857,12 @@ __global__ __launch_bounds__(G3_THREADS, 2) void glu_fwd3_kernel(const Glu3Param
 }
 
 template <int C, int ABF>
-static int launch_glu_fwd3(const Glu3Params& P, int G, hipStream_t s) {
+static int launch_glu_fwd3(const Glu3Params& P, int G, bool const_tw, hipStream_t s) {
   constexpr int NT = C / 32, KS = C / 16;
   const size_t smem = (size_t)NT * KS * 2 * 64 * 16 + 2 * C * sizeof(float) +
                       (C <= 64 ? (size_t)4 * 32 * (C + 4) * sizeof(float) : 0);  // + the waves' staged y rows
   static BsedLdsOnce once, once4;
-  if (glu3_const_tw(P)) {
+  if (const_tw) {
     BSED_HIP(bsed_max_lds(once4, (const void*)glu_fwd3_kernel<C, 4, ABF>));
     hipLaunchKernelGGL((glu_fwd3_kernel<C, 4, ABF>), dim3(G), dim3(G3_THREADS), smem, s, P);
   } else {
@@ -882,10 +880,10 @@ static size_t glu_bwd3_smem() {
 }
 
 template <int C, int ABF>
-static int launch_glu_bwd3(const Glu3Params& P, int G, hipStream_t s) {
+static int launch_glu_bwd3(const Glu3Params& P, int G, bool const_tw, hipStream_t s) {
   const size_t smem = glu_bwd3_smem<C>();
   static BsedLdsOnce once, once4;
-  if (glu3_const_tw(P)) {
+  if (const_tw) {
     BSED_HIP(bsed_max_lds(once4, (const void*)glu_bwd3_kernel<C, 4, ABF>));
     hipLaunchKernelGGL((glu_bwd3_kernel<C, 4, ABF>), dim3(G), dim3(G3_THREADS), smem, s, P);
   } else {
@@ -896,98 +894,57 @@ static int launch_glu_bwd3(const Glu3Params& P, int G, hipStream_t s) {
   return BSED_OK;
 }
 
-static int fill_params(Glu3Params& P, int NB, int H, int W, int C, int TH, int TW, int ph, int pw, const char* who) {
-  BSED_CHECK_ARG(NB > 0 && H > 0 && W > 0 && TH * TW == G3_M && W % TW == 0, "%s: bad shape", who);
-  BSED_CHECK_ARG((ph == 1 || ph == 2) && (pw == 1 || pw == 2), "%s: pooling windows must be 1 or 2", who);
-  P.NB = NB; P.H = H; P.W = W; P.TH = TH; P.TW = TW;
-  P.lgTW = ilog2_exact(TW);
-  BSED_CHECK_ARG(P.lgTW >= 0, "%s: TW must be a power of two", who);
-  P.tilesH = ceil_div(H, TH); P.tilesW = W / TW;
-  const long ntiles = (long)NB * P.tilesH * P.tilesW;
-  BSED_CHECK_ARG(ntiles < (1L << 31) && (long)NB * H * W * C < (1L << 32),
-                 "%s: activation tensor beyond the 32-bit element offsets of this kernel", who);
-  P.ntiles = (int)ntiles;
-  P.ph = ph; P.pw = pw; P.Hp = H / ph; P.Wp = W / pw;
-  return BSED_OK;
-}
-
-extern "C" int bsed_glu_bwd3_slabs(int C) { (void)C; return 4; }
-
-// workgroups of one resident round (persistent kernel): LDS- and register-limited occupancy x 256 CUs
-extern "C" int bsed_glu_bwd3_auto_g(int C) { return C == 32 ? 768 : 512; }
-
-extern "C" int bsed_glu_bwd3(const float* y, const float* scale, const float* shift, const float* w, const float* bias,
-                             const float* dpool, float* g, float* part_dw, float* part_db, float* part_st, int G,
-                             int NB, int H, int W, int C, int TH, int TW, int ph, int pw, float drop_p,
-                             uint32_t rng_stream, uint64_t seed, int act_bf16, void* stream) {
-  BSED_CHECK_ARG(y && scale && shift && w && bias && dpool && g && part_dw && part_db && part_st,
-                 "bsed_glu_bwd3: null tensor");
-  BSED_CHECK_ARG(C == 32 || C == 64, "bsed_glu_bwd3: built for C in {32,64} (got %d)", C);
+// const_tw of the launchers: the plan's variant names the build whose tile width is a compile-time constant
+extern "C" int bsed_glu_bwd3(const BsedGluDesc* desc, void* stream) {
   Glu3Params P;
-  int rc = fill_params(P, NB, H, W, C, TH, TW, ph, pw, "bsed_glu_bwd3");
+  BsedGluPlan plan;
+  const int rc = bsed_glu_geometry(P, desc, BSED_GLU_BWD3, GLU_Y | GLU_LIN | GLU_DPOOL | GLU_G | GLU_PART_DW | GLU_PART_B,
+                                   plan);
   if (rc) return rc;
-  BSED_CHECK_ARG(G > 0 && G <= P.ntiles, "bsed_glu_bwd3: G must be in 1..%d tiles", P.ntiles);
-  P.y = y; P.scale = scale; P.shift = shift; P.w = w; P.bias = bias; P.dpool = dpool;
-  P.g = g; P.part_dw = part_dw; P.part_db = part_db; P.part_st = part_st; P.pooled = nullptr;
-  P.drop_p = drop_p; P.rng_stream = rng_stream; P.seed = seed; P.seed_add = bsed_seed_add_ptr();
+  P.w = desc->w; P.pooled = nullptr;
+  const int C = desc->C, G = desc->G;
+  const bool ctw = plan.variant == 4;
   hipStream_t s = (hipStream_t)stream;
-  if (act_bf16) return C == 64 ? launch_glu_bwd3<64, 1>(P, G, s) : launch_glu_bwd3<32, 1>(P, G, s);
-  if (C == 64) return launch_glu_bwd3<64, 0>(P, G, s);
-  return launch_glu_bwd3<32, 0>(P, G, s);
+  if (desc->act_bf16) return C == 64 ? launch_glu_bwd3<64, 1>(P, G, ctw, s) : launch_glu_bwd3<32, 1>(P, G, ctw, s);
+  if (C == 64) return launch_glu_bwd3<64, 0>(P, G, ctw, s);
+  return launch_glu_bwd3<32, 0>(P, G, ctw, s);
 }
 
-extern "C" int bsed_glu_fwd3_auto_g(int C) {
-  // measured (B = 256): C = 32: 512 / 768 / 1024 / 1536 workgroups 0.447 / 0.367 / 0.412 / 0.350 ms; C = 64: 0.180 / 0.160 / 0.167 / 0.155;
-  // C = 128 (64 KB of weight fragments in LDS, two per CU): 256 / 512 / 768 / 1024 0.514 / 0.422 / 0.454 / 0.435
-  return C == 32 ? 1536 : C == 64 ? 1536 : 512;
-}
-
-extern "C" int bsed_glu_fwd3(const float* y, const float* scale, const float* shift, const float* w, const float* bias,
-                             float* pooled, int G, int NB, int H, int W, int C, int TH, int TW, int ph, int pw,
-                             float drop_p, uint32_t rng_stream, uint64_t seed, int act_bf16, void* stream) {
-  BSED_CHECK_ARG(y && scale && shift && w && bias && pooled, "bsed_glu_fwd3: null tensor");
-  BSED_CHECK_ARG(C == 32 || C == 64 || C == 128, "bsed_glu_fwd3: built for C in {32,64,128} (got %d)", C);
+extern "C" int bsed_glu_fwd3(const BsedGluDesc* desc, void* stream) {
   Glu3Params P;
-  int rc = fill_params(P, NB, H, W, C, TH, TW, ph, pw, "bsed_glu_fwd3");
+  BsedGluPlan plan;
+  const int rc = bsed_glu_geometry(P, desc, BSED_GLU_FWD3, GLU_Y | GLU_LIN | GLU_POOLED, plan);
   if (rc) return rc;
-  BSED_CHECK_ARG(G > 0 && G <= P.ntiles, "bsed_glu_fwd3: G must be in 1..%d tiles", P.ntiles);
+  const int C = desc->C, G = desc->G, TH = P.TH, TW = P.TW, ph = P.ph, pw = P.pw;
   BSED_CHECK_ARG(pw == 1 || TW >= 2, "bsed_glu_fwd3: horizontal pooling needs TW >= 2");
   BSED_CHECK_ARG(ph == 1 || ((TW == 16 || TW == 8 || TW == 2 || (TW == 1 && pw == 1)) && TH % 2 == 0),
                  "bsed_glu_fwd3: vertical pooling is lane-local only for TW in {1,2,8,16} (got %d)", TW);
-  P.y = y; P.scale = scale; P.shift = shift; P.w = w; P.bias = bias; P.dpool = nullptr;
-  P.g = nullptr; P.part_dw = nullptr; P.part_db = nullptr; P.part_st = nullptr; P.pooled = pooled;
-  P.drop_p = drop_p; P.rng_stream = rng_stream; P.seed = seed; P.seed_add = bsed_seed_add_ptr();
+  P.w = desc->w; P.pooled = desc->pooled;
+  const bool ctw = plan.variant == 4;
   hipStream_t s = (hipStream_t)stream;
-  if (act_bf16) return C == 128 ? launch_glu_fwd3<128, 1>(P, G, s) : (C == 64 ? launch_glu_fwd3<64, 1>(P, G, s) : launch_glu_fwd3<32, 1>(P, G, s));
-  if (C == 128) return launch_glu_fwd3<128, 0>(P, G, s);
-  if (C == 64) return launch_glu_fwd3<64, 0>(P, G, s);
-  return launch_glu_fwd3<32, 0>(P, G, s);
+  if (desc->act_bf16) return C == 128 ? launch_glu_fwd3<128, 1>(P, G, ctw, s) : (C == 64 ? launch_glu_fwd3<64, 1>(P, G, ctw, s) : launch_glu_fwd3<32, 1>(P, G, ctw, s));
+  if (C == 128) return launch_glu_fwd3<128, 0>(P, G, ctw, s);
+  if (C == 64) return launch_glu_fwd3<64, 0>(P, G, ctw, s);
+  return launch_glu_fwd3<32, 0>(P, G, ctw, s);
 }
 
-// C = 128: g, d_lin (for the separate weight-gradient pass), db and BatchNorm-backward partials.  frag_table: 128 KB
-// of device scratch that this call fills (bsed_glu_bwd3n_table_bytes()).
-extern "C" size_t bsed_glu_bwd3n_table_bytes(void) { return (size_t)2 * 4 * 8 * 2 * 64 * 16; }
-
-extern "C" int bsed_glu_bwd3n(const float* y, const float* scale, const float* shift, const float* w, const float* bias,
-                              const float* dpool, float* g, float* dlin, float* part_db, float* part_st,
-                              void* frag_table, int G, int NB, int H, int W, int C, int TH, int TW, int ph, int pw,
-                              float drop_p, uint32_t rng_stream, uint64_t seed, int act_bf16, void* stream) {
-  BSED_CHECK_ARG(y && scale && shift && w && bias && dpool && g && dlin && part_db && part_st && frag_table,
-                 "bsed_glu_bwd3n: null tensor");
-  BSED_CHECK_ARG(C == 128, "bsed_glu_bwd3n: built for C = 128 (got %d)", C);
+// C = 128: g, d_lin (for the separate weight-gradient pass), db and BatchNorm-backward partials.  frag_table: the
+// plan's table_bytes (128 KB) of device scratch that this call fills.
+extern "C" int bsed_glu_bwd3n(const BsedGluDesc* desc, void* stream) {
   Glu3Params P;
-  int rc = fill_params(P, NB, H, W, C, TH, TW, ph, pw, "bsed_glu_bwd3n");
+  BsedGluPlan plan;
+  const int rc = bsed_glu_geometry(P, desc, BSED_GLU_BWD3N,
+                                   GLU_Y | GLU_LIN | GLU_DPOOL | GLU_G | GLU_DLIN | GLU_PART_B | GLU_FRAG, plan);
   if (rc) return rc;
-  BSED_CHECK_ARG(G > 0 && 2 * (G - 1) < P.ntiles, "bsed_glu_bwd3n: G workgroups take two tiles at a time: 1..%d",
-                 (P.ntiles + 1) / 2);
-  P.y = y; P.scale = scale; P.shift = shift; P.w = w; P.bias = bias; P.dpool = dpool;
-  P.g = g; P.part_dw = nullptr; P.part_db = part_db; P.part_st = part_st; P.pooled = nullptr;
-  P.drop_p = drop_p; P.rng_stream = rng_stream; P.seed = seed; P.seed_add = bsed_seed_add_ptr();
+  P.w = desc->w; P.pooled = nullptr;
+  void* frag_table = desc->frag_table;
+  float* dlin = desc->dlin;
+  const int G = desc->G;
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(glu3_pack_frags_kernel, dim3(4 * 8 * 64 / 256), dim3(256), 0, s, w, (bf16x8*)frag_table);
-  const size_t smem = bsed_glu_bwd3n_table_bytes() + 2 * 128 * sizeof(float) + (size_t)8 * 32 * (2 * 16 + 8) * 2;
+  hipLaunchKernelGGL(glu3_pack_frags_kernel, dim3(4 * 8 * 64 / 256), dim3(256), 0, s, P.w, (bf16x8*)frag_table);
+  const size_t smem = plan.table_bytes + 2 * 128 * sizeof(float) + (size_t)8 * 32 * (2 * 16 + 8) * 2;
   static BsedLdsOnce once, onceb;
-  if (act_bf16) {
+  if (desc->act_bf16) {
     BSED_HIP(bsed_max_lds(onceb, (const void*)glu_bwd3n_kernel<1>));
     hipLaunchKernelGGL(glu_bwd3n_kernel<1>, dim3(G), dim3(G3N_THREADS), smem, s, P, (const bf16x8*)frag_table, dlin);
   } else {

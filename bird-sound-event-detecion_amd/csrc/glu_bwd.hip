@@ -297,31 +297,18 @@ static int launch_glu_bwd(const GluBwdParams& P, int G, hipStream_t s) {
   return BSED_OK;
 }
 
-extern "C" int bsed_glu_bwd_slabs(int C) { return C >= 128 ? 1 : (C == 64 ? 2 : 4); }
-
-extern "C" int bsed_glu_bwd_fused(const float* y, const float* scale, const float* shift, const float* wfwd,
-                                  const float* wbwd, const float* bias, const float* dpool, float* g, float* part_dw,
-                                  float* part_db, float* part_st, int G, int NB, int H, int W, int C, int TH, int TW,
-                                  int ph, int pw, float drop_p, uint32_t rng_stream, uint64_t seed, void* stream) {
-  BSED_CHECK_ARG(y && scale && shift && wfwd && wbwd && bias && dpool && g && part_dw && part_db && part_st,
-                 "bsed_glu_bwd_fused: null tensor");
-  BSED_CHECK_ARG(C == 32 || C == 64 || C == 128, "bsed_glu_bwd_fused: built for C in {32,64,128} (got %d)", C);
-  BSED_CHECK_ARG(NB > 0 && H > 0 && W > 0 && G > 0 && TH * TW == GB_M && W % TW == 0, "bsed_glu_bwd_fused: bad shape");
-  BSED_CHECK_ARG((ph == 1 || ph == 2) && (pw == 1 || pw == 2), "bsed_glu_bwd_fused: pooling windows must be 1 or 2");
+extern "C" int bsed_glu_bwd_fused(const BsedGluDesc* desc, void* stream) {
   GluBwdParams P;
-  P.y = y; P.scale = scale; P.shift = shift; P.wfwd = wfwd; P.wbwd = wbwd; P.bias = bias; P.dpool = dpool;
-  P.g = g; P.part_dw = part_dw; P.part_db = part_db; P.part_st = part_st;
-  P.NB = NB; P.H = H; P.W = W; P.TH = TH; P.TW = TW;
-  P.lgTW = ilog2_exact(TW);
-  BSED_CHECK_ARG(P.lgTW >= 0, "bsed_glu_bwd_fused: TW must be a power of two");
-  P.tilesH = ceil_div(H, TH); P.tilesW = W / TW;
-  const long ntiles = (long)NB * P.tilesH * P.tilesW;
-  BSED_CHECK_ARG(ntiles < (1L << 31) && G <= ntiles, "bsed_glu_bwd_fused: G must not exceed the %ld tiles", ntiles);
-  P.ntiles = (int)ntiles;
-  P.ph = ph; P.pw = pw; P.Hp = H / ph; P.Wp = W / pw;
-  P.drop_p = drop_p; P.rng_stream = rng_stream; P.seed = seed; P.seed_add = bsed_seed_add_ptr();
+  BsedGluPlan plan;
+  const int rc = bsed_glu_geometry(P, desc, BSED_GLU_BWD_FUSED,
+                                   GLU_Y | GLU_LIN | GLU_WFWD | GLU_DPOOL | GLU_G | GLU_PART_DW | GLU_PART_B, plan);
+  if (rc) return rc;
+  P.wfwd = desc->wfwd; P.wbwd = desc->w;
+  const int C = desc->C, G = desc->G, NW = plan.variant;
   hipStream_t s = (hipStream_t)stream;
-  if (C == 128) return launch_glu_bwd<128, 8>(P, G, s);
-  if (C == 64) return launch_glu_bwd<64, 4>(P, G, s);
-  return launch_glu_bwd<32, 4>(P, G, s);
+  if (C == 128 && NW == 8) return launch_glu_bwd<128, 8>(P, G, s);
+  if (C == 64 && NW == 4) return launch_glu_bwd<64, 4>(P, G, s);
+  if (C == 32 && NW == 4) return launch_glu_bwd<32, 4>(P, G, s);
+  bsed_set_error("bsed_glu_bwd_fused: internal: glu_bwd_fused_kernel<%d, %d> is not built", C, NW);
+  return BSED_ERR_STATE;
 }

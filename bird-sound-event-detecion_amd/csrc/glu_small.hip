@@ -233,35 +233,28 @@ __global__ __launch_bounds__(GB16_THREADS, 3) void glu16_bwd_kernel(
   }
 }
 
-extern "C" int bsed_glu16_fwd(const float* y, const float* scale, const float* shift, const float* wg, const float* bg,
-                              float* out, int B, int H, int W, int C, int ph, int pw, float drop_p, uint32_t rng_stream,
-                              uint64_t seed, void* stream) {
-  BSED_CHECK_ARG(y && scale && shift && wg && bg && out, "bsed_glu16_fwd: null tensor");
-  BSED_CHECK_ARG(C == GS_C, "bsed_glu16_fwd: built for C=16 (got %d)", C);
-  BSED_CHECK_ARG(B > 0 && H > 0 && W > 0 && (ph == 1 || ph == 2) && (pw == 1 || pw == 2) && W % pw == 0,
-                 "bsed_glu16_fwd: bad shape");
-  const long items = (long)B * (H / ph);
-  BSED_CHECK_ARG(items > 0, "bsed_glu16_fwd: empty pooled extent");
-  hipLaunchKernelGGL(glu16_fwd_kernel, dim3((unsigned)std::min<long>(items, 8192)), dim3(GS_THREADS), 0,
-                     (hipStream_t)stream, y, scale, shift, wg, bg, out, B, H, W, ph, pw, drop_p, rng_stream, seed,
-                     bsed_seed_add_ptr());
+extern "C" int bsed_glu16_fwd(const BsedGluDesc* desc, void* stream) {
+  BsedGluPlan plan;
+  const uint64_t* seed_add;
+  const int rc = bsed_glu_args(desc, BSED_GLU_16_FWD, GLU_Y | GLU_LIN | GLU_POOLED, plan, seed_add);
+  if (rc) return rc;
+  const BsedGluDesc& d = *desc;
+  hipLaunchKernelGGL(glu16_fwd_kernel, dim3(d.G), dim3(GS_THREADS), 0, (hipStream_t)stream, d.y, d.scale, d.shift, d.w,
+                     d.bias, d.pooled, d.NB, d.H, d.W, d.ph, d.pw, d.drop_p, d.rng_stream, d.seed, seed_add);
   BSED_LAUNCH_CHECK();
   return BSED_OK;
 }
 
-extern "C" int bsed_glu16_bwd(const float* y, const float* scale, const float* shift, const float* wg, const float* bg,
-                              const float* dpool, float* g_out, float* part_dw, float* part_db, float* part_st, int G,
-                              int B, int H, int W, int C, int ph, int pw, float drop_p, uint32_t rng_stream,
-                              uint64_t seed, void* stream) {
-  BSED_CHECK_ARG(y && scale && shift && wg && bg && dpool && g_out && part_dw && part_db && part_st,
-                 "bsed_glu16_bwd: null tensor");
-  BSED_CHECK_ARG(C == GS_C, "bsed_glu16_bwd: built for C=16 (got %d)", C);
-  BSED_CHECK_ARG(B > 0 && H > 0 && W > 0 && G > 0 && (ph == 1 || ph == 2) && (pw == 1 || pw == 2) && W % pw == 0,
-                 "bsed_glu16_bwd: bad shape");
-  BSED_CHECK_ARG((long)B * H * ((W + 63) / 64) + G < (1L << 31), "bsed_glu16_bwd: too many rows");
-  hipLaunchKernelGGL(glu16_bwd_kernel, dim3(G), dim3(GB16_THREADS), 0, (hipStream_t)stream, y, scale, shift, wg, bg,
-                     dpool, g_out, part_dw, part_db, part_st, B, H, W, ph, pw, drop_p, rng_stream, seed,
-                     bsed_seed_add_ptr());
+extern "C" int bsed_glu16_bwd(const BsedGluDesc* desc, void* stream) {
+  BsedGluPlan plan;
+  const uint64_t* seed_add;
+  const int rc = bsed_glu_args(desc, BSED_GLU_16_BWD, GLU_Y | GLU_LIN | GLU_DPOOL | GLU_G | GLU_PART_DW | GLU_PART_B, plan,
+                               seed_add);
+  if (rc) return rc;
+  const BsedGluDesc& d = *desc;
+  hipLaunchKernelGGL(glu16_bwd_kernel, dim3(d.G), dim3(GB16_THREADS), 0, (hipStream_t)stream, d.y, d.scale, d.shift, d.w,
+                     d.bias, d.dpool, d.g, d.part_dw, d.part_db, d.part_st, d.NB, d.H, d.W, d.ph, d.pw, d.drop_p,
+                     d.rng_stream, d.seed, seed_add);
   BSED_LAUNCH_CHECK();
   return BSED_OK;
 }

@@ -15,8 +15,8 @@ EPI_PLAIN, EPI_STATS, EPI_GLU_POOL, EPI_GLU_BWD, EPI_ADD_STATS2 = (
 PACK_MAX_JOBS = L.CONSTANTS["BSED_PACK_MAX_JOBS"]
 REDUCE_MAX_JOBS = L.CONSTANTS["BSED_REDUCE_MAX_JOBS"]
 BN_EVAL_MAX_JOBS = L.CONSTANTS["BSED_BN_EVAL_MAX_JOBS"]
-IgemmDesc, WgradDesc, HeadBwdDesc, PackJob, ReduceJob, BnEvalJob = (L.STRUCTS["Bsed" + n] for n in (
-    "IgemmDesc", "WgradDesc", "HeadBwdDesc", "PackJob", "ReduceJob", "BnEvalJob"))
+IgemmDesc, WgradDesc, HeadBwdDesc, PackJob, ReduceJob, BnEvalJob, GluDesc, GluPlan = (L.STRUCTS["Bsed" + n] for n in (
+    "IgemmDesc", "WgradDesc", "HeadBwdDesc", "PackJob", "ReduceJob", "BnEvalJob", "GluDesc", "GluPlan"))
 
 TAPS3x3 = [(kh - 1, kw - 1) for kh in range(3) for kw in range(3)]
 TAP1 = ((0, 0),)   # a plain GEMM: (positions, CIN) x (CIN, N)
@@ -682,33 +682,84 @@ def conv0_wgrad(x, dy, NB, H, W, CO, y=None, coef=None, mean=None):
     return part, G
 
 
-def _glu_partials(G, rows, C, dev):
-    """partial sums of a GLU backward on G workgroups: (part_dw (rows,C,C), part_db (G,2,C), part_st (G,2,C))"""
-    return (torch.empty((rows, C, C), device=dev, dtype=torch.float32),
-            torch.empty((G, 2, C), device=dev, dtype=torch.float32),
-            torch.empty((G, 2, C), device=dev, dtype=torch.float32))
+# The eight GLU / first-block entry points: one descriptor (BsedGluDesc), one plan query.  entry point -> its
+# BSED_GLU_* id, whether it cuts the map into tiles, and the KernelTimer label of the instance it launches, a format
+# over C, the plan's variant (v), the PH / SMALL halves of block0's variant and act_bf16 (ab)
+_GLU_KERNELS = {
+    "bsed_glu16_fwd": (L.CONSTANTS["BSED_GLU_16_FWD"], False, "glu16_fwd_kernel"),
+    "bsed_glu16_bwd": (L.CONSTANTS["BSED_GLU_16_BWD"], False, "glu16_bwd_kernel"),
+    "bsed_block0_fwd": (L.CONSTANTS["BSED_GLU_BLOCK0_FWD"], False, "b0_fwd_kernel<{ph}, {small}, {ab}>"),
+    "bsed_block0_bwd": (L.CONSTANTS["BSED_GLU_BLOCK0_BWD"], False, "b0_bwd_kernel<{ph}, {small}, {ab}>"),
+    "bsed_glu_bwd_fused": (L.CONSTANTS["BSED_GLU_BWD_FUSED"], True, "glu_bwd_fused_kernel<{C}, {v}>"),
+    "bsed_glu_fwd3": (L.CONSTANTS["BSED_GLU_FWD3"], True, "glu_fwd3_kernel<{C}, {v}, {ab}>"),
+    "bsed_glu_bwd3": (L.CONSTANTS["BSED_GLU_BWD3"], True, "glu_bwd3_kernel<{C}, {v}, {ab}>"),
+    "bsed_glu_bwd3n": (L.CONSTANTS["BSED_GLU_BWD3N"], True, "glu_bwd3n_kernel<{ab}>"),
+}
+_GLU_ACTIVATIONS = ("y", "dpool", "pooled", "g", "dlin")   # fp32, or all bf16 in the "bf16" mode (_pa, _abf)
+_GLU_PARAMETERS = ("cw", "cb", "w", "bias")                # may be views into a flat parameter buffer (_dp)
+
+
+def _glu_plan(entry, d):
+    """BsedGluPlan of the entry point's launch for the shape fields of d; sets d.G to the plan's"""
+    plan = GluPlan()
+    L.check(L.lib().bsed_glu_plan(ctypes.byref(d), _GLU_KERNELS[entry][0], ctypes.byref(plan)), entry)
+    d.G = plan.G
+    return plan
+
+
+def _glu_label(entry, d, plan):
+    v = plan.variant
+    return _GLU_KERNELS[entry][2].format(C=d.C, v=v, ph=v & 15, small="true" if v >> 4 else "false", ab=d.act_bf16)
+
+
+def _glu_desc(entry, NB, H, W, C, pool, drop_p, rng_stream, seed, **tensors):
+    """(BsedGluDesc, its plan) of the entry point's launch on these tensors"""
+    d = GluDesc(NB=NB, H=H, W=W, C=C, ph=pool[0], pw=pool[1], drop_p=drop_p, rng_stream=rng_stream, seed=seed,
+                act_bf16=_abf(*(tensors.get(n) for n in _GLU_ACTIVATIONS)))
+    if _GLU_KERNELS[entry][1]:
+        d.TH, d.TW = tile_for(W)
+    for name, t in tensors.items():
+        setattr(d, name, _pa(t) if name in _GLU_ACTIVATIONS else _dp(t) if name in _GLU_PARAMETERS else L.ptr(t))
+    return d, _glu_plan(entry, d)
+
+
+def _glu_launch(entry, d, plan, flops, nbytes):
+    """launch the entry point; the KernelTimer hears of it under the label of the instance the plan names"""
+    if L.timer is not None:
+        label = _glu_label(entry, d, plan)
+        if _GLU_KERNELS[entry][1]:
+            return _launch((label, 1, d.C, d.C, d.H, d.W), flops, lambda: L.call(entry, ctypes.byref(d), L.stream()), nbytes)
+        _note(label, f"{d.H}x{d.W}", flops, nbytes)
+    L.call(entry, ctypes.byref(d), L.stream())
+
+
+def _glu_partials(plan, C, dev):
+    """partial sums of a GLU backward as its plan sizes them: (part_dw (dw_rows,C,C), part_db (G,2,C), part_st (G,2,C))"""
+    return (torch.empty((plan.dw_rows, C, C), device=dev, dtype=torch.float32),
+            torch.empty((plan.G, 2, C), device=dev, dtype=torch.float32),
+            torch.empty((plan.G, 2, C), device=dev, dtype=torch.float32))
 
 
 def glu16_fwd(y, scale, shift, wg, bg, B, H, W, pool, drop_p, rng_stream, seed):
     ph, pw = pool
     out = torch.empty((B, H // ph, W // pw, 16), device=y.device, dtype=torch.float32)
-    _note("glu16_fwd_kernel", f"{H}x{W}", 2.0 * B * H * W * 256, 4.0 * B * H * W * 16 * (1.0 + 1.0 / (ph * pw)))
-    L.call("bsed_glu16_fwd", L.ptr(y), L.ptr(scale), L.ptr(shift), _dp(wg), _dp(bg), L.ptr(out), B, H, W, 16,
-           ph, pw, drop_p, rng_stream, seed, L.stream())
+    d, plan = _glu_desc("bsed_glu16_fwd", B, H, W, 16, pool, drop_p, rng_stream, seed, y=y, scale=scale,
+                        shift=shift, w=wg, bias=bg, pooled=out)
+    _glu_launch("bsed_glu16_fwd", d, plan, 2.0 * B * H * W * 256, 4.0 * B * H * W * 16 * (1.0 + 1.0 / (ph * pw)))
     return out
 
 
 def glu16_bwd(y, scale, shift, wg, bg, dpool, B, H, W, pool, drop_p, rng_stream, seed):
     """returns (g, part_dw (G,16,16), part_db (G,2,16), part_st (G,2,16), G)"""
     ph, pw = pool
-    dev = y.device
-    G = int(min(2048, B * H))
     g = torch.empty_like(y)
-    part_dw, part_db, part_st = _glu_partials(G, G, 16, dev)
-    _note("glu16_bwd_kernel", f"{H}x{W}", 3 * 2.0 * B * H * W * 256, 4.0 * B * H * W * 16 * (2.0 + 1.0 / (ph * pw)))
-    L.call("bsed_glu16_bwd", L.ptr(y), L.ptr(scale), L.ptr(shift), _dp(wg), _dp(bg), L.ptr(dpool), L.ptr(g),
-           L.ptr(part_dw), L.ptr(part_db), L.ptr(part_st), G, B, H, W, 16, ph, pw, drop_p, rng_stream, seed, L.stream())
-    return g, part_dw, part_db, part_st, G
+    d, plan = _glu_desc("bsed_glu16_bwd", B, H, W, 16, pool, drop_p, rng_stream, seed, y=y, scale=scale,
+                        shift=shift, w=wg, bias=bg, dpool=dpool, g=g)
+    part_dw, part_db, part_st = _glu_partials(plan, 16, y.device)
+    d.part_dw, d.part_db, d.part_st = L.ptr(part_dw), L.ptr(part_db), L.ptr(part_st)
+    _glu_launch("bsed_glu16_bwd", d, plan, 3 * 2.0 * B * H * W * 256,
+                4.0 * B * H * W * 16 * (2.0 + 1.0 / (ph * pw)))
+    return g, part_dw, part_db, part_st, plan.G
 
 
 def block0_stats(x, cw, cb, NB, H, W):
@@ -728,29 +779,24 @@ def block0_stats(x, cw, cb, NB, H, W):
 def block0_fwd(x, cw, cb, scale, shift, wg, bg, B, H, W, pool, drop_p, rng_stream, seed, out_dtype=torch.float32):
     ph, pw = pool
     out = torch.empty((B, H // ph, W // pw, 16), device=x.device, dtype=out_dtype)
-    ab = _abf(out)
-    small = "false" if ab else ("true" if B * H * W < (1 << 28) else "false")
-    _note(f"b0_fwd_kernel<{ph}, {small}, {ab}>", f"{H}x{W}", 2.0 * B * H * W * (9 * 16 + 256),
-          B * H * W * (4.0 + _esz(out) * 16.0 / (ph * pw)))
-    L.call("bsed_block0_fwd", L.ptr(x), _dp(cw), _dp(cb), L.ptr(scale), L.ptr(shift), _dp(wg), _dp(bg), _pa(out), B,
-           H, W, 16, ph, pw, drop_p, rng_stream, seed, ab, L.stream())
+    d, plan = _glu_desc("bsed_block0_fwd", B, H, W, 16, pool, drop_p, rng_stream, seed, x=x, cw=cw, cb=cb,
+                        scale=scale, shift=shift, w=wg, bias=bg, pooled=out)
+    _glu_launch("bsed_block0_fwd", d, plan, 2.0 * B * H * W * (9 * 16 + 256),
+                B * H * W * (4.0 + _esz(out) * 16.0 / (ph * pw)))
     return out
 
 
 def block0_bwd(x, cw, cb, scale, shift, wg, bg, dpool, B, H, W, pool, drop_p, rng_stream, seed):
     """returns (part_dw (G,16,16), part_db (G,2,16), part_st (G,2,16), part_gx (G,9,16), G)"""
     ph, pw = pool
-    dev = x.device
-    G = int(min(8192, B * (H // ph)))   # 2048 / 4096 / 8192 workgroups: 0.983 / 0.966 / 0.957 ms
-    part_dw, part_db, part_st = _glu_partials(G, G, 16, dev)
-    part_gx = torch.empty((G, 9, 16), device=dev, dtype=torch.float32)
-    ab = _abf(dpool)
-    _note(f"b0_bwd_kernel<{ph}, {'true' if B * H * W < (1 << 28) else 'false'}, {ab}>", f"{H}x{W}", 2.0 * B * H * W * (2 * 9 * 16 + 3 * 256),
-          B * H * W * (4.0 + _esz(dpool) * 16.0 / (ph * pw)))
-    L.call("bsed_block0_bwd", L.ptr(x), _dp(cw), _dp(cb), L.ptr(scale), L.ptr(shift), _dp(wg), _dp(bg), _pa(dpool),
-           L.ptr(part_dw), L.ptr(part_db), L.ptr(part_st), L.ptr(part_gx), G, B, H, W, 16, ph, pw, drop_p, rng_stream,
-           seed, ab, L.stream())
-    return part_dw, part_db, part_st, part_gx, G
+    d, plan = _glu_desc("bsed_block0_bwd", B, H, W, 16, pool, drop_p, rng_stream, seed, x=x, cw=cw, cb=cb,
+                        scale=scale, shift=shift, w=wg, bias=bg, dpool=dpool)
+    part_dw, part_db, part_st = _glu_partials(plan, 16, x.device)
+    part_gx = torch.empty((plan.G, 9, 16), device=x.device, dtype=torch.float32)
+    d.part_dw, d.part_db, d.part_st, d.part_gx = L.ptr(part_dw), L.ptr(part_db), L.ptr(part_st), L.ptr(part_gx)
+    _glu_launch("bsed_block0_bwd", d, plan, 2.0 * B * H * W * (2 * 9 * 16 + 3 * 256),
+                B * H * W * (4.0 + _esz(dpool) * 16.0 / (ph * pw)))
+    return part_dw, part_db, part_st, part_gx, plan.G
 
 
 def block0_wgrad_finish(part_gx, G, xr64, coef, mean, cw, cb, dst, accumulate=True):
@@ -759,22 +805,22 @@ def block0_wgrad_finish(part_gx, G, xr64, coef, mean, cw, cb, dst, accumulate=Tr
            _dp(cw), _dp(cb), _dp(dst), 1 if accumulate else 0, 16, L.stream())
 
 
-def glu_bwd_fused(y, scale, shift, wfwd, w, bias, dpool, B, H, W, C, pool, drop_p, rng_stream, seed):
-    """returns (g, part_dw (G*slabs,C,C), part_db (G,2,C), part_st (G,2,C), G, slabs)"""
-    ph, pw = pool
-    dev = y.device
-    TH, TW, ntiles = _map_tiles(B, H, W)
-    G = int(min(ntiles, 256 * (1 if C == 128 else (2 if C == 64 else 3))))
-    slabs = L.lib().bsed_glu_bwd_slabs(C)
+def _glu_bwd_tiled(entry, esz, y, dpool, B, H, W, C, pool, drop_p, rng_stream, seed, **weights):
+    """a tiled fused GLU backward with its weight-gradient slabs; returns (g, part_dw (G*slabs,C,C), part_db (G,2,C),
+    part_st (G,2,C), G, slabs)"""
     g = torch.empty_like(y)
-    part_dw, part_db, part_st = _glu_partials(G, G * slabs, C, dev)
-    flops = 3 * 2.0 * B * H * W * C * C
-    nbytes = 4.0 * B * H * W * C * (2.0 + 1.0 / (ph * pw))  # y, g, d_pooled
-    _launch((f"glu_bwd_fused_kernel<{C}, {8 if C == 128 else 4}>", 1, C, C, H, W), flops,
-            lambda: L.call("bsed_glu_bwd_fused", L.ptr(y), L.ptr(scale), L.ptr(shift), L.ptr(wfwd), _dp(w),
-                           _dp(bias), L.ptr(dpool), L.ptr(g), L.ptr(part_dw), L.ptr(part_db), L.ptr(part_st),
-                           G, B, H, W, C, TH, TW, ph, pw, drop_p, rng_stream, seed, L.stream()), nbytes)
-    return g, part_dw, part_db, part_st, G, slabs
+    d, plan = _glu_desc(entry, B, H, W, C, pool, drop_p, rng_stream, seed, y=y, dpool=dpool, g=g, **weights)
+    part_dw, part_db, part_st = _glu_partials(plan, C, y.device)
+    d.part_dw, d.part_db, d.part_st = L.ptr(part_dw), L.ptr(part_db), L.ptr(part_st)
+    _glu_launch(entry, d, plan, 3 * 2.0 * B * H * W * C * C,
+                esz * B * H * W * C * (2.0 + 1.0 / (pool[0] * pool[1])))  # y, g, d_pooled
+    return g, part_dw, part_db, part_st, plan.G, plan.dw_rows // plan.G
+
+
+def glu_bwd_fused(y, scale, shift, wfwd, w, bias, dpool, B, H, W, C, pool, drop_p, rng_stream, seed):
+    """fp32-core fused GLU backward (C in {32,64,128}); returns (g, part_dw, part_db, part_st, G, slabs)"""
+    return _glu_bwd_tiled("bsed_glu_bwd_fused", 4.0, y, dpool, B, H, W, C, pool, drop_p, rng_stream, seed,
+                          scale=scale, shift=shift, wfwd=wfwd, w=w, bias=bias)
 
 
 def glu_fwd3_supported(W, C, pool):
@@ -786,34 +832,18 @@ def glu_fwd3_supported(W, C, pool):
 def glu_fwd3(y, scale, shift, w, bias, B, H, W, C, pool, drop_p, rng_stream, seed):
     """split-fp32 GLU forward: BN-apply -> Linear -> gate -> dropout -> avg-pool in one pass over y"""
     ph, pw = pool
-    TH, TW, ntiles = _map_tiles(B, H, W)
-    G = int(min(ntiles, L.lib().bsed_glu_fwd3_auto_g(C)))
     out = torch.empty((B, H // ph, W // pw, C), device=y.device, dtype=y.dtype)
-    ab = _abf(y)
-    _launch((f"glu_fwd3_kernel<{C}, {4 if TW == 16 else -1}, {ab}>", 1, C, C, H, W), 2.0 * B * H * W * C * C,
-            lambda: L.call("bsed_glu_fwd3", _pa(y), L.ptr(scale), L.ptr(shift), _dp(w), _dp(bias),
-                           _pa(out), G, B, H, W, C, TH, TW, ph, pw, drop_p, rng_stream, seed, ab, L.stream()),
-            _esz(y) * B * H * W * C * (1.0 + 1.0 / (ph * pw)))  # y, pooled
+    d, plan = _glu_desc("bsed_glu_fwd3", B, H, W, C, pool, drop_p, rng_stream, seed, y=y, scale=scale, shift=shift,
+                        w=w, bias=bias, pooled=out)
+    _glu_launch("bsed_glu_fwd3", d, plan, 2.0 * B * H * W * C * C,
+                _esz(y) * B * H * W * C * (1.0 + 1.0 / (ph * pw)))  # y, pooled
     return out
 
 
 def glu_bwd3(y, scale, shift, w, bias, dpool, B, H, W, C, pool, drop_p, rng_stream, seed):
     """split-fp32 fused GLU backward (C in {32,64}); returns like glu_bwd_fused"""
-    ph, pw = pool
-    dev = y.device
-    TH, TW, ntiles = _map_tiles(B, H, W)
-    G = int(min(ntiles, L.lib().bsed_glu_bwd3_auto_g(C)))
-    slabs = L.lib().bsed_glu_bwd3_slabs(C)
-    g = torch.empty_like(y)
-    part_dw, part_db, part_st = _glu_partials(G, G * slabs, C, dev)
-    flops = 3 * 2.0 * B * H * W * C * C
-    ab = _abf(y, dpool)
-    _launch((f"glu_bwd3_kernel<{C}, {4 if TW == 16 else -1}, {ab}>", 1, C, C, H, W), flops,
-            lambda: L.call("bsed_glu_bwd3", _pa(y), L.ptr(scale), L.ptr(shift), _dp(w), _dp(bias),
-                           _pa(dpool), _pa(g), L.ptr(part_dw), L.ptr(part_db), L.ptr(part_st), G, B, H,
-                           W, C, TH, TW, ph, pw, drop_p, rng_stream, seed, ab, L.stream()),
-            _esz(y) * B * H * W * C * (2.0 + 1.0 / (ph * pw)))  # y, g, d_pooled
-    return g, part_dw, part_db, part_st, G, slabs
+    return _glu_bwd_tiled("bsed_glu_bwd3", _esz(y), y, dpool, B, H, W, C, pool, drop_p, rng_stream, seed,
+                          scale=scale, shift=shift, w=w, bias=bias)
 
 
 _frag_tables = {}
@@ -821,24 +851,20 @@ _frag_tables = {}
 
 def glu_bwd3n(y, scale, shift, w, bias, dpool, B, H, W, C, pool, drop_p, rng_stream, seed):
     """split-fp32 GLU backward for C = 128 without the weight gradient: returns (g, d_lin, part_db, part_st, G)"""
-    ph, pw = pool
     dev = y.device
-    TH, TW, ntiles = _map_tiles(B, H, W)
-    G = int(min((ntiles + 1) // 2, 256))  # 8-wave workgroups take two tiles at a time
-    tb = _frag_tables.get(str(dev))
-    if tb is None:
-        tb = _frag_tables[str(dev)] = torch.empty(L.lib().bsed_glu_bwd3n_table_bytes(), device=dev, dtype=torch.uint8)
     g = torch.empty_like(y)
     dlin = torch.empty_like(y)
-    part_db = torch.empty((G, 2, C), device=dev, dtype=torch.float32)
-    part_st = torch.empty((G, 2, C), device=dev, dtype=torch.float32)
-    ab = _abf(y, dpool)
-    _launch((f"glu_bwd3n_kernel<{ab}>", 1, C, C, H, W), 2 * 2.0 * B * H * W * C * C,
-            lambda: L.call("bsed_glu_bwd3n", _pa(y), L.ptr(scale), L.ptr(shift), _dp(w), _dp(bias),
-                           _pa(dpool), _pa(g), _pa(dlin), L.ptr(part_db), L.ptr(part_st),
-                           tb.data_ptr(), G, B, H, W, C, TH, TW, ph, pw, drop_p, rng_stream, seed, ab, L.stream()),
-            _esz(y) * B * H * W * C * (3.0 + 1.0 / (ph * pw)))  # y, g, d_lin, d_pooled
-    return g, dlin, part_db, part_st, G
+    d, plan = _glu_desc("bsed_glu_bwd3n", B, H, W, C, pool, drop_p, rng_stream, seed, y=y, scale=scale,
+                        shift=shift, w=w, bias=bias, dpool=dpool, g=g, dlin=dlin)
+    tb = _frag_tables.get(str(dev))
+    if tb is None:
+        tb = _frag_tables[str(dev)] = torch.empty(plan.table_bytes, device=dev, dtype=torch.uint8)
+    part_db = torch.empty((plan.G, 2, C), device=dev, dtype=torch.float32)
+    part_st = torch.empty((plan.G, 2, C), device=dev, dtype=torch.float32)
+    d.part_db, d.part_st, d.frag_table = L.ptr(part_db), L.ptr(part_st), tb.data_ptr()
+    _glu_launch("bsed_glu_bwd3n", d, plan, 2 * 2.0 * B * H * W * C * C,
+                _esz(y) * B * H * W * C * (3.0 + 1.0 / (pool[0] * pool[1])))  # y, g, d_lin, d_pooled
+    return g, dlin, part_db, part_st, plan.G
 
 
 def glu_route(direction, C, W, pool, mode, fused=True):

@@ -303,18 +303,69 @@ int bsed_colsum_part(const float* in, long M, int C, int pitch, float* part, int
 /* nn.Dropout(p) with a stateless Philox mask: out = in * keep/(1-p); the same call is its backward */
 int bsed_dropout(const float* in, float* out, long n, float p, uint32_t rng_stream, uint64_t seed, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * GLU half of a CNN block (BatchNorm apply -> Linear -> sigmoid gate -> Dropout -> AvgPool2d, src/models/CNN.py:5-16,
+ * 59-67, and its autograd) and the fused first block: eight entry points, one descriptor, one plan query.
+ * A field an entry point does not read must be NULL / 0 for it (checked); all eight read NB, H, W, C, ph, pw (pooling
+ * windows of 1 or 2), drop_p, rng_stream, seed and G.  The tiled kernels also read TH, TW (TH*TW == 128, TW a power of
+ * two dividing W); the streaming kernels (glu16, block0) have no tile and want W % pw == 0 and H >= ph.
+ *   entry point          tensors read                                        tensors written
+ *   bsed_glu16_fwd       y scale shift w bias                                pooled
+ *   bsed_glu16_bwd       y scale shift w bias dpool                          g part_dw part_db part_st
+ *   bsed_block0_fwd      x cw cb scale shift w bias              [act_bf16]  pooled
+ *   bsed_block0_bwd      x cw cb scale shift w bias dpool        [act_bf16]  part_dw part_db part_st part_gx
+ *   bsed_glu_bwd_fused   y scale shift w wfwd bias dpool                     g part_dw part_db part_st
+ *   bsed_glu_fwd3        y scale shift w bias                    [act_bf16]  pooled
+ *   bsed_glu_bwd3        y scale shift w bias dpool              [act_bf16]  g part_dw part_db part_st
+ *   bsed_glu_bwd3n       y scale shift w bias dpool              [act_bf16]  g dlin part_db part_st frag_table
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct BsedGluDesc {
+  const float* x;        /* block0: the input map (NB,H,W)                                             */
+  const float* y;        /* pre-BatchNorm conv output (NB,H,W,C)                                       */
+  const float *cw, *cb;  /* block0: the (16,1,3,3) conv weight and its bias                            */
+  const float *scale, *shift;   /* (C) BatchNorm apply                                                 */
+  const float* w;        /* the (C,C) Linear weight itself, [n][c]                                     */
+  const float* wfwd;     /* bsed_glu_bwd_fused: bsed_pack_weight'ed W^T, [c][n]                        */
+  const float* bias;     /* (C) Linear bias                                                            */
+  const float* dpool;    /* gradient w.r.t. the pooled output (NB,H/ph,W/pw,C)                         */
+  float* pooled;         /* forward output (NB,H/ph,W/pw,C)                                            */
+  float* g;              /* dL/d(BatchNorm output) (NB,H,W,C)                                          */
+  float* dlin;           /* bsed_glu_bwd3n: d_lin (NB,H,W,C) for the separate weight-gradient pass      */
+  float* part_dw;        /* (BsedGluPlan.dw_rows, C, C) per-workgroup partial slabs of dW              */
+  float *part_db, *part_st;     /* (G,2,C): slot 0 = sum d_lin; (sum g, sum g*y) for bsed_bn_bwd       */
+  float* part_gx;        /* block0: (G,9,16) partial sums of g x_tap for bsed_block0_wgrad_finish      */
+  void* frag_table;      /* bsed_glu_bwd3n: BsedGluPlan.table_bytes of device scratch, filled by the call */
+  int NB, H, W, C;
+  int TH, TW;            /* spatial tile of the tiled kernels; 0, 0 for the streaming ones             */
+  int ph, pw;            /* pooling window                                                             */
+  float drop_p;          /* dropout probability (0 = off)                                              */
+  uint32_t rng_stream;   /* stream id of the mask (layer id)                                           */
+  uint64_t seed;
+  int act_bf16;          /* 1: y, dpool, g, dlin, pooled are bf16 tensors ("bf16" throughput mode); 0 = fp32 */
+  int G;                 /* workgroups to launch: BsedGluPlan.G, or any value in 1..max_G              */
+} BsedGluDesc;
+
+enum {                   /* one value per entry point, for bsed_glu_plan                               */
+  BSED_GLU_16_FWD = 0, BSED_GLU_16_BWD = 1, BSED_GLU_BLOCK0_FWD = 2, BSED_GLU_BLOCK0_BWD = 3,
+  BSED_GLU_BWD_FUSED = 4, BSED_GLU_FWD3 = 5, BSED_GLU_BWD3 = 6, BSED_GLU_BWD3N = 7
+};
+typedef struct BsedGluPlan {
+  int G;                 /* workgroups the library recommends (one resident round of a persistent kernel) */
+  int max_G;             /* the largest G the entry point accepts (its work items)                      */
+  int dw_rows;           /* rows of part_dw at that G: G * slabs per workgroup (0: no part_dw)          */
+  int variant;           /* template arguments the library picks beyond C and act_bf16 (labels of profiles and bench
+                          * lines): glu_fwd3 / glu_bwd3 the compile-time log2 tile width (4, or -1 = run time);
+                          * glu_bwd_fused NW (waves per workgroup); block0 PH | SMALL << 4; 0 otherwise */
+  size_t table_bytes;    /* size of frag_table (0: none)                                                */
+} BsedGluPlan;
+/* checks the shape fields of desc (pointers and G are ignored) and fills *out; makes no HIP call.  The entry points
+ * run the same checks, then want every tensor of their row above and G in 1..max_G. */
+int bsed_glu_plan(const BsedGluDesc* desc /*host*/, int kernel, BsedGluPlan* out);
+
 /* GLU stage of a 16-channel block as HBM-bound streaming kernels (csrc/glu_small.hip): same math as
- * bsed_igemm(BSED_EPI_GLU_POOL) / the GLU backward chain (src/models/CNN.py:5-16,59-67), one pass over y.
- *   forward : y (B,H,W,16) -> pooled (B,H/ph,W/pw,16)
- *   backward: y, dpool -> g = dL/d(BN output) (B,H,W,16), per-workgroup partials part_dw (G,16,16),
- *             part_db (G,2,16) [slot 0], part_st (G,2,16) = (sum g, sum g*y) for bsed_bn_bwd */
-int bsed_glu16_fwd(const float* y, const float* scale, const float* shift, const float* wg, const float* bg,
-                   float* out, int B, int H, int W, int C, int ph, int pw, float drop_p, uint32_t rng_stream,
-                   uint64_t seed, void* stream);
-int bsed_glu16_bwd(const float* y, const float* scale, const float* shift, const float* wg, const float* bg,
-                   const float* dpool, float* g_out, float* part_dw, float* part_db, float* part_st, int G, int B,
-                   int H, int W, int C, int ph, int pw, float drop_p, uint32_t rng_stream, uint64_t seed,
-                   void* stream);
+ * bsed_igemm(BSED_EPI_GLU_POOL) / the GLU backward chain, one pass over y. */
+int bsed_glu16_fwd(const BsedGluDesc* desc /*host*/, void* stream);
+int bsed_glu16_bwd(const BsedGluDesc* desc /*host*/, void* stream);
 
 /* The whole first CNN block (conv3x3 1->16, BatchNorm, GLU, dropout, avg-pool: src/models/CNN.py:46-67, i = 0) WITHOUT
  * its conv output and gradient tensors in HBM (csrc/block0.hip): y0 is a 9-tap stencil of the input and is recomputed
@@ -329,54 +380,23 @@ int bsed_glu16_bwd(const float* y, const float* scale, const float* shift, const
 int bsed_block0_stats(const float* x, const float* cw_t /* the (16,1,3,3) weight transposed: [tap][channel] */,
                       const float* cb, float* stats, float* xr_part, double* xr64,
                       int G, int NB, int H, int W, int CO, void* stream);
-int bsed_block0_fwd(const float* x, const float* cw, const float* cb, const float* scale, const float* shift,
-                    const float* wg, const float* bg, float* out, int B, int H, int W, int CO, int ph, int pw,
-                    float drop_p, uint32_t rng_stream, uint64_t seed,
-                    int act_bf16 /* 1: the pooled output / its gradient is a bf16 tensor (bf16 mode) */, void* stream);
-int bsed_block0_bwd(const float* x, const float* cw, const float* cb, const float* scale, const float* shift,
-                    const float* wg, const float* bg, const float* dpool, float* part_dw, float* part_db,
-                    float* part_st, float* part_gx, int G, int B, int H, int W, int CO, int ph, int pw, float drop_p,
-                    uint32_t rng_stream, uint64_t seed,
-                    int act_bf16 /* 1: the pooled output / its gradient is a bf16 tensor (bf16 mode) */, void* stream);
+int bsed_block0_fwd(const BsedGluDesc* desc /*host*/, void* stream);
+int bsed_block0_bwd(const BsedGluDesc* desc /*host*/, void* stream);
 int bsed_block0_wgrad_finish(const float* part_gx, int G, const double* xr64, const float* coef, const float* mean,
                              const float* cw, const float* cb, float* dst, int accumulate, int CO, void* stream);
 
-/* Fused GLU backward for C in {32,64,128} (csrc/glu_bwd.hip): y, d_pooled -> g = dL/d(BN output) in one pass, with
- * the three contractions (lin recompute, g, dW) chained on chip.  wfwd = bsed_pack_weight'ed W^T ([c][n]),
- * wbwd = the (C,C) Linear weight itself.  Outputs per-workgroup partials: part_dw (G*bsed_glu_bwd_slabs(C), C, C),
- * part_db (G,2,C) [slot 0 = sum d_lin], part_st (G,2,C) = (sum g, sum g*y) for bsed_bn_bwd. */
-int bsed_glu_bwd_fused(const float* y, const float* scale, const float* shift, const float* wfwd,
-                       const float* wbwd, const float* bias, const float* dpool, float* g, float* part_dw,
-                       float* part_db, float* part_st, int G, int NB, int H, int W, int C, int TH, int TW, int ph,
-                       int pw, float drop_p, uint32_t rng_stream, uint64_t seed, void* stream);
-int bsed_glu_bwd_slabs(int C);
-
+/* Fused GLU backward for C in {32,64,128} (csrc/glu_bwd.hip): y, d_pooled -> g in one pass, with the three
+ * contractions (lin recompute, g, dW) chained on chip on the fp32 matrix cores. */
+int bsed_glu_bwd_fused(const BsedGluDesc* desc /*host*/, void* stream);
 /* The same fused GLU backward in the split-fp32 ("bf16x3") contraction mode for C in {32,64} (csrc/glu3.hip): all
- * three contractions on the bf16 matrix cores, activations never staged through LDS.  w = the (C,C) Linear weight.
- * part_dw holds G * bsed_glu_bwd3_slabs(C) slabs; bsed_glu_bwd3_auto_g(C) = workgroups of one resident round. */
-int bsed_glu_bwd3(const float* y, const float* scale, const float* shift, const float* w, const float* bias,
-                  const float* dpool, float* g, float* part_dw, float* part_db, float* part_st, int G, int NB, int H,
-                  int W, int C, int TH, int TW, int ph, int pw, float drop_p, uint32_t rng_stream, uint64_t seed,
-                  int act_bf16 /* 1: y, d_pooled, g, d_lin, pooled are bf16 tensors (bf16 mode) */, void* stream);
-int bsed_glu_bwd3_slabs(int C);
-int bsed_glu_bwd3_auto_g(int C);
-/* C = 128 in the split-fp32 mode: g, db and BatchNorm partials as above, but d_lin (NB,H,W,128) is written out and
- * the Linear weight gradient is a separate 1-tap bsed_wgrad3(in = y with a_scale/a_shift, dy = d_lin).  frag_table:
- * bsed_glu_bwd3n_table_bytes() of device scratch (filled by the call: both weight operands pre-split). */
-int bsed_glu_bwd3n(const float* y, const float* scale, const float* shift, const float* w, const float* bias,
-                   const float* dpool, float* g, float* dlin, float* part_db, float* part_st, void* frag_table, int G,
-                   int NB, int H, int W, int C, int TH, int TW, int ph, int pw, float drop_p, uint32_t rng_stream,
-                   uint64_t seed,
-                  int act_bf16 /* 1: y, d_pooled, g, d_lin, pooled are bf16 tensors (bf16 mode) */, void* stream);
-size_t bsed_glu_bwd3n_table_bytes(void);
-/* Forward of the same stage in the split-fp32 mode, C in {32,64,128}: y (NB,H,W,C) -> pooled (NB,H/ph,W/pw,C);
- * replaces bsed_igemm(BSED_EPI_GLU_POOL) (GLU.forward + nn.Dropout + nn.AvgPool2d, src/models/CNN.py:5-16,59-67).
+ * three contractions on the bf16 matrix cores, activations never staged through LDS. */
+int bsed_glu_bwd3(const BsedGluDesc* desc /*host*/, void* stream);
+/* C = 128 in the split-fp32 mode: g, db and BatchNorm partials as above, but d_lin is written out and the Linear
+ * weight gradient is a separate 1-tap bsed_wgrad3(in = y with a_scale/a_shift, dy = d_lin). */
+int bsed_glu_bwd3n(const BsedGluDesc* desc /*host*/, void* stream);
+/* Forward of the same stage in the split-fp32 mode, C in {32,64,128}; replaces bsed_igemm(BSED_EPI_GLU_POOL).
  * Vertical pooling (ph = 2) is supported for tile widths TW in {2,8,16}. */
-int bsed_glu_fwd3(const float* y, const float* scale, const float* shift, const float* w, const float* bias,
-                  float* pooled, int G, int NB, int H, int W, int C, int TH, int TW, int ph, int pw, float drop_p,
-                  uint32_t rng_stream, uint64_t seed,
-                  int act_bf16 /* 1: y, d_pooled, g, d_lin, pooled are bf16 tensors (bf16 mode) */, void* stream);
-int bsed_glu_fwd3_auto_g(int C);
+int bsed_glu_fwd3(const BsedGluDesc* desc /*host*/, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Clip-level domain discriminator glue (csrc/disc.hip); replaces Clip_Discriminator.forward

@@ -85,7 +85,7 @@ def test_every_prototype_is_bound_from_the_header():
 @pytest.mark.skipif(not (shutil.which("cc") or shutil.which("gcc")), reason="no host C compiler")
 def test_struct_layouts_and_constants_match_the_c_compiler(tmp_path):
     assert set(L.STRUCTS) == {"BsedMelCfg", "BsedIgemmDesc", "BsedPackJob", "BsedWgradDesc", "BsedReduceJob",
-                              "BsedBnEvalJob", "BsedHeadBwdDesc"}
+                              "BsedBnEvalJob", "BsedHeadBwdDesc", "BsedGluDesc", "BsedGluPlan"}
     assert {"BSED_EPI_PLAIN", "BSED_EPI_STATS", "BSED_EPI_GLU_POOL", "BSED_EPI_GLU_BWD", "BSED_EPI_ADD_STATS2",
             "BSED_PACK_MAX_JOBS", "BSED_REDUCE_MAX_JOBS", "BSED_BN_EVAL_MAX_JOBS"} <= set(L.CONSTANTS)
     lines, want = [], []
