@@ -50,7 +50,7 @@ class BsedError(RuntimeError):
 # enums and `#define NAME <int>` -- over the scalar types below and pointers (void*); anything else raises with the
 # offending text.
 _SCALARS = {"int": ctypes.c_int, "long": ctypes.c_long, "long long": ctypes.c_longlong, "size_t": ctypes.c_size_t,
-            "float": ctypes.c_float, "double": ctypes.c_double,
+            "float": ctypes.c_float, "double": ctypes.c_double, "char": ctypes.c_char,
             "uint32_t": ctypes.c_uint32, "uint64_t": ctypes.c_uint64}
 _ITEM = re.compile(r"""(?: typedef\s+struct\s+\w+\s*\{(?P<fields>[^{}]*)\}\s*(?P<struct>\w+)\s*;
                         | enum\s*\{(?P<enum>[^{}]*)\}\s*;

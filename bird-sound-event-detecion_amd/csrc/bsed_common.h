@@ -183,6 +183,45 @@ static int bsed_tile_geometry(Params& P, const char* who, int cin_mult, int pitc
 }
 
 // ----------------------------------------------------------------------------------------------
+// Host side of the six contraction entry points (BsedContractPlan, include/bsed.h).  Each kernel has ONE function
+// bsed_run_*(desc, stream, plan): its prepare step (shape checks, geometry, LDS bytes, grid), then either the pointer / G
+// checks and the launch (plan == null: the entry point) or the plan's numbers and the label (capi.hip's queries).
+// ----------------------------------------------------------------------------------------------
+int bsed_run_igemm(const BsedIgemmDesc* desc, void* stream, BsedContractPlan* plan);
+int bsed_run_igemm3(const BsedIgemmDesc* desc, void* stream, BsedContractPlan* plan);
+int bsed_run_igemm3s(const BsedIgemmDesc* desc, void* stream, BsedContractPlan* plan);
+int bsed_run_igemm3n(const BsedIgemmDesc* desc, void* stream, BsedContractPlan* plan);
+int bsed_run_wgrad(const BsedWgradDesc* desc, int mode3, void* stream, BsedContractPlan* plan);
+// What a template dispatch of the family is handed: a launch or, with `label` set, the request to NAME the instance
+// instead of launching it.  Every leaf launcher opens with BSED_LABEL_ONLY(L, "kernel<%d, ...>", its own template
+// arguments): the label is spelled from the constants the launch below it is instantiated with, as rocprofv3 prints them.
+struct BsedLaunch { dim3 grid; size_t smem; hipStream_t s; char* label; };
+#define BSED_LABEL_ONLY(L, ...) \
+  do { if ((L).label) { snprintf((L).label, sizeof(BsedContractPlan::label), __VA_ARGS__); return BSED_OK; } } while (0)
+static inline BsedLaunch bsed_plan_begin(BsedContractPlan* out, int G, int max_G, int stats_rows) {
+  out->G = G; out->max_G = max_G; out->stats_rows = stats_rows; out->label[0] = 0;
+  return BsedLaunch{dim3(), 0, nullptr, out->label};
+}
+// output channels per workgroup of bsed_igemm, bsed_igemm3 and bsed_igemm3n: the widest of 128 / 64 / 32 dividing NP
+static inline int bsed_contract_bn(int NP) { return NP % 128 == 0 ? 128 : (NP % 64 == 0 ? 64 : 32); }
+// what the prepare steps of bsed_igemm3, bsed_igemm3s and bsed_igemm3n begin with (returns the tile count) ...
+template <class Params>
+static int bsed_igemm3_front(const BsedIgemmDesc* desc, Params& P, const char* who, int cin_mult, int pitch_align) {
+  BSED_CHECK_ARG(desc, "%s: null descriptor", who);
+  P.d = *desc;
+  BSED_CHECK_ARG(P.d.epilogue == BSED_EPI_PLAIN || P.d.epilogue == BSED_EPI_STATS, "%s: PLAIN / STATS epilogues only", who);
+  const int ntiles = bsed_tile_geometry(P, who, cin_mult, pitch_align);
+  if (ntiles >= 0) BSED_CHECK_ARG(P.d.out_pitch >= P.d.N, "%s: bad pitch", who);
+  return ntiles;
+}
+// ... and the pointer checks their entry points add
+static inline int bsed_igemm3_pointers(const BsedIgemmDesc& d, const char* who) {
+  BSED_CHECK_ARG(d.in && d.w && d.out, "%s: null tensor", who);
+  BSED_CHECK_ARG(d.epilogue != BSED_EPI_STATS || d.stats, "%s: STATS needs a stats buffer", who);
+  return BSED_OK;
+}
+
+// ----------------------------------------------------------------------------------------------
 // Host side of the eight GLU / first-block entry points (BsedGluDesc, include/bsed.h).  No HIP call is made here.
 // ----------------------------------------------------------------------------------------------
 // What bsed_glu_plan answers, for the entry point `kernel` (BSED_GLU_*) and the shape fields of d: every shape check of

@@ -1506,13 +1506,14 @@ __global__ void pack_weight_kernel(const float* __restrict__ src, float* __restr
 // host side
 // ---------------------------------------------------------------------------------------------
 template <int KC, int BN>
-static int launch_igemm_epi(const IgemmParams& P, dim3 grid, size_t smem, hipStream_t s) {
+static int launch_igemm_epi(const IgemmParams& P, const BsedLaunch& L) {
   switch (P.d.epilogue) {
 #define CASE(E)                                                                                       \
   case E: {                                                                                           \
+    BSED_LABEL_ONLY(L, "igemm_kernel<%d, %d, %d>", KC, BN, E);                                        \
     static BsedLdsOnce once;                                                                         \
-    BSED_HIP(bsed_max_lds(once, (const void*)igemm_kernel<KC, BN, E>));                                                                                                 \
-    hipLaunchKernelGGL((igemm_kernel<KC, BN, E>), grid, dim3(IG_THREADS), smem, s, P);                \
+    BSED_HIP(bsed_max_lds(once, (const void*)igemm_kernel<KC, BN, E>));                              \
+    hipLaunchKernelGGL((igemm_kernel<KC, BN, E>), L.grid, dim3(IG_THREADS), L.smem, L.s, P);          \
     break;                                                                                            \
   }
     CASE(EPI_PLAIN)
@@ -1529,65 +1530,67 @@ static int launch_igemm_epi(const IgemmParams& P, dim3 grid, size_t smem, hipStr
   return BSED_OK;
 }
 
-extern "C" int bsed_igemm_num_tiles(const BsedIgemmDesc* d) {
-  if (!d || d->TH <= 0 || d->TW <= 0) return -1;
-  return d->NB * ceil_div(d->H, d->TH) * ceil_div(d->W, d->TW);
-}
-
-extern "C" int bsed_igemm(const BsedIgemmDesc* desc, void* stream) {
+// bsed_igemm (plan == null: pointer checks and the launch) and its plan (the label only) after ONE prepare step: every
+// shape check, the derived geometry, the LDS bytes and the grid
+int bsed_run_igemm(const BsedIgemmDesc* desc, void* stream, BsedContractPlan* plan) {
   BSED_CHECK_ARG(desc, "bsed_igemm: null descriptor");
   IgemmParams P;
   P.d = *desc;
-  P.seed_add = bsed_seed_add_ptr();
   BsedIgemmDesc& d = P.d;
-  BSED_CHECK_ARG(d.in && d.w && d.out, "bsed_igemm: null tensor");
   const int ntiles = bsed_tile_geometry(P, "bsed_igemm", 16, 4);
   if (ntiles < 0) return ntiles;
   BSED_CHECK_ARG(d.out_pitch >= d.N, "bsed_igemm: bad pitch");
-  const int KC = (d.CIN % 32 == 0) ? 32 : 16;
-  const int BN = d.NP % 128 == 0 ? 128 : (d.NP % 64 == 0 ? 64 : 32);
+  const int KC = (d.CIN % 32 == 0) ? 32 : 16, BN = bsed_contract_bn(d.NP);
   P.b_off = (P.PP * (KC + 1) + 3) & ~3;
   size_t fl = (size_t)P.b_off + (size_t)KC * BN;
+  const bool pooled = (d.ph == 1 || d.ph == 2) && (d.pw == 1 || d.pw == 2) && d.Hp == d.H / d.ph && d.Wp == d.W / d.pw;
   if (d.epilogue == EPI_GLU_POOL) {
     BSED_CHECK_ARG((d.ph == 1 || d.ph == 2) && (d.pw == 1 || d.pw == 2) && d.TH % d.ph == 0 && d.TW % d.pw == 0,
                    "bsed_igemm: pooling windows must be 1 or 2 and divide the tile");
-    BSED_CHECK_ARG(d.Hp == d.H / d.ph && d.Wp == d.W / d.pw, "bsed_igemm: bad pooled shape");
+    BSED_CHECK_ARG(pooled, "bsed_igemm: bad pooled shape");
     fl = std::max(fl, (size_t)IG_TILE_M * (BN + 1));
   }
   if (d.epilogue == EPI_GLU_POOL || d.epilogue == EPI_GLU_BWD)
-    BSED_CHECK_ARG(d.e_src && d.e_scale && d.e_shift && d.e_pitch >= d.N, "bsed_igemm: GLU epilogue needs e_src/e_scale/e_shift");
-  if (d.epilogue == EPI_GLU_BWD)
-    BSED_CHECK_ARG(d.e_dpool && d.out2 && d.stats && (d.ph == 1 || d.ph == 2) && (d.pw == 1 || d.pw == 2) &&
-                       d.Hp == d.H / d.ph && d.Wp == d.W / d.pw,
-                   "bsed_igemm: GLU_BWD epilogue needs e_dpool/out2/stats and pooled shape");
-  if (d.epilogue == EPI_ADD_STATS2)
-    BSED_CHECK_ARG(d.out2 && d.e_src && d.stats && d.e_pitch >= d.N, "bsed_igemm: ADD_STATS2 needs out2/e_src/stats");
-  if (d.epilogue == EPI_STATS) BSED_CHECK_ARG(d.stats, "bsed_igemm: STATS epilogue needs a stats buffer");
+    BSED_CHECK_ARG(d.e_pitch >= d.N, "bsed_igemm: GLU epilogue needs e_src/e_scale/e_shift");
+  if (d.epilogue == EPI_GLU_BWD) BSED_CHECK_ARG(pooled, "bsed_igemm: GLU_BWD epilogue needs e_dpool/out2/stats and pooled shape");
+  if (d.epilogue == EPI_ADD_STATS2) BSED_CHECK_ARG(d.e_pitch >= d.N, "bsed_igemm: ADD_STATS2 needs out2/e_src/stats");
   fl = std::max(fl, (size_t)8 * BN);
-  const size_t smem = fl * sizeof(float);
-  BSED_CHECK_ARG(smem <= 160 * 1024, "bsed_igemm: tile needs %zu B of LDS", smem);
-  dim3 grid((unsigned)ntiles, d.NP / BN);
-  hipStream_t s = (hipStream_t)stream;
-  if (KC == 32) {
-    if (BN == 128) return launch_igemm_epi<32, 128>(P, grid, smem, s);
-    if (BN == 64) return launch_igemm_epi<32, 64>(P, grid, smem, s);
-    return launch_igemm_epi<32, 32>(P, grid, smem, s);
+  BsedLaunch L{dim3((unsigned)ntiles, d.NP / BN), fl * sizeof(float), (hipStream_t)stream, nullptr};
+  BSED_CHECK_ARG(L.smem <= 160 * 1024, "bsed_igemm: tile needs %zu B of LDS", L.smem);
+  if (plan) L = bsed_plan_begin(plan, ntiles, ntiles, ntiles);   // one workgroup and one statistics row per tile
+  else {
+    P.seed_add = bsed_seed_add_ptr();
+    BSED_CHECK_ARG(d.in && d.w && d.out, "bsed_igemm: null tensor");
+    if (d.epilogue == EPI_GLU_POOL || d.epilogue == EPI_GLU_BWD)
+      BSED_CHECK_ARG(d.e_src && d.e_scale && d.e_shift, "bsed_igemm: GLU epilogue needs e_src/e_scale/e_shift");
+    if (d.epilogue == EPI_GLU_BWD)
+      BSED_CHECK_ARG(d.e_dpool && d.out2 && d.stats, "bsed_igemm: GLU_BWD epilogue needs e_dpool/out2/stats and pooled shape");
+    if (d.epilogue == EPI_ADD_STATS2) BSED_CHECK_ARG(d.out2 && d.e_src && d.stats, "bsed_igemm: ADD_STATS2 needs out2/e_src/stats");
+    if (d.epilogue == EPI_STATS) BSED_CHECK_ARG(d.stats, "bsed_igemm: STATS epilogue needs a stats buffer");
   }
-  if (BN == 128) return launch_igemm_epi<16, 128>(P, grid, smem, s);
-  if (BN == 64) return launch_igemm_epi<16, 64>(P, grid, smem, s);
-  return launch_igemm_epi<16, 32>(P, grid, smem, s);
+  if (KC == 32) {
+    if (BN == 128) return launch_igemm_epi<32, 128>(P, L);
+    if (BN == 64) return launch_igemm_epi<32, 64>(P, L);
+    return launch_igemm_epi<32, 32>(P, L);
+  }
+  if (BN == 128) return launch_igemm_epi<16, 128>(P, L);
+  if (BN == 64) return launch_igemm_epi<16, 64>(P, L);
+  return launch_igemm_epi<16, 32>(P, L);
 }
+extern "C" int bsed_igemm(const BsedIgemmDesc* desc, void* stream) { return bsed_run_igemm(desc, stream, nullptr); }
 
 template <int MAXS, int NW>
-static int launch_wgrad(const WgradParams& P, dim3 grid, size_t smem, hipStream_t s) {
+static int launch_wgrad(const WgradParams& P, const BsedLaunch& L) {
+  BSED_LABEL_ONLY(L, "wgrad_kernel<%d, %d>", MAXS, NW);
   static BsedLdsOnce once;
   BSED_HIP(bsed_max_lds(once, (const void*)wgrad_kernel<MAXS, NW>));
-  hipLaunchKernelGGL((wgrad_kernel<MAXS, NW>), grid, dim3(NW * 64), smem, s, P);
+  hipLaunchKernelGGL((wgrad_kernel<MAXS, NW>), L.grid, dim3(NW * 64), L.smem, L.s, P);
   BSED_LAUNCH_CHECK();
   return BSED_OK;
 }
 
-// shape checks + derived launch geometry shared by bsed_wgrad and bsed_wgrad_auto_g
+// Host-side prepare step of bsed_wgrad and bsed_wgrad3 (mode3), shared with their plan: every shape check, the derived
+// geometry, the LDS bytes and grid.y / grid.z.  The entry points add the pointer and G checks and the launch.
 static int wgrad_prepare(const BsedWgradDesc* desc, WgradParams& P, size_t& smem, dim3& grid_yz, int mode3 = 0) {
   BSED_CHECK_ARG(desc, "bsed_wgrad: null descriptor");
   P.d = *desc;
@@ -1638,19 +1641,14 @@ static int wgrad_prepare(const BsedWgradDesc* desc, WgradParams& P, size_t& smem
 }
 
 // number of partial slabs G such that G x (n tiles) x (channel chunks) is about three workgroups per CU
-extern "C" int bsed_wgrad_auto_g(const BsedWgradDesc* desc) {
-  WgradParams P;
-  size_t smem;
-  dim3 gyz;
-  if (wgrad_prepare(desc, P, smem, gyz) != BSED_OK) return -1;
+static int wgrad_auto_g(const WgradParams& P, size_t smem, dim3 gyz) {
   // exactly one resident round of workgroups (2 per CU when two tiles fit in LDS): no partial tail round
   const long slots = smem <= 80 * 1024 ? 512 : 256;
   const long want = std::max<long>(1, slots / ((long)gyz.y * gyz.z));
   return (int)std::max<long>(1, std::min<long>(want, P.ntiles));
 }
 
-// The ONE choice of wgrad_kernel<MAXS, NW> for a shape, as MAXS * 16 + NW: bsed_wgrad launches it, bsed_wgrad_variant
-// reports it (profiling / bench labels)
+// The ONE choice of wgrad_kernel<MAXS, NW> for a shape, as MAXS * 16 + NW
 static int wgrad_variant(const WgradParams& P) {
   const BsedWgradDesc& d = P.d;
   const int nitems = (P.pack2 ? (d.ntaps + 1) / 2 : d.ntaps) * P.nct * P.ntw;
@@ -1665,28 +1663,10 @@ static int wgrad_variant(const WgradParams& P) {
   return m * 16 + 4;
 }
 
-extern "C" int bsed_wgrad_variant(const BsedWgradDesc* desc) {
-  WgradParams P;
-  size_t smem;
-  dim3 gyz;
-  if (wgrad_prepare(desc, P, smem, gyz) != BSED_OK) return -1;
-  return wgrad_variant(P);
-}
-
-extern "C" int bsed_wgrad(const BsedWgradDesc* desc, void* stream) {
-  WgradParams P;
-  size_t smem;
-  dim3 gyz;
-  int rc = wgrad_prepare(desc, P, smem, gyz);
-  if (rc != BSED_OK) return rc;
-  BsedWgradDesc& d = P.d;
-  BSED_CHECK_ARG(d.in && d.dy && d.part, "bsed_wgrad: null tensor");
-  BSED_CHECK_ARG(d.G > 0 && d.G <= P.ntiles, "bsed_wgrad: G (%d) must be in 1..%d tiles", d.G, P.ntiles);
-  dim3 grid((unsigned)d.G, gyz.y, gyz.z);
-  hipStream_t s = (hipStream_t)stream;
+static int wgrad_dispatch(const WgradParams& P, const BsedLaunch& L) {
   switch (wgrad_variant(P)) {
 #define CASE(MAXS, NW) \
-  case MAXS * 16 + NW: return launch_wgrad<MAXS, NW>(P, grid, smem, s);
+  case MAXS * 16 + NW: return launch_wgrad<MAXS, NW>(P, L);
     CASE(2, 8) CASE(3, 8) CASE(5, 8)
     CASE(1, 4) CASE(2, 4) CASE(3, 4) CASE(5, 4) CASE(9, 4)
 #undef CASE
@@ -1696,28 +1676,30 @@ extern "C" int bsed_wgrad(const BsedWgradDesc* desc, void* stream) {
 }
 
 template <int MAXS, int NW, bool BS>
-static int launch_wgrad3(const WgradParams& P, dim3 grid, size_t smem, hipStream_t s) {
+static int launch_wgrad3(const WgradParams& P, const BsedLaunch& L) {
+  BSED_LABEL_ONLY(L, "wgrad3_kernel<%d, %d, %s, %d>", MAXS, NW, BS ? "true" : "false", P.d.act_bf16 ? 1 : 0);
   static BsedLdsOnce once, onceb;
   if (P.d.act_bf16) {
     BSED_HIP(bsed_max_lds(onceb, (const void*)wgrad3_kernel<MAXS, NW, BS, 1>));
-    hipLaunchKernelGGL((wgrad3_kernel<MAXS, NW, BS, 1>), grid, dim3(NW * 64), smem, s, P);
+    hipLaunchKernelGGL((wgrad3_kernel<MAXS, NW, BS, 1>), L.grid, dim3(NW * 64), L.smem, L.s, P);
   } else {
     BSED_HIP(bsed_max_lds(once, (const void*)wgrad3_kernel<MAXS, NW, BS, 0>));
-    hipLaunchKernelGGL((wgrad3_kernel<MAXS, NW, BS, 0>), grid, dim3(NW * 64), smem, s, P);
+    hipLaunchKernelGGL((wgrad3_kernel<MAXS, NW, BS, 0>), L.grid, dim3(NW * 64), L.smem, L.s, P);
   }
   BSED_LAUNCH_CHECK();
   return BSED_OK;
 }
 
 template <int MAXS, int GEO>
-static int launch_wgrad3p_geo(const WgradParams& P, dim3 grid, size_t smem, hipStream_t s) {
+static int launch_wgrad3p_geo(const WgradParams& P, const BsedLaunch& L) {
+  BSED_LABEL_ONLY(L, "wgrad3p_kernel<%d, %d, %d>", MAXS, GEO, P.d.act_bf16 ? 1 : 0);
   static BsedLdsOnce once, onceb;
   if (P.d.act_bf16) {
     BSED_HIP(bsed_max_lds(onceb, (const void*)wgrad3p_kernel<MAXS, GEO, 1>));
-    hipLaunchKernelGGL((wgrad3p_kernel<MAXS, GEO, 1>), grid, dim3(512), 2 * smem, s, P);
+    hipLaunchKernelGGL((wgrad3p_kernel<MAXS, GEO, 1>), L.grid, dim3(512), 2 * L.smem, L.s, P);
   } else {
     BSED_HIP(bsed_max_lds(once, (const void*)wgrad3p_kernel<MAXS, GEO, 0>));
-    hipLaunchKernelGGL((wgrad3p_kernel<MAXS, GEO, 0>), grid, dim3(512), 2 * smem, s, P);
+    hipLaunchKernelGGL((wgrad3p_kernel<MAXS, GEO, 0>), L.grid, dim3(512), 2 * L.smem, L.s, P);
   }
   BSED_LAUNCH_CHECK();
   return BSED_OK;
@@ -1756,8 +1738,8 @@ static bool wgrad1_streaming(const WgradParams& P) {
          (long)d.NB * d.H * d.W < (1L << 31) - 4 * 65536;
 }
 
-// The ONE choice of the split-fp32 weight-gradient kernel for a shape: bsed_wgrad3 launches it, bsed_wgrad3_variant
-// reports it and bsed_wgrad3_auto_g sizes its grid.
+// The ONE choice of the split-fp32 weight-gradient kernel for a shape: bsed_wgrad3 launches it, its plan names it and
+// wgrad3_auto_g sizes its grid.
 enum W3Kind { W3_TILE, W3_PIPE, W3_STREAM1 };
 struct W3Plan {
   W3Kind kind;
@@ -1775,42 +1757,39 @@ static W3Plan wgrad3_plan(const WgradParams& P, size_t smem) {
 }
 
 template <int GEO = W3_NGEO>
-static int launch_wgrad3p(const W3Plan& pl, const WgradParams& P, dim3 grid, size_t smem, hipStream_t s) {
+static int launch_wgrad3p(const W3Plan& pl, const WgradParams& P, const BsedLaunch& L) {
   if constexpr (GEO > 0) {
-    if (pl.geo == GEO) return launch_wgrad3p_geo<w3p_geo_maxs(GEO), GEO>(P, grid, smem, s);
-    return launch_wgrad3p<GEO - 1>(pl, P, grid, smem, s);
+    if (pl.geo == GEO) return launch_wgrad3p_geo<w3p_geo_maxs(GEO), GEO>(P, L);
+    return launch_wgrad3p<GEO - 1>(pl, P, L);
   } else {
-    if (pl.maxs == 3) return launch_wgrad3p_geo<3, 0>(P, grid, smem, s);
-    if (pl.maxs == 5) return launch_wgrad3p_geo<5, 0>(P, grid, smem, s);
-    return launch_wgrad3p_geo<9, 0>(P, grid, smem, s);
+    if (pl.maxs == 3) return launch_wgrad3p_geo<3, 0>(P, L);
+    if (pl.maxs == 5) return launch_wgrad3p_geo<5, 0>(P, L);
+    return launch_wgrad3p_geo<9, 0>(P, L);
   }
 }
 
 template <bool SHIFT>
-static int launch_wgrad1(const WgradParams& P, dim3 grid, hipStream_t s) {
+static int launch_wgrad1(const WgradParams& P, const BsedLaunch& L) {
+  BSED_LABEL_ONLY(L, "wgrad1_kernel<%s, %d>", SHIFT ? "true" : "false", P.d.act_bf16 ? 1 : 0);
   static BsedLdsOnce once, onceb;
   if (P.d.act_bf16) {
     BSED_HIP(bsed_max_lds(onceb, (const void*)wgrad1_kernel<SHIFT, 1>));
-    hipLaunchKernelGGL((wgrad1_kernel<SHIFT, 1>), grid, dim3(W1_THREADS), 2 * W1_STAGE, s, P);
+    hipLaunchKernelGGL((wgrad1_kernel<SHIFT, 1>), L.grid, dim3(W1_THREADS), 2 * W1_STAGE, L.s, P);
   } else {
     BSED_HIP(bsed_max_lds(once, (const void*)wgrad1_kernel<SHIFT, 0>));
-    hipLaunchKernelGGL((wgrad1_kernel<SHIFT, 0>), grid, dim3(W1_THREADS), 2 * W1_STAGE, s, P);
+    hipLaunchKernelGGL((wgrad1_kernel<SHIFT, 0>), L.grid, dim3(W1_THREADS), 2 * W1_STAGE, L.s, P);
   }
   BSED_LAUNCH_CHECK();
   return BSED_OK;
 }
 
 template <int MAXS, int NW>
-static int launch_wgrad3_tile(const W3Plan& pl, const WgradParams& P, dim3 grid, size_t smem, hipStream_t s) {
-  return pl.bs ? launch_wgrad3<MAXS, NW, true>(P, grid, smem, s) : launch_wgrad3<MAXS, NW, false>(P, grid, smem, s);
+static int launch_wgrad3_tile(const W3Plan& pl, const WgradParams& P, const BsedLaunch& L) {
+  return pl.bs ? launch_wgrad3<MAXS, NW, true>(P, L) : launch_wgrad3<MAXS, NW, false>(P, L);
 }
 
-extern "C" int bsed_wgrad3_auto_g(const BsedWgradDesc* desc) {
-  WgradParams P;
-  size_t smem;
-  dim3 gyz;
-  if (wgrad_prepare(desc, P, smem, gyz, 1) != BSED_OK) return -1;
-  const W3Plan pl = wgrad3_plan(P, smem);
+// the recommended number of partial slabs G of bsed_wgrad3 (it differs between the three kernels)
+static int wgrad3_auto_g(const WgradParams& P, const W3Plan& pl, size_t smem, dim3 gyz) {
   long slots = pl.kind == W3_PIPE ? 256 : smem <= 80 * 1024 ? 512 : 256;
   // small tiles (conv1 16 -> 32 channel gradient: 39 KB, 136 registers): a third workgroup per CU fits and hides more of
   // the stage / barrier / MFMA serialisation: 0.956 -> 0.753 ms; a fourth (the kernel pinned to 128 registers) 0.651 ms
@@ -1823,43 +1802,42 @@ extern "C" int bsed_wgrad3_auto_g(const BsedWgradDesc* desc) {
   return (int)std::max<long>(1, std::min<long>(want, P.ntiles));
 }
 
-// bench / profile labels: wgrad1_kernel<SHIFT> = 1 << 13 | SHIFT; otherwise MAXS * 16 + NW with NW = 1 for
-// wgrad3p_kernel<MAXS, GEO> (GEO in bits 8..11) and bit 12 = the BS template argument of wgrad3_kernel
-extern "C" int bsed_wgrad3_variant(const BsedWgradDesc* desc) {
-  WgradParams P;
-  size_t smem;
-  dim3 gyz;
-  if (wgrad_prepare(desc, P, smem, gyz, 1) != BSED_OK) return -1;
-  const W3Plan pl = wgrad3_plan(P, smem);
-  if (pl.kind == W3_STREAM1) return (1 << 13) | (pl.shifted ? 1 : 0);
-  return pl.maxs * 16 + pl.nw + (pl.geo << 8) + (pl.bs ? 1 << 12 : 0);
+static int wgrad3_dispatch(const WgradParams& P, const W3Plan& pl, const BsedLaunch& L) {
+  if (pl.kind == W3_STREAM1) return pl.shifted ? launch_wgrad1<true>(P, L) : launch_wgrad1<false>(P, L);
+  if (pl.kind == W3_PIPE) return launch_wgrad3p(pl, P, L);
+  if (pl.nw == 8) {
+    if (pl.maxs == 2) return launch_wgrad3_tile<2, 8>(pl, P, L);
+    if (pl.maxs == 3) return launch_wgrad3_tile<3, 8>(pl, P, L);
+    return launch_wgrad3_tile<5, 8>(pl, P, L);
+  }
+  if (pl.maxs == 1) return launch_wgrad3_tile<1, 4>(pl, P, L);
+  if (pl.maxs == 2) return launch_wgrad3_tile<2, 4>(pl, P, L);
+  if (pl.maxs == 3) return launch_wgrad3_tile<3, 4>(pl, P, L);
+  if (pl.maxs == 5) return launch_wgrad3_tile<5, 4>(pl, P, L);
+  return launch_wgrad3_tile<9, 4>(pl, P, L);
 }
 
-extern "C" int bsed_wgrad3(const BsedWgradDesc* desc, void* stream) {
+// both weight-gradient entry points (pointer and G checks, launch) and their plan (recommended G, label only)
+int bsed_run_wgrad(const BsedWgradDesc* desc, int mode3, void* stream, BsedContractPlan* plan) {
   WgradParams P;
   size_t smem;
   dim3 gyz;
-  int rc = wgrad_prepare(desc, P, smem, gyz, 1);
+  const int rc = wgrad_prepare(desc, P, smem, gyz, mode3);
   if (rc != BSED_OK) return rc;
-  BsedWgradDesc& d = P.d;
-  BSED_CHECK_ARG(d.in && d.dy && d.part, "bsed_wgrad3: null tensor");
-  BSED_CHECK_ARG(d.G > 0 && d.G <= P.ntiles, "bsed_wgrad3: G (%d) must be in 1..%d tiles", d.G, P.ntiles);
-  dim3 grid((unsigned)d.G, gyz.y, gyz.z);
-  hipStream_t s = (hipStream_t)stream;
-  const W3Plan pl = wgrad3_plan(P, smem);
-  if (pl.kind == W3_STREAM1) return pl.shifted ? launch_wgrad1<true>(P, grid, s) : launch_wgrad1<false>(P, grid, s);
-  if (pl.kind == W3_PIPE) return launch_wgrad3p(pl, P, grid, smem, s);
-  if (pl.nw == 8) {
-    if (pl.maxs == 2) return launch_wgrad3_tile<2, 8>(pl, P, grid, smem, s);
-    if (pl.maxs == 3) return launch_wgrad3_tile<3, 8>(pl, P, grid, smem, s);
-    return launch_wgrad3_tile<5, 8>(pl, P, grid, smem, s);
+  const BsedWgradDesc& d = P.d;
+  const W3Plan pl = mode3 ? wgrad3_plan(P, smem) : W3Plan{};
+  BsedLaunch L;
+  if (plan) L = bsed_plan_begin(plan, mode3 ? wgrad3_auto_g(P, pl, smem, gyz) : wgrad_auto_g(P, smem, gyz), P.ntiles, 0);
+  else {
+    const char* who = mode3 ? "bsed_wgrad3" : "bsed_wgrad";
+    BSED_CHECK_ARG(d.in && d.dy && d.part, "%s: null tensor", who);
+    BSED_CHECK_ARG(d.G > 0 && d.G <= P.ntiles, "%s: G (%d) must be in 1..%d tiles", who, d.G, P.ntiles);
+    L = BsedLaunch{dim3((unsigned)d.G, gyz.y, gyz.z), smem, (hipStream_t)stream, nullptr};
   }
-  if (pl.maxs == 1) return launch_wgrad3_tile<1, 4>(pl, P, grid, smem, s);
-  if (pl.maxs == 2) return launch_wgrad3_tile<2, 4>(pl, P, grid, smem, s);
-  if (pl.maxs == 3) return launch_wgrad3_tile<3, 4>(pl, P, grid, smem, s);
-  if (pl.maxs == 5) return launch_wgrad3_tile<5, 4>(pl, P, grid, smem, s);
-  return launch_wgrad3_tile<9, 4>(pl, P, grid, smem, s);
+  return mode3 ? wgrad3_dispatch(P, pl, L) : wgrad_dispatch(P, L);
 }
+extern "C" int bsed_wgrad(const BsedWgradDesc* desc, void* stream) { return bsed_run_wgrad(desc, 0, stream, nullptr); }
+extern "C" int bsed_wgrad3(const BsedWgradDesc* desc, void* stream) { return bsed_run_wgrad(desc, 1, stream, nullptr); }
 
 extern "C" int bsed_reduce_partials(const float* part, int G, int ntaps, int KP, int NP, int K, int N, float* dst,
                                     long s_tap, long s_k, long s_n, int accumulate, void* stream) {

@@ -627,10 +627,11 @@ __global__ __launch_bounds__(I3_THREADS) void igemm3s_kernel(const Igemm3Params 
 }
 
 template <int BN, int STATS, int RB, int PV>
-static int launch_i3pv(const Igemm3Params& P, dim3 grid, size_t smem, hipStream_t s) {
+static int launch_i3pv(const Igemm3Params& P, const BsedLaunch& L) {
+  BSED_LABEL_ONLY(L, "igemm3_kernel<%d, %d, %d, %d>", BN, STATS, RB, PV);
   static BsedLdsOnce once;
   BSED_HIP(bsed_max_lds(once, (const void*)igemm3_kernel<BN, STATS, RB, PV>));
-  hipLaunchKernelGGL((igemm3_kernel<BN, STATS, RB, PV>), grid, dim3(I3_THREADS), smem, s, P);
+  hipLaunchKernelGGL((igemm3_kernel<BN, STATS, RB, PV>), L.grid, dim3(I3_THREADS), L.smem, L.s, P);
   BSED_LAUNCH_CHECK();
   return BSED_OK;
 }
@@ -638,38 +639,36 @@ static int launch_i3pv(const Igemm3Params& P, dim3 grid, size_t smem, hipStream_
 // PV = float4 patch elements per thread: ceil(PP * 8 / 256), instantiated for 6 (up to 192 patch positions: the 18x10
 // patch of a 16x8 tile), 9 (288: tall narrow tiles) and 12 (384)
 template <int BN, int STATS>
-static int launch_i3(const Igemm3Params& P, dim3 grid, size_t smem, hipStream_t s) {
+static int launch_i3(const Igemm3Params& P, const BsedLaunch& L) {
   const int need = ceil_div(P.PP * 8, I3_THREADS);
-  if (need <= 6) return launch_i3pv<BN, STATS, 1, 6>(P, grid, smem, s);
-  if (need <= 9) return launch_i3pv<BN, STATS, 1, 9>(P, grid, smem, s);
-  if (need <= 12) return launch_i3pv<BN, STATS, 1, 12>(P, grid, smem, s);
+  if (need <= 6) return launch_i3pv<BN, STATS, 1, 6>(P, L);
+  if (need <= 9) return launch_i3pv<BN, STATS, 1, 9>(P, L);
+  if (need <= 12) return launch_i3pv<BN, STATS, 1, 12>(P, L);
   bsed_set_error("bsed_igemm3: patch of %d positions exceeds the 384 supported", P.PP);
   return BSED_ERR_ARG;
 }
 
-extern "C" int bsed_igemm3(const BsedIgemmDesc* desc, void* stream) {
-  BSED_CHECK_ARG(desc, "bsed_igemm3: null descriptor");
+// bsed_igemm3 (plan == null: pointer checks and the launch) and its plan (the label only) after ONE prepare step: every
+// shape check, the derived geometry, the LDS bytes and the grid
+int bsed_run_igemm3(const BsedIgemmDesc* desc, void* stream, BsedContractPlan* plan) {
   Igemm3Params P;
-  P.d = *desc;
-  BsedIgemmDesc& d = P.d;
-  BSED_CHECK_ARG(d.in && d.w && d.out, "bsed_igemm3: null tensor");
-  BSED_CHECK_ARG(d.epilogue == BSED_EPI_PLAIN || d.epilogue == BSED_EPI_STATS, "bsed_igemm3: PLAIN / STATS epilogues only");
-  BSED_CHECK_ARG(d.epilogue != BSED_EPI_STATS || d.stats, "bsed_igemm3: STATS needs a stats buffer");
-  const int ntiles = bsed_tile_geometry(P, "bsed_igemm3", 32, 4);
+  const int ntiles = bsed_igemm3_front(desc, P, "bsed_igemm3", 32, 4);
   if (ntiles < 0) return ntiles;
-  BSED_CHECK_ARG(d.out_pitch >= d.N, "bsed_igemm3: bad pitch");
-  const int BN = d.NP % 128 == 0 ? 128 : (d.NP % 64 == 0 ? 64 : 32);
+  const BsedIgemmDesc& d = P.d;
+  const int BN = bsed_contract_bn(d.NP);
   P.b_off = (P.PP * I3_ROW + 7) & ~7;
   size_t bytes = ((size_t)P.b_off + (size_t)BN * I3_ROW) * sizeof(unsigned short);
   bytes = std::max(bytes, (size_t)8 * BN * sizeof(float));
   BSED_CHECK_ARG(bytes <= 160 * 1024, "bsed_igemm3: tile needs %zu B of LDS", bytes);
-  dim3 grid((unsigned)ntiles, d.NP / BN);
-  hipStream_t s = (hipStream_t)stream;
+  BsedLaunch L{dim3((unsigned)ntiles, d.NP / BN), bytes, (hipStream_t)stream, nullptr};
+  if (plan) L = bsed_plan_begin(plan, ntiles, ntiles, ntiles);   // one workgroup and one statistics row per tile
+  else if (const int rc = bsed_igemm3_pointers(d, "bsed_igemm3")) return rc;
   const bool st = d.epilogue == BSED_EPI_STATS;
-  if (BN == 128) return st ? launch_i3<128, 1>(P, grid, bytes, s) : launch_i3<128, 0>(P, grid, bytes, s);
-  if (BN == 64) return st ? launch_i3<64, 1>(P, grid, bytes, s) : launch_i3<64, 0>(P, grid, bytes, s);
-  return st ? launch_i3<32, 1>(P, grid, bytes, s) : launch_i3<32, 0>(P, grid, bytes, s);
+  if (BN == 128) return st ? launch_i3<128, 1>(P, L) : launch_i3<128, 0>(P, L);
+  if (BN == 64) return st ? launch_i3<64, 1>(P, L) : launch_i3<64, 0>(P, L);
+  return st ? launch_i3<32, 1>(P, L) : launch_i3<32, 0>(P, L);
 }
+extern "C" int bsed_igemm3(const BsedIgemmDesc* desc, void* stream) { return bsed_run_igemm3(desc, stream, nullptr); }
 
 // ---- CIN = 16 variant: w = bsed_pack_weight3s table; persistent grid of G workgroups per 32 output channels;
 // stats (STATS epilogue) has G rows (one per workgroup), not one per tile
@@ -684,45 +683,45 @@ extern "C" int bsed_pack_weight3s(const float* src, void* dst, int ntaps, int K,
   return BSED_OK;
 }
 
-extern "C" int bsed_igemm3s_auto_g(void) { return 1024; }
-// per shape: the 32 -> 16 channel data gradient (half-width weight table, 52 KB of LDS) runs three workgroups per CU:
-// 768 / 1024 / 1536 workgroups 0.380 / 0.452 / 0.384 ms; the 16 -> 32 forward four: 0.406 / 0.365 / 0.409
-extern "C" int bsed_igemm3s_auto_g2(int CIN, int N) { return (CIN == 32 && N <= 16) ? 768 : 1024; }
-
-extern "C" int bsed_igemm3s(const BsedIgemmDesc* desc, int G, void* stream) {
-  BSED_CHECK_ARG(desc, "bsed_igemm3s: null descriptor");
+// bsed_igemm3s (plan == null: pointer and G checks and the launch) and its plan (G and the label only) after ONE prepare
+// step: every shape check, the derived geometry, the LDS bytes, grid.y and the epilogue choice (nv16)
+int bsed_run_igemm3s(const BsedIgemmDesc* desc, void* stream, BsedContractPlan* plan) {
   Igemm3Params P;
-  P.d = *desc;
-  BsedIgemmDesc& d = P.d;
-  BSED_CHECK_ARG(d.in && d.w && d.out, "bsed_igemm3s: null tensor");
-  BSED_CHECK_ARG(d.epilogue == BSED_EPI_PLAIN || d.epilogue == BSED_EPI_STATS, "bsed_igemm3s: PLAIN / STATS epilogues only");
-  BSED_CHECK_ARG(d.epilogue != BSED_EPI_STATS || d.stats, "bsed_igemm3s: STATS needs a stats buffer");
+  const int ntiles = bsed_igemm3_front(desc, P, "bsed_igemm3s", 16, desc && desc->act_bf16 ? 8 : 4);
+  if (ntiles < 0) return ntiles;
+  const BsedIgemmDesc& d = P.d;
   BSED_CHECK_ARG(d.CIN == 16 || d.CIN == 32, "bsed_igemm3s: built for CIN = 16 or 32");
   BSED_CHECK_ARG(d.ntaps == 9 || d.ntaps == 1, "bsed_igemm3s: 9 or 1 taps");
-  const int ntiles = bsed_tile_geometry(P, "bsed_igemm3s", 16, d.act_bf16 ? 8 : 4);
-  if (ntiles < 0) return ntiles;
-  BSED_CHECK_ARG(d.out_pitch >= d.N, "bsed_igemm3s: bad pitch");
   const int KS = d.CIN / 16;
   BSED_CHECK_ARG(P.PP <= (KS == 1 ? 256 : 192), "bsed_igemm3s: patch of %d positions exceeds the %d supported", P.PP,
                  KS == 1 ? 256 : 192);
   P.b_off = 0;
-  BSED_CHECK_ARG(G > 0 && G <= ntiles, "bsed_igemm3s: G must be in 1..%d tiles", ntiles);
   // N <= 16: transposed epilogue (wave-private LDS image, float4 row stores)
   const bool nv16 = d.N <= 16 && d.N % 4 == 0 && d.out_pitch % 4 == 0;
   const size_t bytes = (size_t)d.ntaps * KS * 2 * (nv16 ? 32 : 64) * 16 + (size_t)P.PP * ((d.act_bf16 ? 1 : 2) * d.CIN + 8) * 2 +
                        (nv16 ? (size_t)4 * 32 * I3S_EROW * sizeof(float) : 0);
-  dim3 grid((unsigned)G, d.NP / 32);
-  hipStream_t s = (hipStream_t)stream;
+  BsedLaunch L{dim3((unsigned)d.G, d.NP / 32), bytes, (hipStream_t)stream, nullptr};
+  if (plan) {
+    // persistent grid, one resident round: the 32 -> 16 channel data gradient (half-width weight table, 52 KB of LDS) runs
+    // three workgroups per CU: 768 / 1024 / 1536 workgroups 0.380 / 0.452 / 0.384 ms; the 16 -> 32 forward four: 0.406 /
+    // 0.365 / 0.409.  STATS writes one row per workgroup.
+    const int G = std::min(ntiles, (d.CIN == 32 && d.N <= 16) ? 768 : 1024);
+    L = bsed_plan_begin(plan, G, ntiles, G);
+  } else {
+    if (const int rc = bsed_igemm3_pointers(d, "bsed_igemm3s")) return rc;
+    BSED_CHECK_ARG(d.G > 0 && d.G <= ntiles, "bsed_igemm3s: G must be in 1..%d tiles", ntiles);
+  }
   const bool st = d.epilogue == BSED_EPI_STATS;
 #define I3S_LAUNCH1(S, T, K, V)                                                                                       \
   do {                                                                                                                \
+    BSED_LABEL_ONLY(L, "igemm3s_kernel<%d, %d, %d, %d, %d>", S, T, K, V, d.act_bf16 ? 1 : 0);                         \
     static BsedLdsOnce once, onceb;                                                                                   \
     if (d.act_bf16) {                                                                                                 \
       BSED_HIP(bsed_max_lds(onceb, (const void*)igemm3s_kernel<S, T, K, V, 1>));                                     \
-      hipLaunchKernelGGL((igemm3s_kernel<S, T, K, V, 1>), grid, dim3(I3_THREADS), bytes, s, P);                       \
+      hipLaunchKernelGGL((igemm3s_kernel<S, T, K, V, 1>), L.grid, dim3(I3_THREADS), L.smem, L.s, P);                  \
     } else {                                                                                                          \
       BSED_HIP(bsed_max_lds(once, (const void*)igemm3s_kernel<S, T, K, V, 0>));                                      \
-      hipLaunchKernelGGL((igemm3s_kernel<S, T, K, V, 0>), grid, dim3(I3_THREADS), bytes, s, P);                       \
+      hipLaunchKernelGGL((igemm3s_kernel<S, T, K, V, 0>), L.grid, dim3(I3_THREADS), L.smem, L.s, P);                  \
     }                                                                                                                 \
   } while (0)
 #define I3S_LAUNCH(T, K)                                                                                              \
@@ -741,6 +740,7 @@ extern "C" int bsed_igemm3s(const BsedIgemmDesc* desc, int G, void* stream) {
   BSED_LAUNCH_CHECK();
   return BSED_OK;
 }
+extern "C" int bsed_igemm3s(const BsedIgemmDesc* desc, void* stream) { return bsed_run_igemm3s(desc, stream, nullptr); }
 
 extern "C" int bsed_pack_weights_batch(const BsedPackJob* jobs, int njobs, void* stream) {
   BSED_CHECK_ARG(jobs && njobs > 0 && njobs <= BSED_PACK_MAX_JOBS, "bsed_pack_weights_batch: 1..%d jobs", BSED_PACK_MAX_JOBS);

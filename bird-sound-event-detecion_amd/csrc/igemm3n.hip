@@ -387,19 +387,21 @@ static int i3n_shape16(int abf) {
   return v ? v == 16 : !abf;
 }
 template <int NWN, int MW, int STATS, int PV, int NT9, int WPE, int ABF = 0>
-static int launch_i3n6(const Igemm3nParams& P, dim3 grid, size_t smem, hipStream_t s) {
+static int launch_i3n6(const Igemm3nParams& P, const BsedLaunch& L) {
   if constexpr (NT9 == 1 || (NWN == 4 && WPE == 2)) {   // (... and the two-wave BN = 128 builds of the 1 - 4 tap forms: GRU projections)
     if (i3n_shape16(ABF)) {
+      BSED_LABEL_ONLY(L, "igemm3n_kernel<%d, %d, %d, %d, %d, %d, %d, %d>", NWN, MW, STATS, PV, NT9, WPE, ABF, 1);
       static BsedLdsOnce once16;
       BSED_HIP(bsed_max_lds(once16, (const void*)igemm3n_kernel<NWN, MW, STATS, PV, NT9, WPE, ABF, 1>));
-      hipLaunchKernelGGL((igemm3n_kernel<NWN, MW, STATS, PV, NT9, WPE, ABF, 1>), grid, dim3(64 * NWN * MW), smem, s, P);
+      hipLaunchKernelGGL((igemm3n_kernel<NWN, MW, STATS, PV, NT9, WPE, ABF, 1>), L.grid, dim3(64 * NWN * MW), L.smem, L.s, P);
       BSED_LAUNCH_CHECK();
       return BSED_OK;
     }
   }
+  BSED_LABEL_ONLY(L, "igemm3n_kernel<%d, %d, %d, %d, %d, %d, %d, %d>", NWN, MW, STATS, PV, NT9, WPE, ABF, 0);
   static BsedLdsOnce once;
   BSED_HIP(bsed_max_lds(once, (const void*)igemm3n_kernel<NWN, MW, STATS, PV, NT9, WPE, ABF>));
-  hipLaunchKernelGGL((igemm3n_kernel<NWN, MW, STATS, PV, NT9, WPE, ABF>), grid, dim3(64 * NWN * MW), smem, s, P);
+  hipLaunchKernelGGL((igemm3n_kernel<NWN, MW, STATS, PV, NT9, WPE, ABF>), L.grid, dim3(64 * NWN * MW), L.smem, L.s, P);
   BSED_LAUNCH_CHECK();
   return BSED_OK;
 }
@@ -433,67 +435,50 @@ static I3nPlan i3n_plan(int NP, int PP, int ntaps, int abf) {
 }
 
 template <int NWN, int STATS, int PV, int WPE, int ABF = 0>
-static int launch_i3n4(const Igemm3nParams& P, dim3 grid, size_t smem, hipStream_t s) {
-  return P.d.ntaps == 9 ? launch_i3n6<NWN, 4 / NWN, STATS, PV, 1, WPE, ABF>(P, grid, smem, s)
-                        : launch_i3n6<NWN, 4 / NWN, STATS, PV, 0, WPE, ABF>(P, grid, smem, s);
+static int launch_i3n4(const Igemm3nParams& P, const BsedLaunch& L) {
+  return P.d.ntaps == 9 ? launch_i3n6<NWN, 4 / NWN, STATS, PV, 1, WPE, ABF>(P, L)
+                        : launch_i3n6<NWN, 4 / NWN, STATS, PV, 0, WPE, ABF>(P, L);
 }
 
 template <int NWN, int STATS>
-static int launch_i3n(const Igemm3nParams& P, dim3 grid, size_t smem, hipStream_t s) {
+static int launch_i3n(const Igemm3nParams& P, const BsedLaunch& L) {
   const I3nPlan pl = i3n_plan(P.d.NP, P.PP, P.d.ntaps, P.d.act_bf16);
   if (P.d.act_bf16) {
-    if (pl.PV == 3) return launch_i3n4<NWN, STATS, 3, 3, 1>(P, grid, smem, s);
-    if (pl.PV == 5) return launch_i3n4<NWN, STATS, 5, 3, 1>(P, grid, smem, s);
+    if (pl.PV == 3) return launch_i3n4<NWN, STATS, 3, 3, 1>(P, L);
+    if (pl.PV == 5) return launch_i3n4<NWN, STATS, 5, 3, 1>(P, L);
   } else {
-    if (NWN == 4 && pl.PV == 6 && pl.WPE == 3) return launch_i3n4<NWN, STATS, 6, 3>(P, grid, smem, s);
-    if (NWN == 4 && pl.PV == 9 && pl.WPE == 3) return launch_i3n4<NWN, STATS, 9, 3>(P, grid, smem, s);
-    if (NWN == 4 && pl.PV == 6) return launch_i3n4<NWN, STATS, 6, 2>(P, grid, smem, s);
-    if (NWN == 4 && pl.PV == 9) return launch_i3n4<NWN, STATS, 9, 2>(P, grid, smem, s);
-    if (NWN != 4 && pl.PV == 6) return launch_i3n4<NWN, STATS, 6, 3>(P, grid, smem, s);
-    if (NWN != 4 && pl.PV == 9) return launch_i3n4<NWN, STATS, 9, 3>(P, grid, smem, s);
+    if (NWN == 4 && pl.PV == 6 && pl.WPE == 3) return launch_i3n4<NWN, STATS, 6, 3>(P, L);
+    if (NWN == 4 && pl.PV == 9 && pl.WPE == 3) return launch_i3n4<NWN, STATS, 9, 3>(P, L);
+    if (NWN == 4 && pl.PV == 6) return launch_i3n4<NWN, STATS, 6, 2>(P, L);
+    if (NWN == 4 && pl.PV == 9) return launch_i3n4<NWN, STATS, 9, 2>(P, L);
+    if (NWN != 4 && pl.PV == 6) return launch_i3n4<NWN, STATS, 6, 3>(P, L);
+    if (NWN != 4 && pl.PV == 9) return launch_i3n4<NWN, STATS, 9, 3>(P, L);
   }
   bsed_set_error("bsed_igemm3n: patch of %d positions exceeds the 288 this build stages", P.PP);
   return BSED_ERR_ARG;
 }
 
-// NWN | MW << 4 | PV << 8 | WPE << 12 | ABF << 16 of the build bsed_igemm3n would launch (kernel labels of bench.py)
-extern "C" int bsed_igemm3n_variant(const BsedIgemmDesc* d) {
-  if (!d || d->TH <= 0 || d->TW <= 0) return -1;
-  const int PP = (d->TW + 2 * d->hw) * (d->TH + 2 * d->hh);
-  const I3nPlan pl = i3n_plan(d->NP, PP, d->ntaps, d->act_bf16);
-  // bit 17: the 16 x 16 x 32 MFMA form (nine-tap instances, template argument SH)
-  return pl.NWN | pl.MW << 4 | pl.PV << 8 | pl.WPE << 12 | (d->act_bf16 ? 1 : 0) << 16 |
-         (((d->ntaps == 9 || (pl.NWN == 4 && pl.WPE == 2)) && i3n_shape16(d->act_bf16)) ? 1 : 0) << 17;
-}
-
-extern "C" int bsed_igemm3n_stats_rows(const BsedIgemmDesc* d) {
-  if (!d || d->TH <= 0 || d->TW <= 0) return -1;
-  const I3nPlan pl = i3n_plan(d->NP, (d->TW + 2 * d->hw) * (d->TH + 2 * d->hh), d->ntaps, d->act_bf16);
-  return d->NB * ceil_div(d->H, d->TH) * (d->W / d->TW) * pl.MW;
-}
-
-extern "C" int bsed_igemm3n(const BsedIgemmDesc* desc, void* stream) {
-  BSED_CHECK_ARG(desc, "bsed_igemm3n: null descriptor");
+// bsed_igemm3n (plan == null: pointer checks and the launch) and its plan (the label only) after ONE prepare step: every
+// shape check, the derived geometry, the LDS bytes and the grid
+int bsed_run_igemm3n(const BsedIgemmDesc* desc, void* stream, BsedContractPlan* plan) {
   Igemm3nParams P;
-  P.d = *desc;
-  BsedIgemmDesc& d = P.d;
-  BSED_CHECK_ARG(d.in && d.w && d.out, "bsed_igemm3n: null tensor");
-  BSED_CHECK_ARG(d.epilogue == BSED_EPI_PLAIN || d.epilogue == BSED_EPI_STATS, "bsed_igemm3n: PLAIN / STATS epilogues only");
-  BSED_CHECK_ARG(d.epilogue != BSED_EPI_STATS || d.stats, "bsed_igemm3n: STATS needs a stats buffer");
-  const int ntiles = bsed_tile_geometry(P, "bsed_igemm3n", 32, d.act_bf16 ? 8 : 4);
+  const int ntiles = bsed_igemm3_front(desc, P, "bsed_igemm3n", 32, desc && desc->act_bf16 ? 8 : 4);
   if (ntiles < 0) return ntiles;
-  BSED_CHECK_ARG(d.out_pitch >= d.N, "bsed_igemm3n: bad pitch");
-  const int BN = d.NP % 128 == 0 ? 128 : (d.NP % 64 == 0 ? 64 : 32);
+  const BsedIgemmDesc& d = P.d;
+  const int BN = bsed_contract_bn(d.NP);
   P.b_off = (P.PP * (d.act_bf16 ? 40 : I3N_ROW) + 7) & ~7;
   P.prio = (i3n_knob() & 8) ? 0 : 1;
   // two patch buffers when the layer has more than one chunk
   const size_t bytes = (size_t)P.b_off * sizeof(unsigned short) * (d.CIN > I3N_KC ? 2 : 1);
   BSED_CHECK_ARG(bytes <= 160 * 1024, "bsed_igemm3n: tile needs %zu B of LDS", bytes);
   BSED_CHECK_ARG((size_t)d.H * d.W * d.in_pitch < (1ull << 31), "bsed_igemm3n: an image of 2^31 elements or more");
-  dim3 grid((unsigned)ntiles, d.NP / BN);
-  hipStream_t s = (hipStream_t)stream;
+  BsedLaunch L{dim3((unsigned)ntiles, d.NP / BN), bytes, (hipStream_t)stream, nullptr};
+  // a tile writes MW = 4 / NWN = 128 / BN partial rows of statistics: one per wave along M
+  if (plan) L = bsed_plan_begin(plan, ntiles, ntiles, ntiles * (128 / BN));
+  else if (const int rc = bsed_igemm3_pointers(d, "bsed_igemm3n")) return rc;
   const bool st = d.epilogue == BSED_EPI_STATS;
-  if (BN == 128) return st ? launch_i3n<4, 1>(P, grid, bytes, s) : launch_i3n<4, 0>(P, grid, bytes, s);
-  if (BN == 64) return st ? launch_i3n<2, 1>(P, grid, bytes, s) : launch_i3n<2, 0>(P, grid, bytes, s);
-  return st ? launch_i3n<1, 1>(P, grid, bytes, s) : launch_i3n<1, 0>(P, grid, bytes, s);
+  if (BN == 128) return st ? launch_i3n<4, 1>(P, L) : launch_i3n<4, 0>(P, L);
+  if (BN == 64) return st ? launch_i3n<2, 1>(P, L) : launch_i3n<2, 0>(P, L);
+  return st ? launch_i3n<1, 1>(P, L) : launch_i3n<1, 0>(P, L);
 }
+extern "C" int bsed_igemm3n(const BsedIgemmDesc* desc, void* stream) { return bsed_run_igemm3n(desc, stream, nullptr); }

@@ -2,6 +2,7 @@
 function fills a descriptor with device pointers / shapes and launches HIP kernels on the current
 stream.  Activations are NHWC fp32 tensors."""
 import ctypes
+import functools
 import os
 from typing import NamedTuple
 
@@ -15,8 +16,9 @@ EPI_PLAIN, EPI_STATS, EPI_GLU_POOL, EPI_GLU_BWD, EPI_ADD_STATS2 = (
 PACK_MAX_JOBS = L.CONSTANTS["BSED_PACK_MAX_JOBS"]
 REDUCE_MAX_JOBS = L.CONSTANTS["BSED_REDUCE_MAX_JOBS"]
 BN_EVAL_MAX_JOBS = L.CONSTANTS["BSED_BN_EVAL_MAX_JOBS"]
-IgemmDesc, WgradDesc, HeadBwdDesc, PackJob, ReduceJob, BnEvalJob, GluDesc, GluPlan = (L.STRUCTS["Bsed" + n] for n in (
-    "IgemmDesc", "WgradDesc", "HeadBwdDesc", "PackJob", "ReduceJob", "BnEvalJob", "GluDesc", "GluPlan"))
+IgemmDesc, WgradDesc, HeadBwdDesc, PackJob, ReduceJob, BnEvalJob, GluDesc, GluPlan, ContractPlan = (
+    L.STRUCTS["Bsed" + n] for n in ("IgemmDesc", "WgradDesc", "HeadBwdDesc", "PackJob", "ReduceJob", "BnEvalJob", "GluDesc",
+                                    "GluPlan", "ContractPlan"))
 
 TAPS3x3 = [(kh - 1, kw - 1) for kh in range(3) for kw in range(3)]
 TAP1 = ((0, 0),)   # a plain GEMM: (positions, CIN) x (CIN, N)
@@ -178,12 +180,6 @@ def tile_for(W):
     return 128 // tw, tw
 
 
-def _map_tiles(NB, H, W):
-    """(TH, TW, tile count) of an (NB, H, W) map cut into tile_for(W) tiles"""
-    TH, TW = tile_for(W)
-    return TH, TW, NB * ((H + TH - 1) // TH) * (W // TW)
-
-
 def _p(t):
     return L.ptr(t).value if t is not None else None
 
@@ -220,21 +216,30 @@ def pack_weight(src, ntaps, K, N, s_tap, s_k, s_n, src_offset=0):
 
 
 def _tile_taps(d, H, W, taps):
-    """Tile, taps and halo of an IgemmDesc / WgradDesc; returns the tile count of one (H, W) image."""
-    d.TH, d.TW, ntiles = _map_tiles(1, H, W)
+    """Tile, taps and halo of an IgemmDesc / WgradDesc"""
+    d.TH, d.TW = tile_for(W)
     hh = hw = 0
     for i, (a, b) in enumerate(taps):
         d.dh[i], d.dw[i] = a, b
         hh, hw = max(hh, abs(a)), max(hw, abs(b))
     d.hh, d.hw, d.ntaps = hh, hw, len(taps)
-    return ntiles
+
+
+def _contract_plan(entry, d):
+    """BsedContractPlan of the contraction entry point's launch for the shape fields of d: the grid size G (stored into
+    d.G), the rows of statistics the launch writes and, as plan.label, the instance it runs (the KernelTimer label)"""
+    plan = ContractPlan()
+    query = L.lib().bsed_wgrad_plan if isinstance(d, WgradDesc) else L.lib().bsed_igemm_plan
+    L.check(query(ctypes.byref(d), L.CONSTANTS["BSED_CONTRACT_" + entry[len("bsed_"):].upper()], ctypes.byref(plan)), entry)
+    d.G = plan.G
+    return plan
 
 
 def _igemm_desc(NB, H, W, CIN, N, NP, taps, epilogue, valid=None):
-    """(IgemmDesc, tile count) of a contraction without pooling, with dense rows (pitch = channel count); the
-    pointers, and whatever else differs, are the caller's."""
+    """IgemmDesc of a contraction without pooling, with dense rows (pitch = channel count); the pointers, and whatever
+    else differs, are the caller's."""
     d = IgemmDesc()
-    ntiles = NB * _tile_taps(d, H, W, taps)
+    _tile_taps(d, H, W, taps)
     d.NB, d.H, d.W, d.CIN, d.N, d.NP = NB, H, W, CIN, N, NP
     d.in_pitch, d.out_pitch, d.e_pitch = CIN, N, N
     d.ph = d.pw = 1
@@ -242,7 +247,7 @@ def _igemm_desc(NB, H, W, CIN, N, NP, taps, epilogue, valid=None):
     d.epilogue = epilogue
     if valid:
         d.valid_h, d.valid_w = valid
-    return d, ntiles
+    return d
 
 
 def igemm(inp, wpk, N, NB, H, W, CIN, taps=((0, 0),), bias=None, out=None, epilogue=EPI_PLAIN, in_pitch=None,
@@ -251,18 +256,15 @@ def igemm(inp, wpk, N, NB, H, W, CIN, taps=((0, 0),), bias=None, out=None, epilo
     """Launch the implicit GEMM.  Returns (out, stats or None).  valid = (h, w): only output positions inside that
     extent are stored / enter the STATS sums (the rest of a freshly allocated ``out`` is zero)."""
     NP = wpk.shape[2]
-    d, ntiles = _igemm_desc(NB, H, W, CIN, N, NP, taps, epilogue, valid)
+    d = _igemm_desc(NB, H, W, CIN, N, NP, taps, epilogue, valid)
     ph, pw = pool
     Hp, Wp = H // ph, W // pw
     dev = inp.device
     if out is None:
         shape = (NB, Hp, Wp, N) if epilogue == EPI_GLU_POOL else (NB, H, W, N)
         out = (torch.zeros if valid else torch.empty)(shape, device=dev, dtype=torch.float32)
-    stats = None
-    if epilogue in (EPI_STATS, EPI_GLU_BWD, EPI_ADD_STATS2):
-        stats = torch.empty((ntiles, 2, N), device=dev, dtype=torch.float32)
     d.in_ = _dp(inp, in_offset); d.w = _p(wpk); d.bias = _p(bias); d.out = _p(out); d.out2 = _p(out2)
-    d.stats = _p(stats); d.a_scale = _p(a_scale); d.a_shift = _p(a_shift); d.e_src = _p(e_src)
+    d.a_scale = _p(a_scale); d.a_shift = _p(a_shift); d.e_src = _p(e_src)
     d.e_scale = _p(e_scale); d.e_shift = _p(e_shift); d.e_dpool = _p(e_dpool)
     if in_pitch is not None:
         d.in_pitch = in_pitch
@@ -270,9 +272,12 @@ def igemm(inp, wpk, N, NB, H, W, CIN, taps=((0, 0),), bias=None, out=None, epilo
         d.out_pitch = out_pitch
     d.ph, d.pw, d.Hp, d.Wp = ph, pw, Hp, Wp
     d.drop_p, d.rng_stream, d.seed = drop_p, rng_stream, seed
-    kc = 32 if CIN % 32 == 0 else 16
-    bn = 128 if NP % 128 == 0 else (64 if NP % 64 == 0 else 32)
-    _launch((f"igemm_kernel<{kc}, {bn}, {epilogue}>", len(taps), CIN, N, H, W), 2.0 * NB * H * W * len(taps) * CIN * N,
+    plan = _contract_plan("bsed_igemm", d)
+    stats = None
+    if epilogue in (EPI_STATS, EPI_GLU_BWD, EPI_ADD_STATS2):
+        stats = torch.empty((plan.stats_rows, 2, N), device=dev, dtype=torch.float32)
+        d.stats = _p(stats)
+    _launch((plan.label.decode(), len(taps), CIN, N, H, W), 2.0 * NB * H * W * len(taps) * CIN * N,
             lambda: L.call("bsed_igemm", ctypes.byref(d), L.stream()))
     return out, stats
 
@@ -415,49 +420,46 @@ def pack_weight3s(src, ntaps, N, s_tap, s_k, s_n, K=16):
     return dst
 
 
+@functools.lru_cache(maxsize=None)
 def igemm3s_supported(W, CIN, ntaps=9):
-    TH, TW = tile_for(W)
-    halo = 1 if ntaps > 1 else 0
-    return CIN in (16, 32) and (TH + 2 * halo) * (TW + 2 * halo) <= (256 if CIN == 16 else 192)
+    """True iff bsed_igemm3s takes CIN input channels over ntaps (9 or 1) taps on a width-W map: its plan's answer for a
+    one-row map of that width (the checks do not depend on the other sizes)"""
+    d = _igemm_desc(1, 1, W, CIN, 32, 32, TAPS3x3[:ntaps] if ntaps > 1 else TAP1, EPI_PLAIN)
+    return L.lib().bsed_igemm_plan(ctypes.byref(d), L.CONSTANTS["BSED_CONTRACT_IGEMM3S"], ctypes.byref(ContractPlan())) == 0
+
+
+def _igemm3_launch(entry, inp, w, N, NP, NB, H, W, CIN, taps, bias, epilogue, valid=None):
+    """One split-fp32 forward contraction (bsed_igemm3 / bsed_igemm3s / bsed_igemm3n) with packed weights w of NP output
+    channels: buffers sized by the entry point's plan.  Returns (out, stats (plan.stats_rows, 2, N) or None)."""
+    d = _igemm_desc(NB, H, W, CIN, N, NP, taps, epilogue, valid)
+    d.act_bf16 = _abf(inp)
+    plan = _contract_plan(entry, d)
+    out = (torch.zeros if valid else torch.empty)((NB, H, W, N), device=inp.device, dtype=inp.dtype)
+    stats = torch.empty((plan.stats_rows, 2, N), device=inp.device, dtype=torch.float32) if epilogue == EPI_STATS else None
+    d.in_ = _dp(inp); d.w = w.data_ptr(); d.bias = _p(bias); d.out = out.data_ptr(); d.stats = _p(stats)
+    _launch((plan.label.decode(), len(taps), CIN, N, H, W), 2.0 * NB * H * W * len(taps) * CIN * N,
+            lambda: L.call(entry, ctypes.byref(d), L.stream()), _esz(inp) * NB * H * W * (CIN + N))
+    return out, stats
 
 
 def igemm3s(inp, wtab, N, NB, H, W, taps, bias=None, epilogue=EPI_PLAIN):
     """CIN = 16 / 32 convolution on the bf16 cores (split-fp32), all taps' weights resident in LDS.
     Returns (out, stats (G,2,N) or None)."""
-    CIN = 16 * wtab.shape[2]
-    d, ntiles = _igemm_desc(NB, H, W, CIN, N, wtab.shape[0] * 32, taps, epilogue)
-    dev = inp.device
-    out = torch.empty((NB, H, W, N), device=dev, dtype=inp.dtype)
-    G = int(min(ntiles, L.lib().bsed_igemm3s_auto_g2(inp.shape[-1], N)))
-    stats = torch.empty((G, 2, N), device=dev, dtype=torch.float32) if epilogue == EPI_STATS else None
-    d.act_bf16 = _abf(inp)
-    d.in_ = _dp(inp); d.w = wtab.data_ptr(); d.bias = _p(bias); d.out = out.data_ptr(); d.stats = _p(stats)
-    nv = 16 if N <= 16 and N % 4 == 0 else 32                      # transposed epilogue (bsed_igemm3s)
-    _launch((f"igemm3s_kernel<{1 if epilogue == EPI_STATS else 0}, {len(taps)}, {CIN // 16}, {nv}, {d.act_bf16}>", len(taps), CIN, N, H, W),
-            2.0 * NB * H * W * len(taps) * CIN * N, lambda: L.call("bsed_igemm3s", ctypes.byref(d), G, L.stream()),
-            _esz(inp) * NB * H * W * (CIN + N))
-    return out, stats
+    return _igemm3_launch("bsed_igemm3s", inp, wtab, N, wtab.shape[0] * 32, NB, H, W, 16 * wtab.shape[2], taps, bias, epilogue)
 
 
 def igemm3(inp, w3, N, NB, H, W, CIN, taps, bias=None, epilogue=EPI_PLAIN, valid=None):
     """3x3 conv forward / dgrad on the bf16 matrix cores with split-fp32 operands.  Returns (out, stats or None).
-    valid: see igemm."""
+    valid: see igemm.  w3: the fragment-order table of pack_weight3s for the layer (K = CIN; bsed_igemm3n) or the slab
+    layout of bsed_pack_weight3 (bsed_igemm3)."""
     if w3.dim() == 6:
-        return _igemm3n(inp, w3, N, NB, H, W, CIN, taps, bias, epilogue, valid)
+        if w3.shape[2] * 16 != CIN or w3.shape[1] != len(taps):
+            raise L.BsedError(f"igemm3: weight table packed for K={w3.shape[2] * 16}, {w3.shape[1]} taps; "
+                              f"called with CIN={CIN}, {len(taps)} taps")
+        return _igemm3_launch("bsed_igemm3n", inp, w3, N, w3.shape[0] * 32, NB, H, W, CIN, taps, bias, epilogue, valid)
     if inp.dtype != torch.float32:
         raise L.BsedError("bf16 activations need the N-split route of igemm3 (igemm3_nsplit()), not the slab kernel")
-    NP = w3.shape[2]
-    d, ntiles = _igemm_desc(NB, H, W, CIN, N, NP, taps, epilogue, valid)
-    bn = 128 if NP % 128 == 0 else (64 if NP % 64 == 0 else 32)
-    dev = inp.device
-    out = (torch.zeros if valid else torch.empty)((NB, H, W, N), device=dev, dtype=torch.float32)
-    stats = torch.empty((ntiles, 2, N), device=dev, dtype=torch.float32) if epilogue == EPI_STATS else None
-    d.in_ = _dp(inp); d.w = w3.data_ptr(); d.bias = _p(bias); d.out = _p(out); d.stats = _p(stats)
-    need = ((d.TH + 2 * d.hh) * (d.TW + 2 * d.hw) * 8 + 255) // 256        # float4 patch elements per thread (launch_i3)
-    pv = 12 if need > 9 else (9 if need > 6 else 6)
-    _launch((f"igemm3_kernel<{bn}, {1 if epilogue == EPI_STATS else 0}, 1, {pv}>", len(taps), CIN, N, H, W),
-            2.0 * NB * H * W * len(taps) * CIN * N, lambda: L.call("bsed_igemm3", ctypes.byref(d), L.stream()))
-    return out, stats
+    return _igemm3_launch("bsed_igemm3", inp, w3, N, w3.shape[2], NB, H, W, CIN, taps, bias, epilogue, valid)
 
 
 def set_igemm3n_shape(shape):
@@ -469,28 +471,6 @@ def set_igemm3n_wpe(wpe):
     """A/B knob of the BN = 128 build: 2 / 3 = built for that many waves per SIMD whatever the shape; + 8 = no raised
     wave priority outside the MFMA loop; 0 / None = default"""
     L.lib().bsed_igemm3n_set_wpe(wpe or 0)
-
-
-def _igemm3n(inp, wtab, N, NB, H, W, CIN, taps, bias, epilogue, valid):
-    """bsed_igemm3n: wtab = pack_weight3s table of the layer (K = CIN).  Returns (out, stats (rows,2,N) or None)."""
-    if wtab.shape[2] * 16 != CIN or wtab.shape[1] != len(taps):
-        raise L.BsedError(f"igemm3: weight table packed for K={wtab.shape[2] * 16}, {wtab.shape[1]} taps; "
-                          f"called with CIN={CIN}, {len(taps)} taps")
-    d, _ = _igemm_desc(NB, H, W, CIN, N, wtab.shape[0] * 32, taps, epilogue, valid)
-    dev = inp.device
-    out = (torch.zeros if valid else torch.empty)((NB, H, W, N), device=dev, dtype=inp.dtype)
-    d.act_bf16 = _abf(inp)
-    d.in_ = _dp(inp); d.w = wtab.data_ptr(); d.bias = _p(bias); d.out = out.data_ptr()
-    rows = L.lib().bsed_igemm3n_stats_rows(ctypes.byref(d))
-    var = L.lib().bsed_igemm3n_variant(ctypes.byref(d))
-    stats = torch.empty((rows, 2, N), device=dev, dtype=torch.float32) if epilogue == EPI_STATS else None
-    d.stats = _p(stats)
-    _launch((f"igemm3n_kernel<{var & 15}, {(var >> 4) & 15}, {1 if epilogue == EPI_STATS else 0}, {(var >> 8) & 15}, "
-             f"{1 if len(taps) == 9 else 0}, {(var >> 12) & 15}, {(var >> 16) & 1}, {(var >> 17) & 1}>",
-             len(taps), CIN, N, H, W),
-            2.0 * NB * H * W * len(taps) * CIN * N, lambda: L.call("bsed_igemm3n", ctypes.byref(d), L.stream()),
-            _esz(inp) * NB * H * W * (CIN + N))
-    return out, stats
 
 
 def contract_route(direction, CIN, N, W, ntaps, mode):
@@ -550,28 +530,15 @@ def wgrad(inp, dy, NB, H, W, CIN, N, taps=((0, 0),), in_pitch=None, dy_pitch=Non
     d.bn_y, d.bn_coef, d.bn_mean, d.dy_out = _dp(bn_y), _p(bn_coef), _p(bn_mean), _dp(dy_out)
     d.in_pitch = CIN if in_pitch is None else in_pitch
     d.dy_pitch = N if dy_pitch is None else dy_pitch
-    d.NB, d.H, d.W, d.CIN, d.CINP, d.N, d.NP, d.G = NB, H, W, CIN, CINP, N, NP, 0
-    G = getattr(L.lib(), f"bsed_wgrad{sfx}_auto_g")(ctypes.byref(d))
-    if G <= 0:
-        raise L.BsedError("bsed_wgrad_auto_g: " + L.lib().bsed_last_error().decode())
+    d.NB, d.H, d.W, d.CIN, d.CINP, d.N, d.NP = NB, H, W, CIN, CINP, N, NP
+    plan = _contract_plan(f"bsed_wgrad{sfx}", d)
+    G = plan.G
     part = torch.empty((G, len(taps), CINP, NP), device=inp.device, dtype=torch.float32)
-    d.part, d.G = _p(part), G
-    var = getattr(L.lib(), f"bsed_wgrad{sfx}_variant")(ctypes.byref(d))
-    # labels = the template instances as rocprofv3 prints them (bench.py joins the two by name)
-    w1 = (var >> 13) & 1
-    bs, geo, var = (var >> 12) & 1, (var >> 8) & 0xf, var & 0xff
-    ab = d.act_bf16
-    if w1:
-        kname = f"wgrad1_kernel<{'true' if var & 1 else 'false'}, {ab}>"
-    elif var % 16 == 1:
-        kname = f"wgrad3p_kernel<{var // 16}, {geo}, {ab}>"
-    elif sfx:
-        kname = f"wgrad3_kernel<{var // 16}, {var % 16}, {'true' if bs else 'false'}, {ab}>"
-    else:
-        kname = f"wgrad_kernel<{var // 16}, {var % 16}>"
+    d.part = _p(part)
     # algorithmic bytes: the input and dy once; with the fused BatchNorm backward also y (read) and d_y (written)
     nbytes = _esz(inp) * NB * H * W * (CIN + N * (1 + (1 if bn_y is not None else 0) + (1 if dy_out is not None else 0)))
-    _launch((kname, len(taps), CIN, N, H, W),
+    # the label = the template instance as rocprofv3 prints it (bench.py joins the two by name)
+    _launch((plan.label.decode(), len(taps), CIN, N, H, W),
             2.0 * NB * H * W * len(taps) * CIN * N, lambda: L.call(f"bsed_wgrad{sfx}", ctypes.byref(d), L.stream()), nbytes)
     return part, G, CINP, NP
 

@@ -152,10 +152,26 @@ typedef struct BsedIgemmDesc {
                                * whose last row / column of the grid is not an output).  PLAIN / STATS epilogues. */
   int act_bf16;               /* bsed_igemm3n / bsed_igemm3s: 1 = `in` and `out` are bf16 tensors ("bf16" throughput mode:
                                * one bf16 MFMA per product, fp32 accumulation, bias and statistics); 0 = fp32 */
+  int G;                      /* bsed_igemm3s: workgroups per 32 output channels, BsedContractPlan.G or any value in
+                               * 1..max_G; the other entry points ignore it */
 } BsedIgemmDesc;
 
+/* What the library would launch for a contraction descriptor (ABI 12): one answer for the six entry points below. */
+enum { BSED_CONTRACT_IGEMM = 0, BSED_CONTRACT_IGEMM3 = 1, BSED_CONTRACT_IGEMM3S = 2, BSED_CONTRACT_IGEMM3N = 3,
+       BSED_CONTRACT_WGRAD = 4, BSED_CONTRACT_WGRAD3 = 5 };
+typedef struct BsedContractPlan {
+  int G;           /* recommended workgroups along grid.x: igemm3s / wgrad* the persistent-grid size, else the tile count */
+  int max_G;       /* largest G the entry point accepts (position tiles) */
+  int stats_rows;  /* rows of (2, N) the STATS-type epilogues write at that G; 0 for the weight gradients */
+  char label[96];  /* the template instance the entry point would launch now, spelled as rocprofv3 prints it */
+} BsedContractPlan;
+/* Both queries run every shape check of the entry point `kernel` names, with its messages, and return BSED_ERR_ARG
+ * where the launch would; they make no HIP call.  Pointers and G are ignored, except that a BsedWgradDesc with bn_y set
+ * is planned as the BatchNorm-backward-on-load form it asks for.  `label` follows the bsed_igemm3n_set_* hooks and
+ * BSED_WGRAD3_NOPIPE as they stand at the call. */
+int bsed_igemm_plan(const BsedIgemmDesc* desc /*host*/, int kernel /*0..3*/, BsedContractPlan* out /*host*/);
+
 int bsed_igemm(const BsedIgemmDesc* desc /*host*/, void* stream);
-int bsed_igemm_num_tiles(const BsedIgemmDesc* desc /*host*/);
 
 /* Same contraction with split-fp32 operands on the bf16 matrix cores ("bf16x3": a*b ~ a_hi*b_hi + a_hi*b_lo +
  * a_lo*b_hi, fp32 accumulate, ~1e-5 relative; csrc/igemm3.hip).  BSED_EPI_PLAIN / BSED_EPI_STATS only, CIN a
@@ -165,7 +181,7 @@ int bsed_pack_weight3(const float* src, void* dst, int ntaps, int K, int N, int 
                       void* stream);
 /* CIN = 16 / 32 variant (the 16 -> 32 channel convolution, data gradients of 32-channel layers): weights of all taps
  * stay in LDS, CIN/16 MFMA K steps per tap,
- * persistent grid of G workgroups per 32 output channels (bsed_igemm3s_auto_g()); desc as for bsed_igemm3 with
+ * persistent grid of desc->G workgroups per 32 output channels (bsed_igemm_plan); desc as for bsed_igemm3 with
  * w = bsed_pack_weight3s table ((NP/32) * ntaps * (K/16) * 2 * 64 * 16 bytes); STATS writes G partial rows (one per workgroup). */
 int bsed_pack_weight3s(const float* src, void* dst, int ntaps, int K, int N, int NP, long s_tap, long s_k, long s_n,
                        void* stream);
@@ -180,22 +196,18 @@ typedef struct BsedPackJob {
   long s_tap, s_k, s_n;
 } BsedPackJob;
 int bsed_pack_weights_batch(const BsedPackJob* jobs /*host*/, int njobs, void* stream);
-int bsed_igemm3s(const BsedIgemmDesc* desc, int G, void* stream);
+int bsed_igemm3s(const BsedIgemmDesc* desc /*host*/, void* stream);
 /* The same contraction as bsed_igemm3 (same reference layers: src/models/CNN.py:46-47, the seven nn.Conv2d; GRU input
  * projections src/models/RNN.py:7-16) in the round-3 structure (csrc/igemm3n.hip): a wave owns 32 output channels and
  * fetches their weight fragments straight from global memory (w = bsed_pack_weight3s table, K any multiple of 32), the
  * activation patch is double-buffered in LDS, one barrier per 32-channel chunk.  `out` is bit-identical to
- * bsed_igemm3's; STATS writes bsed_igemm3n_stats_rows(desc) partial rows of (2, N). */
+ * bsed_igemm3's; STATS writes BsedContractPlan.stats_rows partial rows of (2, N): 4 / NWN per tile. */
 int bsed_igemm3n(const BsedIgemmDesc* desc /*host*/, void* stream);
-int bsed_igemm3n_stats_rows(const BsedIgemmDesc* desc /*host: NB, H, W, TH, TW, NP*/);
-int bsed_igemm3n_variant(const BsedIgemmDesc* desc);   /* NWN | MW << 4 | PV << 8 | WPE << 12 of the build */
 void bsed_igemm3n_set_wpe(int knob);  /* test hook: 2 / 3 = the BN = 128 build for that many waves per SIMD whatever the
                                        * shape, + 8 = no raised wave priority outside the MFMA loop, 0 = default */
 void bsed_igemm3n_set_shape(int shape); /* test hook: MFMA shape of the nine-tap instances, 16 = v_mfma_f32_16x16x32_bf16 (default with
                                          * fp32 activations), 32 = v_mfma_f32_32x32x16_bf16 (default with bf16 activations, and
                                          * bit-identical to bsed_igemm3); 0 = defaults */
-int bsed_igemm3s_auto_g(void);
-int bsed_igemm3s_auto_g2(int CIN, int N);   /* per shape (resident workgroups differ with the LDS footprint) */
 
 /* dW[tap][k][n] = sum_p in[p + (dh,dw)(tap)][k] * dy[p][n]: persistent workgroups over position tiles
  * write partial slabs part[G][ntaps][CINP][NP]; bsed_reduce_partials sums them into the gradient. */
@@ -221,20 +233,16 @@ typedef struct BsedWgradDesc {
                           * the BatchNorm-backward map and the accumulation in fp32); 0 = fp32 */
 } BsedWgradDesc;
 
+/* BsedContractPlan of bsed_wgrad (BSED_CONTRACT_WGRAD) / bsed_wgrad3 (BSED_CONTRACT_WGRAD3): G = the recommended number
+ * of partial slabs, label = wgrad_kernel / wgrad3_kernel / wgrad3p_kernel / wgrad1_kernel with its template arguments */
+int bsed_wgrad_plan(const BsedWgradDesc* desc /*host*/, int kernel /*4, 5*/, BsedContractPlan* out /*host*/);
 int bsed_wgrad(const BsedWgradDesc* desc /*host*/, void* stream);
-/* recommended number of partial slabs G for this shape (pointers in desc are ignored) */
-int bsed_wgrad_auto_g(const BsedWgradDesc* desc /*host*/);
-/* template instance bsed_wgrad launches for this shape, as MAXS*16 + NW (labels profiles and bench lines) */
-int bsed_wgrad_variant(const BsedWgradDesc* desc /*host*/);
 /* the same contraction with split-fp32 operands on the bf16 matrix cores (bf16x3, ~1e-5 relative): both tiles stay
  * position-major in LDS (bf16 hi / lo planes) and the operand fragments come out of transposing LDS reads; multi-tap
  * shapes whose two tile buffers fit in LDS run the producer/consumer kernel (wgrad3p_kernel).  Same descriptor, same
- * partial-slab layout; G must come from bsed_wgrad3_auto_g (it differs between the two kernels).
- * bsed_wgrad3_variant: MAXS*16 + NW, NW == 1 meaning wgrad3p_kernel<MAXS>; bit 12 = the BS template argument of
- * wgrad3_kernel<MAXS, NW, BS> (labels only).  BSED_WGRAD3_NOPIPE=1 in the environment forces wgrad3_kernel (tests). */
+ * partial-slab layout; G should come from bsed_wgrad_plan (the recommendation differs between the kernels).
+ * BSED_WGRAD3_NOPIPE=1 in the environment forces wgrad3_kernel (tests). */
 int bsed_wgrad3(const BsedWgradDesc* desc /*host*/, void* stream);
-int bsed_wgrad3_auto_g(const BsedWgradDesc* desc /*host*/);
-int bsed_wgrad3_variant(const BsedWgradDesc* desc /*host*/);
 /* dst[tap*s_tap + k*s_k + n*s_n] (+)= sum_g part[g][tap][k][n]   (k < K, n < N) */
 int bsed_reduce_partials(const float* part, int G, int ntaps, int KP, int NP, int K, int N, float* dst,
                          long s_tap, long s_k, long s_n, int accumulate, void* stream);

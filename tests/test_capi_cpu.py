@@ -85,7 +85,7 @@ def test_every_prototype_is_bound_from_the_header():
 @pytest.mark.skipif(not (shutil.which("cc") or shutil.which("gcc")), reason="no host C compiler")
 def test_struct_layouts_and_constants_match_the_c_compiler(tmp_path):
     assert set(L.STRUCTS) == {"BsedMelCfg", "BsedIgemmDesc", "BsedPackJob", "BsedWgradDesc", "BsedReduceJob",
-                              "BsedBnEvalJob", "BsedHeadBwdDesc", "BsedGluDesc", "BsedGluPlan"}
+                              "BsedBnEvalJob", "BsedHeadBwdDesc", "BsedGluDesc", "BsedGluPlan", "BsedContractPlan"}
     assert {"BSED_EPI_PLAIN", "BSED_EPI_STATS", "BSED_EPI_GLU_POOL", "BSED_EPI_GLU_BWD", "BSED_EPI_ADD_STATS2",
             "BSED_PACK_MAX_JOBS", "BSED_REDUCE_MAX_JOBS", "BSED_BN_EVAL_MAX_JOBS"} <= set(L.CONSTANTS)
     lines, want = [], []
@@ -167,8 +167,8 @@ def _conv_desc(entry, TW=16, TH=8, W=16, dh0=-1, ntaps=9, NP=32):
 def test_ill_formed_tile_geometry_is_rejected_before_any_hip_call(entry, defect):
     lib = L.lib()
     d = _conv_desc(entry, **_GEOMETRY_DEFECTS[defect])
-    args = (ctypes.byref(d), 1, None) if entry == "bsed_igemm3s" else (ctypes.byref(d), None)
-    rc = getattr(lib, entry)(*args)
+    d.G = 1                                                       # bsed_igemm3s reads its grid size from the descriptor
+    rc = getattr(lib, entry)(ctypes.byref(d), None)
     msg = lib.bsed_last_error().decode()
     assert rc == -1, (entry, defect, rc, msg)                     # BSED_ERR_ARG: no HIP call was reached
     # wgrad_prepare serves both weight-gradient entries and reports as bsed_wgrad

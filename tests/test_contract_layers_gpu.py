@@ -169,3 +169,54 @@ def test_bf16_activation_instance(monkeypatch):
     monkeypatch.setenv("BSED_IGEMM3N", "1")
     _check_forward_and_dgrad("conv32_64_w8", "bf16", torch.bfloat16)
     _check_bn_on_load("bf16", torch.bfloat16)
+
+
+# ---- BsedContractPlan sizes exactly what the kernels write: the C ABI called directly, one guard row / slab beyond the plan ----
+GH, GW = 9, 16      # one image, tile 8 x 16: two tile rows, the second partial
+PLAN_CASES = [(k, cin, n, abf) for k, cin, ns, abfs in (("igemm", 32, (32, 128), (0,)), ("igemm3", 32, (32, 128), (0,)),
+                                                        ("igemm3n", 32, (32, 128), (0, 1)), ("igemm3s", 16, (32,), (0, 1)),
+                                                        ("wgrad", 32, (32, 128), (0,)), ("wgrad3", 32, (32, 128), (0, 1)))
+              for n in ns for abf in abfs]
+
+
+@pytest.mark.parametrize("kernel,CIN,N,abf", PLAN_CASES, ids=lambda v: str(v))
+def test_plan_sizes_exactly_what_the_kernel_writes(kernel, CIN, N, abf):
+    import ctypes
+
+    from bsed_amd import _lib as L, ops
+    from test_contract_plan_cpu import _desc, _plan
+    dtype = torch.bfloat16 if abf else torch.float32
+    g = torch.Generator().manual_seed(CIN + N + abf)
+    x = torch.randn(1, GH, GW, CIN, generator=g).to(dtype).cuda()
+    d = _desc(kernel, 1, GH, GW, CIN, N, 9, 0 if kernel.startswith("wgrad") else ops.EPI_STATS, abf)
+    rc, plan = _plan(kernel, d)
+    assert rc == 0, L.lib().bsed_last_error().decode()
+    d.G, d.in_ = plan.G, x.data_ptr()
+    if kernel.startswith("wgrad"):
+        assert plan.stats_rows == 0 and 1 <= plan.G <= plan.max_G == 2
+        dy = torch.randn(1, GH, GW, N, generator=g).to(dtype).cuda()
+        buf = torch.full((plan.G + 1, 9, CIN, N), float("nan"), device="cuda")
+        d.dy, d.part = dy.data_ptr(), buf.data_ptr()
+        rows = plan.G
+    else:
+        # (NWN, MW) of bsed_igemm3n: (1, 4) at N = 32, four partial rows per tile; (4, 1) at N = 128, one
+        assert plan.max_G == 2 and plan.stats_rows == (2 * 128 // N if kernel == "igemm3n" else 2)
+        w = (torch.randn(9, CIN, N, generator=g) / (9 * CIN) ** 0.5).cuda()
+        strides = (CIN * N, N, 1)
+        if kernel == "igemm":
+            wpk = ops.pack_weight(w, 9, CIN, N, *strides)
+        elif kernel == "igemm3":
+            wpk = torch.empty((9, CIN // 32, N, 64), device="cuda", dtype=torch.int16)
+            L.call("bsed_pack_weight3", w.data_ptr(), wpk.data_ptr(), 9, CIN, N, N, *strides, L.stream())
+        else:
+            wpk = ops.pack_weight3s(w, 9, N, *strides, K=CIN)
+        out = torch.empty((1, GH, GW, N), device="cuda", dtype=dtype)
+        buf = torch.full((plan.stats_rows + 1, 2, N), float("nan"), device="cuda")
+        d.w, d.out, d.stats = wpk.data_ptr(), out.data_ptr(), buf.data_ptr()
+        rows = plan.stats_rows
+    L.call("bsed_" + kernel, ctypes.byref(d), L.stream())
+    torch.cuda.synchronize()
+    assert torch.isfinite(buf[:rows]).all(), plan.label
+    assert torch.isnan(buf[rows]).all(), plan.label
+    if not kernel.startswith("wgrad"):
+        assert torch.isfinite(out.float()).all()
