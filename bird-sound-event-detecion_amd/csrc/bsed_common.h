@@ -78,7 +78,15 @@ __device__ __forceinline__ void bsed_split2(float a, float b, uint32_t& hi, uint
 }
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
+// The tile of the fp32-core contraction (igemm.hip) and of the weight gradients (wgrad.hip): 128 output positions, staged
+// by 256 threads in the forward kernel
+#define IG_THREADS 256
+#define IG_TILE_M 128
+
 #if defined(__HIPCC__)
+// row of accumulator register r in the C layout of a 32 x 32 MFMA (lh = lane >> 5; pinned on hardware by bsed_selftest_mfma)
+__device__ __forceinline__ int crow(int r, int lh) { return (r & 3) + 8 * (r >> 2) + 4 * lh; }
+
 // ----------------------------------------------------------------------------------------------
 // Activation storage of a kernel instance: ABF = 0 fp32, ABF = 1 bf16 (the "bf16" throughput mode of BASELINE
 // configs[1-2]: conv outputs, pooled outputs and their gradients are bf16 in HBM; accumulation, BatchNorm statistics,

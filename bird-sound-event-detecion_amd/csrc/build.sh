@@ -19,7 +19,8 @@ for f in *.hip; do
     extra=""; [ "$f" = "mel.hip" ] && extra="-fno-slp-vectorize -mllvm -amdgpu-use-amdgpu-trackers=1"
     # glu3.hip / head.hip: no SLP vectorizer either.  (1) Speed: the packed v_pk_* forms it makes of the epilogues'
     # per-element fp32 arithmetic are SLOWER here (GLU backward family 2.14 -> 1.91 ms per step at B = 256, same-box
-    # A/B; igemm.hip, block0.hip and gru.hip lose without it and keep it).  (2) Repeatability: with the vectorizer on, a
+    # A/B; igemm.hip and wgrad.hip -- one file when that was measured --, block0.hip and gru.hip lose without it and keep
+    # it, as does reduce.hip: all three build with the default flags).  (2) Repeatability: with the vectorizer on, a
     # build of glu_bwd3n_kernel whose tile width is a compile-time constant is not bitwise repeatable (the pool /
     # dropout mask of one element class flips in lanes 48..63 from launch to launch; no wait state, scheduling fence or
     # s_waitcnt changes it -- tools/asm_variant.sh experiments).  Cause not identified; masked by

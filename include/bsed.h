@@ -106,7 +106,7 @@ int bsed_mel_db_views_norm(const float* mel_lin, const float* clip_max, int B, i
                            void* stream);
 
 /* ------------------------------------------------------------------------------------------------
- * Implicit-GEMM contraction on the fp32 matrix cores (v_mfma_f32_32x32x2_f32).
+ * Implicit-GEMM contraction on the fp32 matrix cores (v_mfma_f32_32x32x2_f32; csrc/igemm.hip).
  *   out[p][n] = sum_{tap,k} in[p + (dh,dw)(tap)][k] * w[tap][k][n]      zero padding outside (H,W)
  * One body, selected by `epilogue`, replaces the stock ATen/cuDNN ops the reference reaches through
  *   nn.Conv2d 3x3 + train-mode BatchNorm2d statistics   (src/models/CNN.py:46-49)       BSED_EPI_STATS
@@ -209,8 +209,8 @@ void bsed_igemm3n_set_shape(int shape); /* test hook: MFMA shape of the nine-tap
                                          * fp32 activations), 32 = v_mfma_f32_32x32x16_bf16 (default with bf16 activations, and
                                          * bit-identical to bsed_igemm3); 0 = defaults */
 
-/* dW[tap][k][n] = sum_p in[p + (dh,dw)(tap)][k] * dy[p][n]: persistent workgroups over position tiles
- * write partial slabs part[G][ntaps][CINP][NP]; bsed_reduce_partials sums them into the gradient. */
+/* Weight gradients (csrc/wgrad.hip).  dW[tap][k][n] = sum_p in[p + (dh,dw)(tap)][k] * dy[p][n]: persistent workgroups
+ * over position tiles write partial slabs part[G][ntaps][CINP][NP]; bsed_reduce_partials sums them into the gradient. */
 typedef struct BsedWgradDesc {
   const float* in;       /* (NB,H,W,in_pitch) */
   const float* dy;       /* (NB,H,W,dy_pitch) */
@@ -243,7 +243,8 @@ int bsed_wgrad(const BsedWgradDesc* desc /*host*/, void* stream);
  * partial-slab layout; G should come from bsed_wgrad_plan (the recommendation differs between the kernels).
  * BSED_WGRAD3_NOPIPE=1 in the environment forces wgrad3_kernel (tests). */
 int bsed_wgrad3(const BsedWgradDesc* desc /*host*/, void* stream);
-/* dst[tap*s_tap + k*s_k + n*s_n] (+)= sum_g part[g][tap][k][n]   (k < K, n < N) */
+/* The slab reducers (csrc/reduce.hip; one summation order and one split rule behind both entry points: an immediate and
+ * a batched reduction give the same bits).  dst[tap*s_tap + k*s_k + n*s_n] (+)= sum_g part[g][tap][k][n]   (k < K, n < N) */
 int bsed_reduce_partials(const float* part, int G, int ntaps, int KP, int NP, int K, int N, float* dst,
                          long s_tap, long s_k, long s_n, int accumulate, void* stream);
 /* several bsed_reduce_partials in one launch (the host queues the reductions whose results only the optimizer needs
@@ -255,7 +256,7 @@ typedef struct BsedReduceJob {
   long s_tap, s_k, s_n;
 } BsedReduceJob;
 int bsed_reduce_partials_batch(const BsedReduceJob* jobs /*host*/, int njobs, void* stream);
-/* dst[tap][k][n] = src[tap*s_tap + k*s_k + n*s_n], zero for N <= n < NP */
+/* the weight layout of bsed_igemm (csrc/igemm.hip): dst[tap][k][n] = src[tap*s_tap + k*s_k + n*s_n], zero for N <= n < NP */
 int bsed_pack_weight(const float* src, float* dst, int ntaps, int K, int N, int NP, long s_tap, long s_k,
                      long s_n, void* stream);
 

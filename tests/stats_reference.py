@@ -1,5 +1,5 @@
 """float64 restatement of the contracts include/bsed.h gives for the BatchNorm-statistics, reduction and flat-arena
-entry points (csrc/cnn_ops.hip, the slab reducers of csrc/igemm.hip, csrc/optim.hip).  Plain numpy, no kernel structure:
+entry points (csrc/cnn_ops.hip, the slab reducers of csrc/reduce.hip, csrc/optim.hip).  Plain numpy, no kernel structure:
 sums of partials are exactly rounded (math.fsum), so the reference carries no summation error of its own; everything
 else is the header's formula evaluated in double.  float32 scalars (eps, momentum, lr, betas, ...) are taken at the
 float32 value the ABI receives: they are the operation's inputs.  tests/test_stats_reference_cpu.py pins this module

@@ -1,4 +1,4 @@
-"""GPU tests of the MFMA building blocks (csrc/selftest.hip, csrc/igemm.hip)."""
+"""GPU tests of the MFMA building blocks (csrc/selftest.hip, csrc/igemm.hip, csrc/wgrad.hip, csrc/reduce.hip)."""
 import numpy as np
 import pytest
 import torch

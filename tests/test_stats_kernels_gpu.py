@@ -1,5 +1,5 @@
 """The BatchNorm-statistics kernels of csrc/cnn_ops.hip (stats_chunk + stats_finish behind bsed_bn_finalize, bsed_bn_bwd
-and bsed_stats_to_grad; bn_bwd_apply, bn_eval, bn_eval_batch, colsum) and the three slab reducers of csrc/igemm.hip
+and bsed_stats_to_grad; bn_bwd_apply, bn_eval, bn_eval_batch, colsum) and the three slab reducers of csrc/reduce.hip
 against the float64 restatement in tests/stats_reference.py, whose sums are exactly rounded.
 
 Bounds.  u = 2^-24 (fp32 unit roundoff; one correctly rounded operation errs by at most u |x| <= 1 ulp(x)),
@@ -36,7 +36,7 @@ additions.
                     (s2 + s3): depth d = G // 4 + G % 4 + 2.  Split and batch kernels: wave w of S takes slabs w, w + S,
                     ...: n = ceil(G / S) of them at most, same four sums, then the S wave sums in order:
                     d = n // 4 + n % 4 + 2 + (S - 1).  Error <= g(d) sum|part|, + 1 ulp of the result with accumulate.
-                    S follows the dispatch rule stated in the comment of bsed_reduce_partials (_split_s below).
+                    S follows the split rule of csrc/reduce.hip, reduce_shares (_split_s below).
   bitwise           every case is launched twice on fresh buffers and must repeat its bits; a batched or queued
                     reduction must give the bits of the immediate one; a NULL running-statistics call must give the
                     bits of the full one.
@@ -503,7 +503,7 @@ def test_colsum(M, C, pitch, G):
 
 # ------------------------------------------------------------------------------------------------ slab reducers
 def _split_s(G, total):
-    """the dispatch rule of bsed_reduce_partials: 0 = the plain kernel; else S waves share the slabs of 64 elements"""
+    """the split rule of csrc/reduce.hip (reduce_shares): 0 = the plain kernel; else S waves share the slabs of 64 elements"""
     wgs = -(-total // 64)
     if not (wgs < 1024 and G >= 8):
         return 0
