@@ -10,7 +10,9 @@ Everything per frame runs on the GPU for the whole batch: forward (HIP), thresho
 (``bsed_binarize_median``), contiguous-region decode and the seconds conversion (``bsed_decode_count`` /
 ``bsed_decode_write``).  Only the event list (a few rows per clip) travels to the host, where the DataFrames are
 assembled without a per-clip Python loop.  The collar-based event F1 that picks the best checkpoint is computed here too
-(``validate`` below); the intersection F1 and PSDS (psds_eval) and the segment-based metric stay external.
+(``validate`` below), and so are -- on request -- the intersection-based counts behind psds_eval's macro F1, its
+cross-trigger matrix and PSDS (``intersection_counts_gpu``; rules as stated in include/bsed.h, parity with psds_eval not
+pinned); the segment-based metric stays external.
 
   detect_recording  <- no counterpart in the reference, which cuts recordings into 10 s clips offline
                        (src/data/preprocess.py:176-229) and only ever sees clips: one whole recording -> overlapping
@@ -24,6 +26,13 @@ assembled without a per-clip Python loop.  The collar-based event F1 that picks 
                        (``sweep_events_gpu``), Ntp / Nsys / Nref per (threshold, class) counted on the GPU with sed_eval's
                        optimal matching (``event_counts_gpu``), F1 from the integer counts on the host (``event_f1``).
                        ``score_recording`` applies the same counts to a ``detect_recording`` result.
+                       ``intersection=True`` adds the second number of the reference's ``compute_metrics``
+                       (src/evaluation_measures.py:518-526: psds_eval's intersection-based macro F1 with a cross-trigger
+                       matrix) and what its inference drivers make of the sweep (:287-316, :505-510: PSDS at (0, 0, 100),
+                       (1, 0, 100), (0, 1, 100)): DTC / GTC / CTTC counted on the GPU from the same event lists
+                       (``intersection_counts_gpu``, two more launches per batch), F1 / rates / PSDS from the integer
+                       counts on the host (``intersection_f1``, ``psds_rates``, ``PsdsResult``); ``compute_metrics`` and
+                       ``compute_psds_from_operating_points`` are the drop-ins for DataFrames.
 
   validate_weak / get_f_measure_by_class / pseudo_label
                     <- the clip-level side: the reference's per-class weak F1 (src/evaluation_measures.py:346-446, the
@@ -695,6 +704,25 @@ class EventReference:
             self._dev = (torch.from_numpy(self.offsets).cuda(), torch.from_numpy(sec).cuda())
         return self._dev
 
+    def device_evaluated(self):
+        """``evaluated`` as a (B) uint8 GPU tensor, or None when every clip is evaluated (the kernels' NULL)"""
+        if self.evaluated.all():
+            return None
+        return torch.from_numpy(self.evaluated.astype(np.uint8)).cuda()
+
+    def class_durations(self):
+        """(C) float64: the summed length ``offset - onset`` of every class's reference events over the evaluated clips,
+        added clip by clip in list order (``ref_duration`` of ``psds_rates``)"""
+        out = np.zeros(self.C)
+        group = np.repeat(np.arange(self.B * self.C), self.counts.ravel())
+        keep = self.evaluated[group // self.C]
+        lengths, cls = (self.seconds[:, 1] - self.seconds[:, 0])[keep], (group % self.C)[keep]
+        for c in range(self.C):
+            sel = lengths[cls == c]
+            if len(sel):
+                out[c] = np.cumsum(sel)[-1]             # cumsum adds left to right: the value is defined to the bit
+        return out
+
 
 def event_counts_gpu(events, reference, t_collar=0.2, percentage_of_length=0.2, out=None):
     """``EventLists`` x ``EventReference`` of the same batch -> (S,C,3) int64 GPU tensor of (Ntp, Nsys, Nref) summed over the
@@ -753,14 +781,257 @@ def event_f1(counts):
     return {"class_f1": class_f1, "macro": macro, "micro": f(tot[..., 0], tot[..., 1] + tot[..., 2])}
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# Intersection-based scoring: DTC / GTC / CTTC counts on the GPU, intersection F1, rates and PSDS on the host
+# ---------------------------------------------------------------------------------------------------------------------
+def _criteria(intersection, who):
+    """``intersection`` argument (True or a ``(dtc, gtc, cttc)`` tuple) -> the three thresholds as floats"""
+    if intersection is True:
+        return 0.5, 0.5, 0.3
+    try:
+        dtc, gtc, cttc = (float(v) for v in intersection)
+    except (TypeError, ValueError):
+        raise BsedError(f"{who}: intersection must be None, True or a (dtc, gtc, cttc) tuple, got {intersection!r}") from None
+    return dtc, gtc, cttc
+
+
+def intersection_counts_gpu(events, reference, dtc=0.5, gtc=0.5, cttc=0.3, out=None):
+    """``EventLists`` x ``EventReference`` of the same batch -> ``(acc, ct)`` GPU tensors: ``acc`` (S,C,4) int64 of (Ntp, Nfp,
+    Nsys, Nref) and ``ct`` (S,C,C) int64 cross triggers indexed [reference class][estimated class], summed over the
+    evaluated clips and ADDED into ``out = (acc, ct)`` when given (the accumulators of a validation pass).  The
+    intersection criteria of psds_eval as include/bsed.h states them (``bsed_intersection_counts``; parity with psds_eval
+    not pinned): an estimated event passes DTC when the reference events of its class cover at least ``dtc`` of it, is a
+    false positive when it does not, and then cross-triggers every other class whose reference events cover at least
+    ``cttc`` of it; a reference event is a true positive when the DTC-passing events of its class cover at least ``gtc``
+    of it.  Two HIP launches, no host sync; no cap on the length of a list on either side."""
+    if (events.B, events.C) != (reference.B, reference.C):
+        raise BsedError(f"intersection_counts_gpu: the events cover {events.B} clips x {events.C} classes, the reference "
+                        f"{reference.B} x {reference.C}")
+    S, B, C = events.S, events.B, events.C
+    dev = events.offsets.device
+    if out is None:
+        out = (torch.zeros((S, C, 4), device=dev, dtype=torch.int64), torch.zeros((S, C, C), device=dev, dtype=torch.int64))
+    elif len(out) != 2 or tuple(out[0].shape) != (S, C, 4) or tuple(out[1].shape) != (S, C, C):
+        raise BsedError(f"intersection_counts_gpu: out must be an (({S}, {C}, 4), ({S}, {C}, {C})) pair of tensors")
+    for name, v in (("dtc", dtc), ("gtc", gtc), ("cttc", cttc)):
+        if not 0.0 < float(v) <= 1.0:
+            raise BsedError(f"intersection_counts_gpu: {name} must lie in (0, 1], got {v!r}")
+    if S * B * C == 0:
+        return out
+    if events.total > events.seconds.shape[0] or events.offsets.numel() != S * B * C + 1:
+        raise BsedError(f"intersection_counts_gpu: the event lists hold {events.seconds.shape[0]} rows and "
+                        f"{events.offsets.numel()} offsets for {events.total} events in {S * B * C} groups")
+    ref_off, ref_sec = reference.device()
+    flags = torch.empty(events.seconds.shape[0], device=dev, dtype=torch.uint8)     # max(E, 1) bytes of scratch
+    L.call("bsed_intersection_counts", L.ptr(events.offsets, torch.int32), L.ptr(events.seconds, torch.float64),
+           L.ptr(ref_off, torch.int32), L.ptr(ref_sec, torch.float64), L.ptr(reference.device_evaluated(), torch.uint8),
+           S, B, C, float(dtc), float(gtc), float(cttc), L.ptr(flags, torch.uint8), L.ptr(out[0], torch.int64),
+           L.ptr(out[1], torch.int64), L.stream())
+    return out
+
+
+def _host_counts(a, last, who):
+    a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    if a.ndim < 2 or a.shape[-1] != last:
+        raise BsedError(f"{who}, got shape {a.shape}")
+    return a
+
+
+def intersection_f1(acc):
+    """(..., C, 4) integer counts (Ntp, Nfp, Nsys, Nref) -> dict of float64 numpy arrays: ``class_f1`` (..., C) and ``macro``
+    (...).  Per class F = 2 Ntp / (2 Ntp + Nfp + (Nref - Ntp)); F is NaN where Nref == 0 -- psds_eval's rule: a class
+    without reference events is left out of the average even when it is predicted.  That DIFFERS from ``event_f1``, whose
+    F is NaN only where the class neither occurs nor is predicted (and 0 where it is predicted but does not occur).
+    ``macro`` is the mean over the classes whose F is not NaN, summed in class order (NaN if there is none)."""
+    c = _host_counts(acc, 4, "intersection_f1 takes (..., C, 4) counts").astype(np.float64)
+    ntp, nfp, nref = c[..., 0], c[..., 1], c[..., 3]
+    class_f1 = np.divide(2.0 * ntp, 2.0 * ntp + nfp + (nref - ntp), out=np.full(ntp.shape, np.nan), where=nref > 0)
+    valid = ~np.isnan(class_f1)
+    n_valid = valid.sum(-1)
+    total = np.zeros(n_valid.shape)
+    for k in range(class_f1.shape[-1]):                 # summed in class order, so that the value is defined to the bit
+        total = total + np.where(valid[..., k], class_f1[..., k], 0.0)
+    return {"class_f1": class_f1, "macro": np.divide(total, n_valid, out=np.full(n_valid.shape, np.nan), where=n_valid > 0)}
+
+
+def psds_rates(acc, ct, ref_duration, total_duration):
+    """Counts -> dict of float64 rates, per hour where they are rates: ``tpr`` (S,C) = Ntp / Nref, NaN where Nref == 0;
+    ``fpr`` (S,C) = Nfp / total_duration * 3600; ``ctr`` (S,C,C) = ct[s,k,j] / ref_duration[k] * 3600, NaN where
+    ref_duration[k] == 0.  ``ref_duration`` (C): the summed length in seconds of every class's reference events over the
+    evaluated clips (``EventReference.class_durations``); ``total_duration``: the summed duration of the evaluated clips."""
+    a = _host_counts(acc, 4, "psds_rates takes (S, C, 4) counts").astype(np.float64)
+    x = _host_counts(ct, a.shape[-2], "psds_rates takes an (S, C, C) cross-trigger matrix").astype(np.float64)
+    dur = np.asarray(ref_duration, np.float64)
+    if a.ndim != 3 or x.shape != a.shape[:2] + (a.shape[1],) or dur.shape != (a.shape[1],):
+        raise BsedError(f"psds_rates: counts {a.shape}, cross triggers {x.shape} and durations {dur.shape} do not belong together")
+    tpr = np.divide(a[..., 0], a[..., 3], out=np.full(a.shape[:2], np.nan), where=a[..., 3] > 0)
+    fpr = a[..., 1] / float(total_duration) * 3600.0
+    per_k = np.broadcast_to(dur[None, :, None], x.shape)
+    ctr = np.divide(x, per_k, out=np.full(x.shape, np.nan), where=per_k != 0) * 3600.0
+    return {"tpr": tpr, "fpr": fpr, "ctr": ctr}
+
+
+class PsdsScore:
+    """``PsdsResult.psds``'s return value: ``value``, and the curve it is the area under: ``efpr`` (the axis up to
+    ``max_efpr``, per hour) and ``etpr`` (the effective true-positive rate held from each point to the next)"""
+
+    def __init__(self, value, efpr, etpr, alpha_ct, alpha_st, max_efpr):
+        self.value, self.efpr, self.etpr = float(value), efpr, etpr
+        self.alpha_ct, self.alpha_st, self.max_efpr = alpha_ct, alpha_st, max_efpr
+
+    def __repr__(self):
+        return f"PsdsScore(value={self.value:.5f}, alpha_ct={self.alpha_ct}, alpha_st={self.alpha_st}, max_efpr={self.max_efpr})"
+
+
+def psds_from_rates(tpr, efpr, alpha_st=0.0, max_efpr=100.0):
+    """(S,C) true-positive rates and effective false-positive rates of S operating points -> ``(value, axis, curve)``.
+    Per class the points are ordered by (efpr, tpr) and tpr replaced by its running maximum; on the union of all finite
+    efpr values each class curve holds its previous value (a left-held step, 0 before the class's first point; a class
+    whose tpr is NaN -- no reference event -- is NaN throughout); across classes ``nanmean - alpha_st * nanstd`` (ddof 0);
+    ``max_efpr`` is inserted into the axis with the held value if absent; the area is ``sum(diff(x) * y[:-1])`` over
+    ``x <= max_efpr``, divided by ``max_efpr``."""
+    tpr, efpr = np.asarray(tpr, np.float64), np.asarray(efpr, np.float64)
+    if tpr.ndim != 2 or tpr.shape != efpr.shape:
+        raise BsedError(f"psds_from_rates takes (S, C) tpr and efpr, got {tpr.shape} and {efpr.shape}")
+    if not max_efpr > 0:
+        raise BsedError(f"psds_from_rates: max_efpr must be positive, got {max_efpr!r}")
+    S, C = tpr.shape
+    axis = np.unique(np.concatenate([efpr[np.isfinite(efpr)], [float(max_efpr)]]))
+    axis = axis[axis <= max_efpr]
+    curves = np.full((C, len(axis)), np.nan)
+    for c in range(C):
+        if np.isnan(tpr[:, c]).any():
+            continue
+        ok = np.isfinite(efpr[:, c])
+        curves[c] = 0.0
+        if not ok.any():
+            continue
+        x, y = efpr[ok, c], tpr[ok, c]
+        order = np.lexsort((y, x))
+        x, y = x[order], np.maximum.accumulate(y[order])
+        at = np.searchsorted(x, axis, side="right") - 1         # the last point with efpr <= the axis value
+        curves[c] = np.where(at >= 0, y[np.maximum(at, 0)], 0.0)
+    live = ~np.isnan(curves).all(1)
+    if not live.any():
+        return float("nan"), axis, np.full(len(axis), np.nan)
+    curve = curves[live].mean(0) - alpha_st * curves[live].std(0)
+    return float(np.sum(np.diff(axis) * curve[:-1]) / max_efpr), axis, curve
+
+
+class PsdsResult:
+    """The intersection-based result of S operating points (thresholds): ``counts`` (S,C,4) int64 numpy (Ntp, Nfp, Nsys,
+    Nref), ``ct`` (S,C,C) int64 cross triggers [reference class][estimated class], ``class_f1`` (S,C) / ``macro_f1`` (S)
+    (``intersection_f1``), ``tpr`` / ``fpr`` (S,C) and ``ctr`` (S,C,C) (``psds_rates``), ``ref_duration`` (C),
+    ``total_duration``, ``criteria`` = (dtc, gtc, cttc), ``labels``, ``thresholds``.  ``psds(alpha_ct, alpha_st, max_efpr)``
+    is psds_eval's score as this project states it (include/bsed.h; parity with psds_eval not pinned)."""
+
+    def __init__(self, counts, ct, ref_duration, total_duration, labels=None, thresholds=None, criteria=(0.5, 0.5, 0.3)):
+        self.counts = _host_counts(counts, 4, "PsdsResult takes (S, C, 4) counts").astype(np.int64)
+        self.ct = _host_counts(ct, self.counts.shape[-2], "PsdsResult takes an (S, C, C) cross-trigger matrix").astype(np.int64)
+        self.ref_duration = np.asarray(ref_duration, np.float64)
+        self.total_duration = float("nan") if total_duration is None else float(total_duration)
+        self.labels = None if labels is None else list(labels)
+        self.thresholds = None if thresholds is None else list(thresholds)
+        self.criteria = tuple(criteria)
+        f = intersection_f1(self.counts)
+        self.class_f1, self.macro_f1 = f["class_f1"], f["macro"]
+        r = psds_rates(self.counts, self.ct, self.ref_duration, self.total_duration)
+        self.tpr, self.fpr, self.ctr = r["tpr"], r["fpr"], r["ctr"]
+
+    def efpr(self, alpha_ct=0.0):
+        """(S,C) effective false-positive rate: ``fpr[s,c] + alpha_ct * (mean over k != c of ctr[s,k,c])``, the mean over
+        the classes k whose rate is not NaN, summed in class order; the term is left out when ``alpha_ct == 0`` and
+        where no other class has a rate (one class, or no other class with reference events)"""
+        if alpha_ct == 0:
+            return self.fpr.copy()
+        S, C = self.fpr.shape
+        total, n = np.zeros((S, C)), np.zeros((S, C))
+        for k in range(C):
+            use = ~np.isnan(self.ctr[:, k, :])
+            use[:, k] = False
+            total, n = total + np.where(use, self.ctr[:, k, :], 0.0), n + use
+        return self.fpr + np.where(n > 0, alpha_ct * (total / np.maximum(n, 1)), 0.0)
+
+    def psds(self, alpha_ct=0, alpha_st=0, max_efpr=100):
+        """-> ``PsdsScore`` with ``.value``, ``.efpr`` and ``.etpr`` (``psds_from_rates`` on ``tpr`` and ``efpr(alpha_ct)``)"""
+        if not np.isfinite(self.total_duration) or self.total_duration <= 0:
+            raise BsedError("PsdsResult.psds: the false-positive rates need the total duration of the evaluated audio")
+        value, axis, curve = psds_from_rates(self.tpr, self.efpr(alpha_ct), alpha_st, max_efpr)
+        return PsdsScore(value, axis, curve, alpha_ct, alpha_st, max_efpr)
+
+
+def _frame_lists(dfs, labels, names, who):
+    """prediction frames (one per operating point; event_label / onset / offset / filename) -> ``EventLists`` over
+    ``names`` x ``labels``: rows grouped by (clip, class) in frame order; rows of other files are ignored, rows with a
+    NaN time dropped, a label outside ``labels`` raises"""
+    index = {n: i for i, n in enumerate(names)}
+    B, C = len(names), len(labels)
+    counts, secs = np.zeros((len(dfs), B, C), np.int64), []
+    for s, df in enumerate(dfs):
+        if df is None or len(df) == 0:
+            continue
+        clip = np.asarray([index.get(f, -1) for f in df["filename"]], np.int64)
+        k, on, off, keep, bad = _event_table(df, labels, False, clip >= 0)
+        if bad is not None:
+            raise BsedError(f"{who}: estimated event label {df['event_label'].iloc[bad]!r} is not in the label list")
+        group = (clip * C + k)[keep]
+        order = np.argsort(group, kind="stable")
+        counts[s] = np.bincount(group, minlength=B * C).reshape(B, C)
+        secs.append(np.stack([on[keep][order], off[keep][order]], 1))
+    return EventLists.from_host(counts, np.concatenate(secs) if secs else np.zeros((0, 2)))
+
+
+def _meta_names(groundtruth_df, meta_df):
+    """the clips of a scoring call: the files of ``meta_df`` in order, else those of the ground truth -> (names, durations)"""
+    if meta_df is not None and len(meta_df):
+        names = list(dict.fromkeys(meta_df["filename"]))
+        first = meta_df.drop_duplicates("filename").set_index("filename")["duration"]
+        return names, np.asarray([float(first[n]) for n in names], np.float64)
+    if groundtruth_df is None or len(groundtruth_df) == 0:
+        raise BsedError("scoring needs the files of meta_df (filename / duration) or a ground truth")
+    names = list(dict.fromkeys(groundtruth_df["filename"]))
+    return names, np.full(len(names), np.nan)
+
+
+def compute_psds_from_operating_points(list_predictions, groundtruth_df, meta_df, labels, dtc_threshold=0.5,
+                                       gtc_threshold=0.5, cttc_threshold=0.3):
+    """The reference's call (src/evaluation_measures.py:505-510) without psds_eval: one prediction frame per operating
+    point + ground truth + ``meta_df`` (filename / duration) -> ``PsdsResult``, whose ``.psds(alpha_ct, alpha_st,
+    max_efpr).value`` is what ``psds_score`` prints.  ``labels``: the class list (psds_eval takes it from the ground
+    truth).  Files of ``meta_df`` without a row in the ground truth are not evaluated and do not count in the duration."""
+    dfs = list(list_predictions) if isinstance(list_predictions, (list, tuple)) else [list_predictions]
+    names, durations = _meta_names(groundtruth_df, meta_df)
+    reference = EventReference.from_frame(groundtruth_df, labels, names)
+    events = _frame_lists(dfs, list(labels), names, "compute_psds_from_operating_points")
+    criteria = (float(dtc_threshold), float(gtc_threshold), float(cttc_threshold))
+    acc, ct = intersection_counts_gpu(events, reference, *criteria)
+    total = float(np.cumsum(durations[reference.evaluated])[-1]) if reference.evaluated.any() else 0.0
+    return PsdsResult(acc, ct, reference.class_durations(), total, labels, None, criteria)
+
+
+def compute_metrics(predictions, gtruth_df, meta_df, labels):
+    """The reference's per-epoch scoring (src/evaluation_measures.py:518-526) on DataFrames -> ``(ct_matrix, macro_f1_event,
+    psds_macro_f1)``: the (C,C) int64 cross-trigger matrix [reference class][estimated class] at (dtc, gtc, cttc) =
+    (0.5, 0.5, 0.3) (psds_eval's has one more row and column, for its "world" label), the collar-based macro event F1
+    (``event_counts_gpu`` / ``event_f1``: t_collar 0.2 s, 20 % of the length) and the intersection-based macro F1
+    (``intersection_f1``), both counted on the GPU."""
+    names, _ = _meta_names(gtruth_df, meta_df)
+    reference = EventReference.from_frame(gtruth_df, labels, names)
+    events = _frame_lists([predictions], list(labels), names, "compute_metrics")
+    macro_f1_event = float(event_f1(event_counts_gpu(events, reference))["macro"][0])
+    acc, ct = intersection_counts_gpu(events, reference)
+    return ct[0].cpu().numpy(), macro_f1_event, float(intersection_f1(acc)["macro"][0])
+
+
 class ValidationResult:
     """``validate``'s return value: ``thresholds`` (list), ``counts`` (S,C,3) int64 numpy (Ntp, Nsys, Nref), ``class_f1``
     (S,C), ``macro_f1`` / ``micro_f1`` (S), ``best_index`` / ``best_threshold`` (highest macro F, ties to the lowest
     threshold; NaN counts as lowest), ``labels``, and -- on request -- ``predictions`` (one DataFrame per threshold) and
     ``groundtruth_df``; ``tagging``: the ``TaggingResult`` of the same pass when ``validate`` was given
-    ``tagging_thresholds``, else None."""
+    ``tagging_thresholds``, else None; ``intersection``: the ``PsdsResult`` of the same pass when ``validate`` was given
+    ``intersection``, else None."""
 
-    def __init__(self, thresholds, counts, labels, predictions=None, groundtruth_df=None, tagging=None):
+    def __init__(self, thresholds, counts, labels, predictions=None, groundtruth_df=None, tagging=None, intersection=None):
         self.thresholds, self.counts, self.labels = list(thresholds), counts, list(labels)
         f = event_f1(counts)
         self.class_f1, self.macro_f1, self.micro_f1 = f["class_f1"], f["macro"], f["micro"]
@@ -771,12 +1042,13 @@ class ValidationResult:
         self.best_macro_f1 = float(self.macro_f1[self.best_index])
         self.predictions, self.groundtruth_df = predictions, groundtruth_df
         self.tagging = tagging
+        self.intersection = intersection
 
 
 def validate(model, dataloader, decoder, predictor=None, fpn=False, thresholds=(0.5,), median_window=1, learned_post=False,
              t_collar=0.2, percentage_of_length=0.2, pooling_time_ratio=1, sr=32000, hop_size=255, max_len_seconds=10.0,
              classwise_median_window=None, return_predictions=False, require_annotations=False, ignore_unknown=False,
-             tagging_thresholds=None):
+             tagging_thresholds=None, intersection=None):
     """One validation pass, scored on the GPU: the eval-mode forward of ``get_predictions`` (same ``dataloader``, ``decoder``,
     ``predictor`` / ``fpn`` forms and the same ``annotation/<name>.txt`` files), every batch swept over ALL ``thresholds``
     (``sweep_events_gpu``: one host sync per batch) and matched against its reference (``event_counts_gpu``), the counts
@@ -786,9 +1058,16 @@ def validate(model, dataloader, decoder, predictor=None, fpn=False, thresholds=(
     only with ``return_predictions``.  A clip name may occur once per pass.  Training flags are restored on exit.
     ``tagging_thresholds`` (opt-in): the weak output of the same forward is scored against the loader's own targets over
     these thresholds (``tag_counts_gpu``, one more launch per batch) and the ``TaggingResult`` hangs on ``.tagging``; with
-    the default None the pass launches and returns what it did without the argument."""
+    the default None the pass launches and returns what it did without the argument.
+    ``intersection`` (opt-in): True, or a ``(dtc, gtc, cttc)`` tuple (True = (0.5, 0.5, 0.3)): the same event lists are also
+    scored by the intersection criteria (``intersection_counts_gpu``, one more call per batch, accumulated on the device
+    and read once at the end) and the ``PsdsResult`` -- counts, cross-trigger matrix, class and macro intersection F1 per
+    threshold, ``.psds(...)`` over the thresholds as operating points -- hangs on ``.intersection``; every evaluated clip
+    counts ``max_len_seconds`` in the total duration.  With None the pass launches and returns what it did without it."""
     import pandas as pd
     _check_form("validate", predictor, fpn)
+    criteria = None if intersection is None or intersection is False else _criteria(intersection, "validate")
+    isect_acc, ref_duration, n_evaluated = None, None, 0
     labels = _encoder_labels(decoder, "decode_strong")
     if labels is None:
         raise BsedError("validate decodes and scores on the GPU and needs the label list: pass the bound decode_strong of a "
@@ -821,6 +1100,11 @@ def validate(model, dataloader, decoder, predictor=None, fpn=False, thresholds=(
             reference = EventReference.from_frame(pd.concat(dfs, ignore_index=True) if dfs else None, labels[:C], names,
                                                   ignore_unknown)
             event_counts_gpu(events, reference, t_collar, percentage_of_length, out=acc)
+            if criteria is not None:
+                isect_acc = intersection_counts_gpu(events, reference, *criteria, out=isect_acc)
+                durations = reference.class_durations()
+                ref_duration = durations if ref_duration is None else ref_duration + durations
+                n_evaluated += int(reference.evaluated.sum())
             if return_predictions:
                 gts += dfs
                 for s, df in enumerate(events.frames(labels, names)):
@@ -832,7 +1116,11 @@ def validate(model, dataloader, decoder, predictor=None, fpn=False, thresholds=(
         predictions = [pd.concat(f, ignore_index=True)[_EVENT_COLUMNS] for f in frames]
         groundtruth_df = pd.concat(gts, ignore_index=True) if gts else None
     tagging = None if tag_thr is None else TaggingResult(tag_thr.host, tag_acc.cpu().numpy(), labels[:tag_acc.shape[1]])
-    return ValidationResult(thresholds, acc.cpu().numpy(), labels[:acc.shape[1]], predictions, groundtruth_df, tagging)
+    isect = None
+    if criteria is not None:
+        isect = PsdsResult(isect_acc[0], isect_acc[1], ref_duration, n_evaluated * float(max_len_seconds),
+                           labels[:acc.shape[1]], thresholds, criteria)
+    return ValidationResult(thresholds, acc.cpu().numpy(), labels[:acc.shape[1]], predictions, groundtruth_df, tagging, isect)
 
 
 _SEGMENT_SLACK = 1e-6       # seconds; far above the rounding of second-valued float64 differences, far below any collar
@@ -892,17 +1180,32 @@ def recording_problem(events_df, groundtruth_df, labels, t_collar=0.2, ignore_un
     return counts, np.concatenate(secs) if secs else np.zeros((0, 2)), reference
 
 
-def score_recording(events_df, groundtruth_df, labels, t_collar=0.2, percentage_of_length=0.2, ignore_unknown=False):
+def score_recording(events_df, groundtruth_df, labels, t_collar=0.2, percentage_of_length=0.2, ignore_unknown=False,
+                    intersection=None, duration=None):
     """The event counts of ``validate`` for ONE recording: ``events_df`` is what ``detect_recording`` returns (a DataFrame,
     or a list of them, one per threshold), ``groundtruth_df`` has onset / offset / event_label rows in seconds of the
     recording (rows with NaN are dropped).  Returns the (S,C,3) int64 numpy counts (Ntp, Nsys, Nref); ``event_f1`` turns
     them into F1.  The match kernel works on lists of at most 64 reference events, so each class's time line is first
     cut where two neighbouring reference onsets lie more than ``2 * t_collar`` apart (``recording_problem``); the cap that
     remains: at most 64 reference events of one class in a run whose neighbouring onsets all lie within ``2 * t_collar``.
-    The estimated lists have no cap."""
+    The estimated lists have no cap.
+    ``intersection`` (opt-in, as for ``validate``): True or a ``(dtc, gtc, cttc)`` tuple returns ``(counts, PsdsResult)``
+    instead: the recording scored as ONE clip by the intersection criteria (``intersection_counts_gpu``; no pieces and no
+    cap: nothing is matched), each estimated list in the order of its frame, the reference sorted by onset.  ``duration``:
+    the recording's length in seconds, which only ``PsdsResult.psds`` and the false-positive rates need."""
     counts, seconds, reference = recording_problem(events_df, groundtruth_df, labels, t_collar, ignore_unknown)
     events = EventLists.from_host(counts, seconds)
-    return event_counts_gpu(events, reference, t_collar, percentage_of_length).cpu().numpy()
+    event_counts = event_counts_gpu(events, reference, t_collar, percentage_of_length).cpu().numpy()
+    if intersection is None or intersection is False:
+        return event_counts
+    criteria = _criteria(intersection, "score_recording")
+    labels = list(labels)
+    dfs = [df.assign(filename="recording") for df in (events_df if isinstance(events_df, (list, tuple)) else [events_df])]
+    gt = None if groundtruth_df is None or len(groundtruth_df) == 0 else groundtruth_df.assign(filename="recording")
+    whole = EventReference.from_frame(gt, labels, ["recording"], ignore_unknown)
+    whole.evaluated[:] = True                           # a recording without a reference event is still scored
+    acc, ct = intersection_counts_gpu(_frame_lists(dfs, labels, ["recording"], "score_recording"), whole, *criteria)
+    return event_counts, PsdsResult(acc, ct, whole.class_durations(), duration, labels, None, criteria)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -600,6 +600,40 @@ int bsed_event_match(const int* est_offsets, const double* est_seconds, const in
                      int S, int B, int C, double t_collar, double percentage_of_length, long long* acc, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Intersection-based counts (csrc/intersect.hip, ABI 13): what psds_eval's macro F1 with a cross-trigger matrix
+ * (PSDSEval(0.5, 0.5, 0.3).compute_macro_f_score, reference src/evaluation_measures.py:518-526) and its PSDS
+ * (:287-316, :505-510) are computed from.  psds_eval is not installed where this project is developed: the rules below
+ * are psds_eval's AS THIS PROJECT STATES THEM, parity with psds_eval not pinned; the integer counts are the primary
+ * result, the F1 / rates / PSDS arithmetic on them is float64 numpy on the host (evaluation.py).
+ *
+ * Everything is per (threshold s, clip b) over C classes; est[s][b][j] and ref[b][k] are the lists of the layout of
+ * bsed_event_match (est_offsets (S*B*C + 1), est_seconds (E,2), ref_offsets (B*C + 1), ref_seconds (R,2), float64
+ * [onset, offset], list order).  The totals E and R are read from the offsets on the device.
+ *   pair intersection   it = fmin(off_e, off_r) - fmax(on_e, on_r); a pair counts only when it > 0, so touching or
+ *                       zero-length events contribute nothing and nothing divides by zero
+ *   pair ratios         det_precision = it / (off_e - on_e),   gt_coverage = it / (off_r - on_r)
+ * All sums are float64, sequential, left to right in the list order of the OTHER side, one division per pair; a host that
+ * loops the same way gets the same bits, so the counts are compared with ==, no tolerance.
+ *   DTC   an estimated event of class j passes when the sum of det_precision over ref[b][j] is >= dtc
+ *   GTC   a reference event of class k is a true positive when the sum of gt_coverage over the DTC-PASSING events of
+ *         est[s][b][k] is >= gtc (a failing detection adds no coverage)
+ *   FP    an estimated event that fails DTC is a false positive of its class (a passing one is neither TP nor FP)
+ *   CTTC  a DTC-FAILING estimated event of class j and every class k != j: when the sum of its det_precision over
+ *         ref[b][k] is >= cttc, ct[k][j] += 1 -- once per (event, k), however many reference events contributed; a
+ *         DTC-passing event never cross-triggers
+ * evaluated: (B) uint8 on the device, or NULL = every clip; a clip with evaluated[b] == 0 is skipped whole, both sides.
+ * Outputs, integer atomics, persistent across calls (zero them first), two runs give the same bits:
+ *   acc (S,C,4) int64 += (Ntp, Nfp, Nsys, Nref);   ct (S,C,C) int64, [reference class k][estimated class j], zero diagonal.
+ * dtc_flags: caller-owned scratch of max(E, 1) bytes (1 = the event passed DTC), written by the first launch and read by
+ * the second.  No cap on the length of a list on either side (no matching is involved); lists may overlap and need not
+ * come from bsed_sweep_write.  Two launches, no host sync.  Refused before any launch: null pointers (evaluated may be
+ * NULL), non-positive S, B or C, dtc / gtc / cttc outside (0, 1], S*C*C or S*B*C beyond int32.
+ * ---------------------------------------------------------------------------------------------- */
+int bsed_intersection_counts(const int* est_offsets, const double* est_seconds, const int* ref_offsets,
+                             const double* ref_seconds, const uint8_t* evaluated, int S, int B, int C, double dtc,
+                             double gtc, double cttc, uint8_t* dtc_flags, long long* acc, long long* ct, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Clip-level tagging (csrc/tagging.hip, ABI 7): the counts behind the reference's per-class weak F1
  * (get_f_measure_by_class, src/evaluation_measures.py:346-427, intermediate_at_measures :430-446) for a whole threshold
  * sweep, and the pseudo weak labels of a batch (src/audio_tagging_inference.py:289-316).
