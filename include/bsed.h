@@ -604,7 +604,7 @@ int bsed_event_match(const int* est_offsets, const double* est_seconds, const in
  * (PSDSEval(0.5, 0.5, 0.3).compute_macro_f_score, reference src/evaluation_measures.py:518-526) and its PSDS
  * (:287-316, :505-510) are computed from.  psds_eval is not installed where this project is developed: the rules below
  * are psds_eval's AS THIS PROJECT STATES THEM, parity with psds_eval not pinned; the integer counts are the primary
- * result, the F1 / rates / PSDS arithmetic on them is float64 numpy on the host (evaluation.py).
+ * result, the F1 / rates / PSDS arithmetic on them is float64 numpy on the host (evaluation/intersection.py).
  *
  * Everything is per (threshold s, clip b) over C classes; est[s][b][j] and ref[b][k] are the lists of the layout of
  * bsed_event_match (est_offsets (S*B*C + 1), est_seconds (E,2), ref_offsets (B*C + 1), ref_seconds (R,2), float64

@@ -6,7 +6,8 @@ import pytest
 import torch
 
 from bsed_amd._lib import BsedError
-from bsed_amd.evaluation import _eval_mode, _event_frame, _event_table, _read_annotations
+from bsed_amd.evaluation._common import _eval_mode, _event_frame, _read_annotations
+from bsed_amd.evaluation.events import _event_table
 
 
 def test_annotation_reader_on_a_tree_of_five_clips(tmp_path):
