@@ -197,57 +197,6 @@ __global__ __launch_bounds__(NW * 64) void wgrad_kernel(const WgradParams P) {
 // Rows of 32 channels are 64-byte chunks; a fragment read touches 4 consecutive patch columns of one chunk, so the
 // chunk index is XOR-swizzled with the patch COLUMN (invariant under row steps): 4 columns x 64 B tile the 64 banks.
 // ---------------------------------------------------------------------------------------------
-typedef short w3_bf16x8 __attribute__((ext_vector_type(8)));
-typedef short w3_bf16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) unsigned short w3_lds_u16;
-typedef __attribute__((address_space(3))) w3_bf16x4 w3_lds_v4;
-typedef uint32_t w3_u32x2 __attribute__((ext_vector_type(2)));
-typedef float w3_f32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) w3_u32x2 w3_lds_u2;
-
-// physical 32-channel chunk of logical chunk `ch` in the row of position / patch column pc (nch = chunks per row: 1, 2
-// or 4): 4 consecutive pc x 64 B then tile the 64 banks
-__device__ __forceinline__ int w3_chunk(int ch, int pc, int nch) {
-  return ch ^ ((nch == 2 ? (pc >> 1) : pc) & (nch - 1));
-}
-
-// 8 consecutive positions of this lane's channel: two transposing reads of 4 rows each.  a0 / a1 are LDS BYTE
-// addresses (plane base included, so that no base add is left in the K loop)
-__device__ __forceinline__ w3_bf16x8 w3_frag(uint32_t a0, uint32_t a1) {
-  const w3_bf16x4 u = __builtin_amdgcn_ds_read_tr16_b64_v4i16((w3_lds_v4*)(uintptr_t)a0);
-  const w3_bf16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((w3_lds_v4*)(uintptr_t)a1);
-  return __builtin_shufflevector(u, v, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-
-// 4 channels of one position -> the two planes (ABF, the bf16 mode: the hi plane alone)
-template <int ABF = 0>
-__device__ __forceinline__ void w3_store4(w3_lds_u16* hi_plane, w3_lds_u16* lo_plane, int o, const float4& v) {
-  w3_u32x2 hi, lo;
-  uint32_t h0, l0, h1, l1;
-  bsed_split2(v.x, v.y, h0, l0);
-  bsed_split2(v.z, v.w, h1, l1);
-  hi[0] = h0; hi[1] = h1; lo[0] = l0; lo[1] = l1;
-  *(w3_lds_u2*)(hi_plane + o) = hi;
-  if (!ABF) *(w3_lds_u2*)(lo_plane + o) = lo;
-}
-// activation loads / stores through a pointer computed in ELEMENTS from the tensor base (ABF: the tensor is bf16)
-template <int ABF> __device__ __forceinline__ float4 w3_ld4(const float* base, const float* q) {
-  const f32x4 t = act_ld4<ABF>(base, (size_t)(q - base));
-  return make_float4(t[0], t[1], t[2], t[3]);
-}
-template <int ABF> __device__ __forceinline__ void w3_st4(float* base, float* q, const float4& v) {
-  act_st4<ABF>(base, (size_t)(q - base), f32x4{v.x, v.y, v.z, v.w});
-}
-template <int ABF>
-__device__ __forceinline__ f32x16 w3_mfma(const w3_bf16x8& a_hi, const w3_bf16x8& a_lo, const w3_bf16x8& b_hi,
-                                          const w3_bf16x8& b_lo, f32x16 acc) {
-  if (!ABF) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_lo, b_hi, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_hi, b_lo, acc, 0, 0, 0);
-  }
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_hi, b_hi, acc, 0, 0, 0);
-}
-
 // the 1- and 2-slot 4-wave forms (conv1 16 -> 32 channels: 39 KB of LDS) are pinned to 128 registers so that FOUR
 // workgroups share a CU: 0.753 (three, 136 registers) -> 0.651 ms, 4.9 TB/s
 #define W3_WPE(MAXS, NW) ((MAXS) <= 2 && (NW) == 4 ? 4 : 2)

@@ -172,6 +172,7 @@ class CRNN(_FlatModule):
         self.n_hidden = n_RNN_cell
         self.seed = 0
         self.fused_glu_bwd = True  # False = the unfused 4-launch chain (kept as a cross-check in the tests)
+        self.fused_conv_bwd = True  # False = never the one-pass conv backward (ops.conv_bn_backward): its two kernels
         # GRU weight gradients of layer l on a side stream, beside the (latency-bound, half-chip) recurrence of layer
         # l-1: -0.26 ms per step at B = 256 (14.07 -> 13.81 ms), bitwise identical results (tests/test_fullsize_gpu.py).
         # The overlapped 1-tap weight gradients are stretched by the recurrence they share the chip with (0.076 ->
@@ -473,18 +474,16 @@ class CRNN(_FlatModule):
             # which also writes d_y once for the data gradient: the separate apply pass over g and y is gone
             coef = ops.bn_bwd(st2, co, float(B * Hh * Ww), bn.weight, blk["mean"], blk["invstd"], bn.weight.grad,
                               bn.bias.grad, g, y, apply=False)
-            dy = torch.empty_like(g) if need_dgrad else None
-            ops.weight_grad(blk["inp"], g, wv.over(cw.grad), B, Hh, Ww, mode=self.conv_mode, bn_y=y, bn_coef=coef,
-                            bn_mean=blk["mean"], dy_out=dy)
-        else:
-            # (4) BatchNorm backward -> d_y in place
-            ops.bn_bwd(st2, co, float(B * Hh * Ww), bn.weight, blk["mean"], blk["invstd"], bn.weight.grad,
-                       bn.bias.grad, g, y)
-            dy = g
-            ops.weight_grad(blk["inp"], dy, wv.over(cw.grad), B, Hh, Ww, mode=self.conv_mode)
+            # ... and where that pass is HBM-bound, the data gradient comes out of it as well (ops.conv_bn_backward)
+            return ops.conv_bn_backward(blk["inp"], g, y, coef, blk["mean"], wv, wv.over(cw.grad), B, Hh, Ww,
+                                        mode=self.conv_mode, need_dgrad=need_dgrad,
+                                        fused=None if self.fused_conv_bwd else False)
+        # (4) BatchNorm backward -> d_y in place
+        ops.bn_bwd(st2, co, float(B * Hh * Ww), bn.weight, blk["mean"], blk["invstd"], bn.weight.grad, bn.bias.grad, g, y)
+        ops.weight_grad(blk["inp"], g, wv.over(cw.grad), B, Hh, Ww, mode=self.conv_mode)
         if not need_dgrad:
             return None
-        return ops.contract(dy, wv, B, Hh, Ww, mode=self.conv_mode, direction="dgrad")[0]
+        return ops.contract(g, wv, B, Hh, Ww, mode=self.conv_mode, direction="dgrad")[0]
 
     def _cnn_forward(self, x, ctx):
         """the seven conv/BN/GLU/dropout/pool blocks; returns (a (B,T',1,C), T')"""

@@ -614,6 +614,73 @@ def weight_grad(inp, dy, gv, NB, H, W, *, mode, accumulate=True, defer=True, **k
                     dst_offset=gv.offset, defer=defer)
 
 
+def _conv_bwd_desc(NB, H, W, CIN, N, act_bf16=0):
+    """the shape fields of bsed_conv_bwd3's descriptor: a 3x3 / pad 1 convolution of CIN -> N channels with dense rows"""
+    d = WgradDesc()
+    _tile_taps(d, H, W, TAPS3x3)
+    d.NB, d.H, d.W, d.CIN, d.CINP, d.N, d.NP = NB, H, W, CIN, round_up(CIN, 32), N, round_up(N, 32)
+    d.in_pitch, d.dy_pitch, d.din_pitch, d.act_bf16 = CIN, N, CIN, act_bf16
+    return d
+
+
+def conv_bwd_plan(NB, H, W, CIN, N, act_bf16=0):
+    """(descriptor, BsedContractPlan) of the one-pass backward kernel (bsed_conv_bwd3) for a 3x3 convolution under a
+    BatchNorm, or (descriptor, None) where the kernel does not take the shape (L.last_error() says why).  plan.G = 0:
+    the kernel takes it, but the library keeps the layer on its two kernels (bsed_conv_bwd_plan's rule)."""
+    d = _conv_bwd_desc(NB, H, W, CIN, N, act_bf16)
+    plan = ContractPlan()
+    if L.lib().bsed_conv_bwd_plan(ctypes.byref(d), ctypes.byref(plan)) != 0:
+        return d, None
+    return d, plan
+
+
+def conv_bwd_fused(inp, g, y, coef, mean, wv, NB, H, W, G=None):
+    """One pass over inp, g and y (csrc/conv_bwd.hip): BatchNorm backward on load, the partial slabs of the weight gradient
+    AND the data gradient, d_y never written.  wv: the layer's forward WeightView.  G: number of partial slabs (default:
+    the plan's; the kernel takes any 1..max_G).  Returns (d_in, part, G, CINP, NP); raises where the kernel does not take
+    the shape."""
+    CIN, N = wv.K, wv.N
+    d, plan = conv_bwd_plan(NB, H, W, CIN, N, _abf(inp, g, y))
+    if plan is None or wv.taps != tuple(TAPS3x3):
+        raise L.BsedError("conv_bwd_fused: " + (L.lib().bsed_last_error().decode() if plan is None else "3x3 taps only"))
+    G = G or plan.G or min(256, plan.max_G)
+    tv = wv.dgrad()
+    wtab = pack_weight3s(tv.source(), 9, tv.N, tv.s_tap, tv.s_k, tv.s_n, K=tv.K)
+    d_in = torch.empty((NB, H, W, CIN), device=inp.device, dtype=torch.float32)
+    part = torch.empty((G, 9, d.CINP, d.NP), device=inp.device, dtype=torch.float32)
+    d.in_ = _dp(inp); d.dy = _dp(g); d.part = _p(part); d.G = G
+    d.bn_y, d.bn_coef, d.bn_mean = _dp(y), _p(coef), _p(mean)
+    d.w3s, d.d_in = wtab.data_ptr(), _p(d_in)
+    # algorithmic work: both contractions; inp, g and y read once, d_in written once
+    _launch((plan.label.decode(), 9, CIN, N, H, W), 2 * 2.0 * NB * H * W * 9 * CIN * N,
+            lambda: L.call("bsed_conv_bwd3", ctypes.byref(d), L.stream()), 4.0 * NB * H * W * (2 * CIN + 2 * N))
+    return d_in, part, G, d.CINP, d.NP
+
+
+def conv_bn_backward(inp, g, y, coef, mean, wv, gv, NB, H, W, *, mode, need_dgrad=True, fused=None):
+    """Backward of a 3x3 convolution whose output feeds a train-mode BatchNorm, in the split-fp32 modes: g = dL/d(BatchNorm
+    output), y = the convolution's output, coef / mean from bn_bwd(apply=False).  dW is reduced into gv; returns dL/d(inp)
+    (None without need_dgrad).  fused: None = bsed_conv_bwd_plan decides between the one-pass kernel and the two kernels
+    it replaces (weight gradient writing d_y, data gradient reading it back); False = the two kernels; True = the one-pass
+    kernel or an error."""
+    use = False
+    if fused is not False and need_dgrad and mode == "bf16x3":
+        plan = conv_bwd_plan(NB, H, W, wv.K, wv.N, _abf(inp, g, y))[1]
+        use = plan is not None and wv.taps == tuple(TAPS3x3) and (fused is True or plan.G > 0)
+    if fused is True and not use:
+        raise L.BsedError("conv_bn_backward: the one-pass kernel does not take this layer: " +
+                          L.lib().bsed_last_error().decode())
+    if use:
+        d_in, part, G, KP, NP = conv_bwd_fused(inp, g, y, coef, mean, wv, NB, H, W)
+        reduce_partials(part, G, 9, KP, NP, gv.K, gv.N, gv.tensor, gv.s_tap, gv.s_k, gv.s_n, dst_offset=gv.offset)
+        return d_in
+    dy = torch.empty_like(g) if need_dgrad else None
+    weight_grad(inp, g, gv, NB, H, W, mode=mode, bn_y=y, bn_coef=coef, bn_mean=mean, dy_out=dy)
+    if not need_dgrad:
+        return None
+    return contract(dy, wv, NB, H, W, mode=mode, direction="dgrad")[0]
+
+
 _scratch = {}
 
 

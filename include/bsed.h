@@ -231,6 +231,10 @@ typedef struct BsedWgradDesc {
   float* dy_out;
   int act_bf16;          /* bsed_wgrad3: 1 = in, dy, bn_y and dy_out are bf16 tensors ("bf16" mode: one bf16 MFMA per product,
                           * the BatchNorm-backward map and the accumulation in fp32); 0 = fp32 */
+  /* bsed_conv_bwd3 only (ABI 14; the other entry points ignore the three): the data gradient of the same convolution */
+  const void* w3s;       /* bsed_pack_weight3s table of the TRANSPOSED weight (K = N, N = CIN, the layer's nine taps) */
+  float* d_in;           /* (NB,H,W,din_pitch): dL/d(in) */
+  int din_pitch;
 } BsedWgradDesc;
 
 /* BsedContractPlan of bsed_wgrad (BSED_CONTRACT_WGRAD) / bsed_wgrad3 (BSED_CONTRACT_WGRAD3): G = the recommended number
@@ -243,6 +247,20 @@ int bsed_wgrad(const BsedWgradDesc* desc /*host*/, void* stream);
  * partial-slab layout; G should come from bsed_wgrad_plan (the recommendation differs between the kernels).
  * BSED_WGRAD3_NOPIPE=1 in the environment forces wgrad3_kernel (tests). */
 int bsed_wgrad3(const BsedWgradDesc* desc /*host*/, void* stream);
+/* Both gradients of a 3 x 3 / pad 1 convolution under a train-mode BatchNorm in ONE pass (ABI 14; csrc/conv_bwd.hip;
+ * nn.Conv2d + nn.BatchNorm2d backward, reference src/models/CNN.py:46-49): the partial slabs of bsed_wgrad3 with BatchNorm
+ * backward applied on load (bn_y, bn_coef, bn_mean required) AND d_in = conv^T(d_y, w) -- what bsed_wgrad3 with dy_out
+ * followed by bsed_igemm3n computes -- without d_y ever leaving the chip: a persistent producer / consumer workgroup per
+ * CU forms d_y for a 128-position tile plus its one-position ring (zeros outside the image) in LDS and runs both
+ * contractions from it.  Split-fp32 mode, fp32 activations, the nine taps in row-major order, TW <= 16, CIN <= 32 (a
+ * multiple of 4), N = 32 or 64, no a_scale / dy_out; two tile buffers must fit 160 KB of LDS (BSED_ERR_ARG otherwise).
+ * Per slab the products are added in bsed_wgrad3's order, and at the plan's G a slab holds the tiles bsed_wgrad3's slab
+ * holds; per d_in element in the order of the data-gradient kernel the two-kernel route runs (16 -> 32 channels:
+ * bsed_igemm3s's 16 x 16 x 32 form; N = 64: bsed_igemm3n's 32 x 32 x 16 form): the routed layer keeps that route's bits.
+ * bsed_conv_bwd_plan: every shape check, no HIP call; G = the recommended number of slabs, or 0 where the kernel takes
+ * the shape but the two-kernel route measured faster (the caller then keeps it); max_G, label as for bsed_wgrad_plan. */
+int bsed_conv_bwd_plan(const BsedWgradDesc* desc /*host*/, BsedContractPlan* out /*host*/);
+int bsed_conv_bwd3(const BsedWgradDesc* desc /*host*/, void* stream);
 /* The slab reducers (csrc/reduce.hip; one summation order and one split rule behind both entry points: an immediate and
  * a batched reduction give the same bits).  dst[tap*s_tap + k*s_k + n*s_n] (+)= sum_g part[g][tap][k][n]   (k < K, n < N) */
 int bsed_reduce_partials(const float* part, int G, int ntaps, int KP, int NP, int K, int N, float* dst,
