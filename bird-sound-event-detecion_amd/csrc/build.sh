@@ -5,12 +5,14 @@ cd "$(dirname "$0")"
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result"
 mkdir -p obj
+# an object is stale when its source or ANY header (csrc/*.h, the C ABI) is newer
+newer_header() { local h; for h in *.h ../../include/bsed.h; do [ "$h" -nt "$1" ] && return 0; done; return 1; }
 pids=()
 objs=()
 for f in *.hip; do
   o=obj/${f%.hip}.o
   objs+=("$o")
-  if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ bsed_common.h -nt "$o" ] || [ ../../include/bsed.h -nt "$o" ]; then
+  if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || newer_header "$o"; then
     # mel.hip: the SLP vectorizer packs the FFT's scalar fp32 arithmetic into v_pk_* with op_sel swizzles, whose
     # destination-forwarding hazards cost ~90 s_nop per frame: 0.635 -> 0.599 ms without it (A/B on MI355X).
     # The GCN register-pressure trackers let the scheduler see stft_mel2_kernel's real pressure: without them the

@@ -26,8 +26,7 @@
 // With 64 channels of d_y: igemm3n_kernel's 32 x 32 x 16 form (chunk, tap, k half, ...), bitwise that form's.
 // Tiles go to workgroups XCD-affine (a round's 32 consecutive tiles per XCD): the ring a tile re-reads is its
 // neighbours' interior, fetched by the same XCD's L2 at about the same time.
-#include "bsed_common.h"
-#include "../../include/bsed.h"
+#include "wgrad_tiles.h"
 #include <algorithm>
 #include <type_traits>
 
@@ -74,12 +73,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // a thread's pieces all sit in one channel quad (256 threads are a multiple of the quads per position)
     const bool xch_ok = 4 * (tid & 7) < p.CIN, dch_ok = 4 * (tid & (n4n - 1)) < p.N;
     const int xcoff = xch_ok ? 4 * (tid & 7) : 0, dcoff = dch_ok ? 4 * (tid & (n4n - 1)) : 0;
-    // BatchNorm backward on load: d_y = A g + B y + (C - B mean), the expression of wgrad3p_kernel
-    const float4 cA = *reinterpret_cast<const float4*>(p.bn_coef + dcoff);
-    const float4 cB = *reinterpret_cast<const float4*>(p.bn_coef + p.N + dcoff);
-    const float4 c2 = *reinterpret_cast<const float4*>(p.bn_coef + 2 * p.N + dcoff);
-    const float4 mu = *reinterpret_cast<const float4*>(p.bn_mean + dcoff);
-    const float4 cC = make_float4(fmaf(-cB.x, mu.x, c2.x), fmaf(-cB.y, mu.y, c2.y), fmaf(-cB.z, mu.z, c2.z), fmaf(-cB.w, mu.w, c2.w));
+    // BatchNorm backward on load.  (The coefficients are all this kernel takes from wgrad_tiles.h: with the shared tile
+    // decode <3, 2, 0, 0> spills 6 SGPRs for 4, with the shared set-up or epilogue <3, 1, 0, 0> 4 for 0 and <5, 2, 0, 0>
+    // 11-12 for 9; profiles/wgrad_tiles.json.)
+    const W3Bn bn = w3_bn_coef(p, dcoff);
+    const float4 cA = bn.A, cB = bn.B, cC = bn.C;
     // tile-invariant geometry of a piece in ONE register: LDS offset (ushorts, bits 0-15), patch column (16-23), patch row
     // (24-31).  The producers are issue-bound beside the consumers' MFMAs: every VALU instruction per piece counts.
     uint32_t xg[UX], dg[UD];
@@ -255,6 +253,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
       for (int s = 0; s < MAXS; ++s) { xab[s][0] = xa[s][0] + bo; xab[s][1] = xa[s][1] + bo; }
       xbb[0] = xb[0] + bo; xbb[1] = xb[1] + bo;
+      // (not w3_kstep: this loop keeps fragments live ACROSS K steps, a different schedule from the shared K step's)
       // stages (K step, slot group) in order; the fragments of stage st + 1 are requested before the MFMAs of stage st
       // issue, across K steps too (two stages live at a time, the d_y fragment double-buffered per K step): a consumer
       // wave is alone on its SIMD with the matrix cores, so an LDS latency it waits for is not hidden by anyone

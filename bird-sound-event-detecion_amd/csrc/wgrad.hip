@@ -21,9 +21,10 @@
 // bf16 activations and use one MFMA per product.  BatchNorm backward on load (bn_y) is built into wgrad3_kernel and
 // wgrad3p_kernel.  The block above each kernel says why it has its shape.
 //
-// Lane maps as in igemm.hip; IG_TILE_M and crow() come from bsed_common.h.
-#include "bsed_common.h"
-#include "../../include/bsed.h"
+// Lane maps as in igemm.hip; IG_TILE_M and crow() come from bsed_common.h.  wgrad_tiles.h holds the device code that
+// more than one site uses and that could be shared without costing any instance registers: the tile decode, the
+// BatchNorm-backward coefficients and the K step (DESIGN.md section 5 has the figures that kept the rest apart).
+#include "wgrad_tiles.h"
 #include <algorithm>
 #include <type_traits>
 
@@ -200,6 +201,9 @@ __global__ __launch_bounds__(NW * 64) void wgrad_kernel(const WgradParams P) {
 // the 1- and 2-slot 4-wave forms (conv1 16 -> 32 channels: 39 KB of LDS) are pinned to 128 registers so that FOUR
 // workgroups share a CU: 0.753 (three, 136 registers) -> 0.651 ms, 4.9 TB/s
 #define W3_WPE(MAXS, NW) ((MAXS) <= 2 && (NW) == 4 ? 4 : 2)
+// (this kernel calls nothing from wgrad_tiles.h: with any one of its pieces <9, 4, false, 0> spills more -- 406 -> 414
+//  VGPRs with the tile decode or the coefficients, 664 -> 780 B of scratch with the K step -- and <2, 8, *, 1> changes
+//  occupancy 3 -> 4; profiles/wgrad_tiles.json)
 template <int MAXS, int NW, bool BS, int ABF>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(W3_WPE(MAXS, NW)))) void wgrad3_kernel(const WgradParams P) {
   constexpr int NTHR = NW * 64;
@@ -624,17 +628,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // BatchNorm backward on load: d_y = A g + B y + (C - B mean); a thread's dy elements all sit in one channel quad
     const bool bnb = p.bn_y != nullptr;
     const bool dy_store = bnb && p.dy_out != nullptr && blockIdx.z == 0;   // one CIN chunk writes d_y out
-    float4 cA = make_float4(1.f, 1.f, 1.f, 1.f), cB = make_float4(0.f, 0.f, 0.f, 0.f), cC = cB;
-    if (bnb) {
-      // (a thread whose channel quad lies beyond N works on quad 0 instead: its loads stay inside the tensor, its LDS
-      //  image is zeroed, and what it stores to dy_out is the value quad 0's owner stores there as well)
-      const int cn = n0 + 4 * (tid & (n4n - 1)) < p.N ? n0 + 4 * (tid & (n4n - 1)) : 0;
-      cA = *reinterpret_cast<const float4*>(p.bn_coef + cn);
-      cB = *reinterpret_cast<const float4*>(p.bn_coef + p.N + cn);
-      const float4 c2 = *reinterpret_cast<const float4*>(p.bn_coef + 2 * p.N + cn);
-      const float4 mu = *reinterpret_cast<const float4*>(p.bn_mean + cn);
-      cC = make_float4(fmaf(-cB.x, mu.x, c2.x), fmaf(-cB.y, mu.y, c2.y), fmaf(-cB.z, mu.z, c2.z), fmaf(-cB.w, mu.w, c2.w));
-    }
+    W3Bn bn = w3_bn_identity();
+    if (bnb) bn = w3_bn_coef(p, n0 + 4 * (tid & (n4n - 1)) < p.N ? n0 + 4 * (tid & (n4n - 1)) : 0);
+    const float4 cA = bn.A, cB = bn.B, cC = bn.C;
     if constexpr (ABF) {
       // ---- bf16 activations: 16-byte pieces of EIGHT channels (half the load / store / LDS-write instructions of the
       // four-channel pieces), no hi / lo split: a piece goes to the hi plane as it arrives
@@ -647,17 +643,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       const int gW = p.W, gH = p.H;
       const bool xch_ok = cz0 + 8 * (tid & (c8n - 1)) < p.CIN, dch_ok = n0 + 8 * (tid & (n8n - 1)) < p.N;
       const int xcoff = xch_ok ? cz0 + 8 * (tid & (c8n - 1)) : 0, dcoff = dch_ok ? n0 + 8 * (tid & (n8n - 1)) : 0;
-      float cA8[8], cB8[8], cC8[8];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) { cA8[q] = 1.f; cB8[q] = 0.f; cC8[q] = 0.f; }
-      if (bnb) {
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          cA8[q] = p.bn_coef[dcoff + q];
-          cB8[q] = p.bn_coef[p.N + dcoff + q];
-          cC8[q] = fmaf(-cB8[q], p.bn_mean[dcoff + q], p.bn_coef[2 * p.N + dcoff + q]);
-        }
-      }
+      // eight channels: the coefficients of two quads (dcoff is quad 0's where the piece lies beyond N)
+      W3Bn b0 = w3_bn_identity(), b1 = b0;
+      if (bnb) { b0 = w3_bn_coef(p, dcoff); b1 = w3_bn_coef(p, dcoff + 4); }
+      const float cA8[8] = {b0.A.x, b0.A.y, b0.A.z, b0.A.w, b1.A.x, b1.A.y, b1.A.z, b1.A.w};
+      const float cB8[8] = {b0.B.x, b0.B.y, b0.B.z, b0.B.w, b1.B.x, b1.B.y, b1.B.z, b1.B.w};
+      const float cC8[8] = {b0.C.x, b0.C.y, b0.C.z, b0.C.w, b1.C.x, b1.C.y, b1.C.z, b1.C.w};
       float sc8[8], sh8[8];
       const bool affine = p.a_scale != nullptr;
 #pragma unroll
@@ -703,24 +694,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         }
         return r;
       };
-      struct TGeo { int th0, tw0; size_t in_img, dy_img; };
-      auto tgeo = [&](int tile) {
-        int t = tile;
-        const int tw_i = t % p.tilesW; t /= p.tilesW;
-        const int th_i = t % p.tilesH;
-        const int nb = t / p.tilesH;
-        TGeo g;
-        g.th0 = th_i * p.TH; g.tw0 = tw_i * p.TW;
-        g.in_img = (size_t)nb * p.H * p.W * p.in_pitch;
-        g.dy_img = (size_t)nb * p.H * p.W * p.dy_pitch;
-        return g;
-      };
-      auto x_at = [&](int u, const TGeo& g, bool& ok) {
+      auto x_at = [&](int u, const W3Tile& g, bool& ok) {
         const int gh_ = g.th0 + (xrc[u] >> 16), gw = g.tw0 + (int)(short)(xrc[u] & 0xffff);
         ok = (unsigned)gh_ < (unsigned)gH && (unsigned)gw < (unsigned)gW;
         return (uint32_t)((min(max(gh_, 0), gH - 1) * gW + min(max(gw, 0), gW - 1)) * p.in_pitch + xcoff) << 1;
       };
-      auto d_at = [&](int u, const TGeo& g, bool& ok) {
+      auto d_at = [&](int u, const W3Tile& g, bool& ok) {
         const int gh_ = g.th0 + (drc[u] >> 16), gw = g.tw0 + (drc[u] & 0xffff);
         ok = gh_ < gH && gw < gW;
         return (uint32_t)((min(gh_, gH - 1) * gW + min(gw, gW - 1)) * p.dy_pitch + dcoff) << 1;
@@ -734,7 +713,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         bsed_u32x4 vx[UX8], vd[UD8], vy[BNB ? UD8 : 1];
         int tile = blockIdx.x, buf = 0;
         if (tile >= P.ntiles) return;
-        TGeo gc = tgeo(tile);
+        W3Tile gc = w3_tile(p, tile);
 #pragma unroll
         for (int u = 0; u < UD8; ++u) {
           if (GEO && u * NTHR >= d_tot) continue;
@@ -751,7 +730,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         }
         for (; tile < P.ntiles; buf ^= 1) {
           const int nxt = tile + gridDim.x;
-          const TGeo gn = tgeo(nxt < P.ntiles ? nxt : tile);
+          const W3Tile gn = w3_tile(p, nxt < P.ntiles ? nxt : tile);
           const int bo = buf * buf_u16;
 #pragma unroll
           for (int u = 0; u < UD8; ++u) {
@@ -836,25 +815,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       dyo[u] = mm * DYW + (w3_chunk(n4 >> 3, mm, P.ntw) << 5) + 4 * (n4 & 7);
       drc[u] = (e < d_tot && dch_ok) ? (r << 16) | c : (0x4000 << 16);
     }
-    struct TGeo { int th0, tw0; size_t in_img, dy_img; };
-    auto tgeo = [&](int tile) {
-      int t = tile;
-      const int tw_i = t % p.tilesW; t /= p.tilesW;
-      const int th_i = t % p.tilesH;
-      const int nb = t / p.tilesH;
-      TGeo g;
-      g.th0 = th_i * p.TH; g.tw0 = tw_i * p.TW;
-      g.in_img = (size_t)nb * p.H * p.W * p.in_pitch;
-      g.dy_img = (size_t)nb * p.H * p.W * p.dy_pitch;
-      return g;
-    };
     // byte offset of a piece inside its image (clamped into the map) and whether the piece is inside the map
-    auto x_at = [&](int u, const TGeo& g, bool& ok) {
+    auto x_at = [&](int u, const W3Tile& g, bool& ok) {
       const int gh_ = g.th0 + (xrc[u] >> 16), gw = g.tw0 + (int)(short)(xrc[u] & 0xffff);
       ok = (unsigned)gh_ < (unsigned)gH && (unsigned)gw < (unsigned)gW;
       return (uint32_t)((min(max(gh_, 0), gH - 1) * gW + min(max(gw, 0), gW - 1)) * p.in_pitch + xcoff) << 2;
     };
-    auto d_at = [&](int u, const TGeo& g, bool& ok) {
+    auto d_at = [&](int u, const W3Tile& g, bool& ok) {
       const int gh_ = g.th0 + (drc[u] >> 16), gw = g.tw0 + (drc[u] & 0xffff);
       ok = gh_ < gH && gw < gW;
       return (uint32_t)((min(gh_, gH - 1) * gW + min(gw, gW - 1)) * p.dy_pitch + dcoff) << 2;
@@ -867,7 +834,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       w3_f32x4 vx[UX], vd[UD], vy[BNB ? UD : 1];  // native vectors: arrays of HIP float4 structs end up in scratch
       int tile = blockIdx.x, buf = 0;
       if (tile >= P.ntiles) return;
-      TGeo gc = tgeo(tile);
+      W3Tile gc = w3_tile(p, tile);
 #pragma unroll
       for (int u = 0; u < UD; ++u) {
         if (GEO && u * NTHR >= d_tot) continue;
@@ -884,7 +851,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       }
       for (; tile < P.ntiles; buf ^= 1) {
         const int nxt = tile + gridDim.x;
-        const TGeo gn = tgeo(nxt < P.ntiles ? nxt : tile);
+        const W3Tile gn = w3_tile(p, nxt < P.ntiles ? nxt : tile);
         // (the buffer being written was last read before the previous barrier)
         const int bo = buf * buf_u16;
 #pragma unroll
@@ -936,9 +903,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   const int ntap_items = P.pack2 ? (p.ntaps + 1) / 2 : p.ntaps;
   const int nitems = ntap_items * P.nct * P.ntw;
   const int gq = (lane >> 2) & 3, gc = 4 * (lane & 3), gh = (lane >> 4) & 1;  // see wgrad3_kernel
+  // (set-up and epilogue are this kernel's own: as shared functions they take <9, 0, 0> from 48 to 52 B of scratch)
   const uint32_t xh0 = (uint32_t)(uintptr_t)Xh, dh0 = (uint32_t)(uintptr_t)DYh;
   const uint32_t xlo = 2 * P.PP * CC, dlo = 2 * IG_TILE_M * DYW;
-  uint32_t xa[MAXS][2], xb[2];
+  uint32_t xa[MAXS][2], xb[1][2];
   bool valid[MAXS];
   f32x16 acc[MAXS];
 #pragma unroll
@@ -959,94 +927,33 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       const int pr = (mk >> P.lgTW) + p.hh + p.dh[tp], pc = (mk & (p.TW - 1)) + p.hw + p.dw[tp];
       xa[s][rd] = xh0 + 2 * ((pr * PW + pc) * CC + (w3_chunk(cit, pc, P.nct) << 5) + col);
       // the host only picks this kernel when all items of a wave share the dy tile (4 % (nct * ntw) == 0)
-      if (s == 0) xb[rd] = dh0 + 2 * (mk * DYW + (w3_chunk(nt, mk, P.ntw) << 5) + 16 * gh + gc);
+      if (s == 0) xb[0][rd] = dh0 + 2 * (mk * DYW + (w3_chunk(nt, mk, P.ntw) << 5) + 16 * gh + gc);
     }
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[s][r] = 0.f;
   }
   __syncthreads();  // tile 0 is in buffer 0
   int buf = 0;
-  // fragments of slot group g+1 are requested before the MFMAs of group g issue (two groups live at a time)
-  constexpr int SG = 2, NG = (MAXS + SG - 1) / SG;
+  constexpr int SG = 2;   // w3_kstep: two slot groups live at a time
   for (int tile = blockIdx.x; tile < P.ntiles; tile += gridDim.x, buf ^= 1) {
     if constexpr (GEO > 0) {
+      // compile-time geometry: every offset of the K loop is an instruction immediate and the loop is unrolled
       constexpr W3Geo Gm = w3_geo(GEO);
       constexpr uint32_t kstep = 2 * (16 >> Gm.lgTW) * Gm.PW * Gm.CC, bstep = 2 * 16 * 32 * Gm.ntw;
       constexpr uint32_t xloc = 2 * Gm.PP * Gm.CC, dloc = 2 * IG_TILE_M * 32 * Gm.ntw;
       const uint32_t bo = 2 * buf * buf_u16;
-      uint32_t xab[MAXS][2], xbb[2];
+      uint32_t xab[MAXS][2], xbb[1][2];
 #pragma unroll
       for (int s = 0; s < MAXS; ++s) { xab[s][0] = xa[s][0] + bo; xab[s][1] = xa[s][1] + bo; }
-      xbb[0] = xb[0] + bo; xbb[1] = xb[1] + bo;
+      xbb[0][0] = xb[0][0] + bo; xbb[0][1] = xb[0][1] + bo;
 #pragma unroll
-      for (int kpi = 0; kpi < IG_TILE_M / 16; ++kpi) {
-        const uint32_t ko = kpi * kstep, kb = kpi * bstep;
-        w3_bf16x8 ah[2][SG], al[2][SG], bh, bl;
-#pragma unroll
-        for (int g = 0; g <= NG; ++g) {
-          if (g < NG) {
-#pragma unroll
-            for (int j = 0; j < SG; ++j) {
-              const int sl = g * SG + j;
-              if (sl < MAXS) {
-                ah[g & 1][j] = w3_frag(xab[sl][0] + ko, xab[sl][1] + ko);
-                al[g & 1][j] = w3_frag(xab[sl][0] + (ko + xloc), xab[sl][1] + (ko + xloc));
-                if (sl == 0) {
-                  bh = w3_frag(xbb[0] + kb, xbb[1] + kb);
-                  bl = w3_frag(xbb[0] + (kb + dloc), xbb[1] + (kb + dloc));
-                }
-              }
-            }
-          }
-          __builtin_amdgcn_sched_barrier(0);
-          if (g > 0) {
-#pragma unroll
-            for (int j = 0; j < SG; ++j) {
-              const int sl = (g - 1) * SG + j;
-              if (sl < MAXS) {
-                acc[sl] = w3_mfma<ABF>(ah[(g - 1) & 1][j], al[(g - 1) & 1][j], bh, bl, acc[sl]);
-              }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-          }
-        }
-      }
+      for (int kpi = 0; kpi < IG_TILE_M / 16; ++kpi) w3_kstep<MAXS, SG, true, ABF>(xab, xbb, kpi * kstep, kpi * bstep, xloc, dloc, acc);
     } else {
       const uint32_t kstep = 2 * (16 >> P.lgTW) * PW * CC;
       const uint32_t bstep = 2 * 16 * DYW;
       uint32_t ko = 2 * buf * buf_u16, kb = ko;
 #pragma unroll 1
-      for (int kp = 0; kp < IG_TILE_M; kp += 16, ko += kstep, kb += bstep) {
-        w3_bf16x8 ah[2][SG], al[2][SG], bh, bl;
-#pragma unroll
-        for (int g = 0; g <= NG; ++g) {
-          if (g < NG) {
-#pragma unroll
-            for (int j = 0; j < SG; ++j) {
-              const int sl = g * SG + j;
-              if (sl < MAXS) {
-                ah[g & 1][j] = w3_frag(xa[sl][0] + ko, xa[sl][1] + ko);
-                al[g & 1][j] = w3_frag(xa[sl][0] + ko + xlo, xa[sl][1] + ko + xlo);
-                if (sl == 0) {
-                  bh = w3_frag(xb[0] + kb, xb[1] + kb);
-                  bl = w3_frag(xb[0] + kb + dlo, xb[1] + kb + dlo);
-                }
-              }
-            }
-          }
-          __builtin_amdgcn_sched_barrier(0);
-          if (g > 0) {
-#pragma unroll
-            for (int j = 0; j < SG; ++j) {
-              const int sl = (g - 1) * SG + j;
-              if (sl < MAXS) {
-                acc[sl] = w3_mfma<ABF>(ah[(g - 1) & 1][j], al[(g - 1) & 1][j], bh, bl, acc[sl]);
-              }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-          }
-        }
-      }
+      for (int kp = 0; kp < IG_TILE_M; kp += 16, ko += kstep, kb += bstep) w3_kstep<MAXS, SG, true, ABF>(xa, xb, ko, kb, xlo, dlo, acc);
     }
     __syncthreads();
   }

@@ -511,9 +511,10 @@ def contract(inp, wv, NB, H, W, *, mode, direction="forward", bias=None, epilogu
 
 
 def wgrad(inp, dy, NB, H, W, CIN, N, taps=((0, 0),), in_pitch=None, dy_pitch=None, a_scale=None, a_shift=None,
-          in_offset=0, dy_offset=0, *, mode, bn_y=None, bn_coef=None, bn_mean=None, dy_out=None):
+          in_offset=0, dy_offset=0, *, mode, bn_y=None, bn_coef=None, bn_mean=None, dy_out=None, G=None):
     """Partial slabs of dW; returns (part, G, CINP, NP).  mode: the caller's conv_mode -- "fp32" = the fp32-core
-    kernels, "bf16x3" / "bf16" = split-fp32 operands on the bf16 cores.
+    kernels, "bf16x3" / "bf16" = split-fp32 operands on the bf16 cores.  G: number of partial slabs (None or 0: the
+    plan's); the library takes 1..number of tiles and refuses anything else.
     bn_y / bn_coef / bn_mean: `dy` is dL/d(BatchNorm output) and BatchNorm's backward is applied on load (bf16x3 only);
     dy_out then receives d_y for the data-gradient convolution."""
     if mode not in ("fp32", "bf16x3", "bf16"):
@@ -532,7 +533,7 @@ def wgrad(inp, dy, NB, H, W, CIN, N, taps=((0, 0),), in_pitch=None, dy_pitch=Non
     d.dy_pitch = N if dy_pitch is None else dy_pitch
     d.NB, d.H, d.W, d.CIN, d.CINP, d.N, d.NP = NB, H, W, CIN, CINP, N, NP
     plan = _contract_plan(f"bsed_wgrad{sfx}", d)
-    G = plan.G
+    G = d.G = G or plan.G
     part = torch.empty((G, len(taps), CINP, NP), device=inp.device, dtype=torch.float32)
     d.part = _p(part)
     # algorithmic bytes: the input and dy once; with the fused BatchNorm backward also y (read) and d_y (written)
@@ -634,13 +635,13 @@ def conv_bwd_plan(NB, H, W, CIN, N, act_bf16=0):
     return d, plan
 
 
-def conv_bwd_fused(inp, g, y, coef, mean, wv, NB, H, W, G=None):
+def conv_bwd_fused(inp, g, y, coef, mean, wv, NB, H, W, G=None, planned=None):
     """One pass over inp, g and y (csrc/conv_bwd.hip): BatchNorm backward on load, the partial slabs of the weight gradient
     AND the data gradient, d_y never written.  wv: the layer's forward WeightView.  G: number of partial slabs (default:
-    the plan's; the kernel takes any 1..max_G).  Returns (d_in, part, G, CINP, NP); raises where the kernel does not take
-    the shape."""
+    the plan's; the kernel takes any 1..max_G).  planned: conv_bwd_plan's (descriptor, plan) of this shape where the
+    caller has asked already.  Returns (d_in, part, G, CINP, NP); raises where the kernel does not take the shape."""
     CIN, N = wv.K, wv.N
-    d, plan = conv_bwd_plan(NB, H, W, CIN, N, _abf(inp, g, y))
+    d, plan = planned or conv_bwd_plan(NB, H, W, CIN, N, _abf(inp, g, y))
     if plan is None or wv.taps != tuple(TAPS3x3):
         raise L.BsedError("conv_bwd_fused: " + (L.lib().bsed_last_error().decode() if plan is None else "3x3 taps only"))
     G = G or plan.G or min(256, plan.max_G)
@@ -663,15 +664,16 @@ def conv_bn_backward(inp, g, y, coef, mean, wv, gv, NB, H, W, *, mode, need_dgra
     (None without need_dgrad).  fused: None = bsed_conv_bwd_plan decides between the one-pass kernel and the two kernels
     it replaces (weight gradient writing d_y, data gradient reading it back); False = the two kernels; True = the one-pass
     kernel or an error."""
-    use = False
+    use, planned = False, None
     if fused is not False and need_dgrad and mode == "bf16x3":
-        plan = conv_bwd_plan(NB, H, W, wv.K, wv.N, _abf(inp, g, y))[1]
+        planned = conv_bwd_plan(NB, H, W, wv.K, wv.N, _abf(inp, g, y))
+        plan = planned[1]
         use = plan is not None and wv.taps == tuple(TAPS3x3) and (fused is True or plan.G > 0)
     if fused is True and not use:
         raise L.BsedError("conv_bn_backward: the one-pass kernel does not take this layer: " +
                           L.lib().bsed_last_error().decode())
     if use:
-        d_in, part, G, KP, NP = conv_bwd_fused(inp, g, y, coef, mean, wv, NB, H, W)
+        d_in, part, G, KP, NP = conv_bwd_fused(inp, g, y, coef, mean, wv, NB, H, W, planned=planned)
         reduce_partials(part, G, 9, KP, NP, gv.K, gv.N, gv.tensor, gv.s_tap, gv.s_k, gv.s_n, dst_offset=gv.offset)
         return d_in
     dy = torch.empty_like(g) if need_dgrad else None

@@ -340,6 +340,25 @@ def test_conv3x3_weight_gradient_bf16x3_matches_fp64_reference(B, H, W, cin, co,
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("B,H,W,cin,co", [(2, 21, 32, 32, 64), (2, 21, 16, 64, 128)])
+def test_conv3x3_weight_gradient_pipelined_and_tile_forms_give_the_same_slabs(B, H, W, cin, co, monkeypatch):
+    """csrc/wgrad.hip says of wgrad3p_kernel: same tiles, same products, same accumulation order as wgrad3_kernel.  At the
+    SAME number of partial slabs every slab is then the same bit for bit (one full tile row group plus a ragged one per
+    image, 5 and 9 slots)."""
+    from bsed_amd import ops
+    rng = np.random.default_rng(H * W + cin)
+    xg = torch.from_numpy(rng.standard_normal((B, H, W, cin)).astype(np.float32)).cuda()
+    dyg = torch.from_numpy(rng.standard_normal((B, H, W, co)).astype(np.float32)).cuda()
+    monkeypatch.delenv("BSED_WGRAD3_NOPIPE", raising=False)
+    pipe, G, _, _ = ops.wgrad(xg, dyg, B, H, W, cin, co, taps=ops.TAPS3x3, mode="bf16x3")
+    monkeypatch.setenv("BSED_WGRAD3_NOPIPE", "1")
+    tile, G1, _, _ = ops.wgrad(xg, dyg, B, H, W, cin, co, taps=ops.TAPS3x3, mode="bf16x3", G=G)
+    assert G1 == G and pipe.shape == tile.shape
+    assert float(pipe[:, :, :cin].abs().max()) > 0
+    assert torch.equal(pipe[:, :, :cin], tile[:, :, :cin])
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("B,H,W,cin,co", [
     (2, 37, 16, 64, 128),    # every workgroup stores d_y (one input-channel chunk), ragged last tile row
     (2, 61, 8, 128, 128),    # two input-channel chunks: only chunk 0 stores d_y
