@@ -13,6 +13,10 @@ input without leaving HBM.
   resample_filter(sr_in, sr_out)            (csrc/resample.hip).  The filter is this project's own Kaiser-windowed sinc,
                                             fully specified in ``resample_filter``; it is NOT librosa's (soxr's)
                                             resampler and no bit parity with it is claimed.
+
+  loudness(waves, sr)                    ITU-R BS.1770-4 integrated loudness (LUFS) of every row of a batch, and the rows
+  normalize_loudness(waves, sr, target)     scaled to a target (csrc/loudness.hip; the rules are include/bsed.h's: what
+                                            scaper levels the reference's SYN set by, its values not pinned).
 """
 import ctypes
 import math
@@ -328,3 +332,49 @@ def load_audio(path, sr=32000, **quality):
     from .data import read_wav
     x, sr_in = read_wav(path)
     return resampler(sr_in, sr, **quality)(x), int(sr)
+
+
+def _rows_f32(waves, sr, who):
+    """(n,) or (B, n), numpy or GPU tensor, float32 or int16 -> a contiguous (B, n) float32 device tensor (int16 scaled by
+    1 / 32768 on the device, as ``load_audio`` converts it)"""
+    if not isinstance(waves, (np.ndarray, torch.Tensor)):
+        raise L.BsedError(f"{who} takes a numpy array or a GPU tensor, got {type(waves).__name__}")
+    dt = str(waves.dtype).replace("torch.", "")
+    if dt not in ("int16", "float32"):
+        raise L.BsedError(f"{who} takes int16 or float32 samples, got {dt}")
+    if waves.ndim not in (1, 2) or min(waves.shape) < 1:
+        raise L.BsedError(f"{who} takes waveforms shaped (n,) or (B, n) with at least one sample, got shape {tuple(waves.shape)}")
+    L._require_gpu()
+    if isinstance(waves, np.ndarray):
+        waves = torch.from_numpy(np.ascontiguousarray(waves)).cuda()
+    elif not waves.is_cuda:
+        raise L.BsedError(f"{who} takes a numpy array or a GPU tensor, got a CPU tensor")
+    rows = waves.contiguous().reshape(-1, waves.shape[-1])
+    if rows.dtype == torch.int16:
+        rows = resampler(sr, sr)(rows.reshape(-1)).reshape(rows.shape)          # the convert-only launch
+    return rows
+
+
+def loudness(waves, sr):
+    """Integrated loudness of every waveform in LUFS: ITU-R BS.1770-4 for one channel (K-weighting, 400 ms blocks at a
+    100 ms hop, the -70 LUFS and the relative -10 LU gates), by the rules include/bsed.h states for ``bsed_loudness``.
+    waves: (n,) or (B, n), a numpy array or a GPU tensor, float32 or int16 -> (B,) float64 GPU tensor from one call of
+    the entry point; a waveform with no block above -70 LUFS (silence) gives -inf; one shorter than half a second is
+    measured over whole repetitions of itself.  Nothing waits for the device.  The values are this rule's: no parity with
+    pyloudnorm's or scaper's numbers is pinned."""
+    rows = _rows_f32(waves, sr, "loudness")
+    B, n = rows.shape
+    off = torch.arange(B, device=rows.device, dtype=torch.int64) * n
+    length = torch.full((B,), n, device=rows.device, dtype=torch.int64)
+    return ops.loudness(rows.reshape(-1), off, length, sr, n, samples=B * n)
+
+
+def normalize_loudness(waves, sr, target_lufs):
+    """Scale every waveform to ``target_lufs``: row * 10^((target - L) / 20) with L = ``loudness`` of the row, on the
+    device; a row at -inf (silence) is left unchanged.  -> (scaled float32, of the input's shape; lufs (B,) float64: the
+    loudness BEFORE scaling).  Nothing waits for the device."""
+    rows = _rows_f32(waves, sr, "normalize_loudness")
+    lufs = loudness(rows, sr)
+    gain = torch.where(torch.isinf(lufs), torch.ones_like(lufs), torch.pow(10.0, (float(target_lufs) - lufs) / 20.0))
+    scaled = rows * gain.to(torch.float32)[:, None]
+    return scaled.reshape(tuple(waves.shape)), lufs

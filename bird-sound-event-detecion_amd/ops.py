@@ -1243,3 +1243,25 @@ def synth_targets(n_ev, cls, on_f, off_f, B, K, T, C):
     L.call("bsed_synth_targets", L.ptr(n_ev, i32), L.ptr(cls, i32), L.ptr(on_f, i32), L.ptr(off_f, i32), B, K, T, C,
            L.ptr(strong), L.ptr(weak), L.stream())
     return strong, weak
+
+
+def loudness(x, seg_off, seg_len, sr, max_len, counts=False, samples=None):
+    """``bsed_loudness``: the BS.1770-4 integrated loudness (LUFS) of S segments of the flat fp32 device buffer ``x``
+    (include/bsed.h states the rules).  seg_off / seg_len: (S,) int64 device tensors; max_len: a host bound on the
+    lengths (a longer segment is measured over its first max_len samples).  samples: the effective samples of all
+    segments, for the work announcement alone (default S * max_len).  -> loud (S,) float64, or (loud, counts (S, 3)
+    int32: blocks, blocks above the absolute gate, blocks above both) with ``counts=True``.  Two launches, no host sync."""
+    S, sr, max_len = int(seg_off.numel()), int(sr), int(max_len)
+    if int(seg_len.numel()) != S:
+        raise L.BsedError(f"loudness: {S} offsets but {int(seg_len.numel())} lengths")
+    nbytes = L.lib().bsed_loudness_ws_bytes(S, max_len, sr)
+    if nbytes < 0:
+        raise L.BsedError("loudness: " + L.lib().bsed_last_error().decode())
+    ws = torch.empty(nbytes // 8, device=x.device, dtype=torch.float64)
+    loud = torch.empty(S, device=x.device, dtype=torch.float64)
+    cnt = torch.empty((S, 3), device=x.device, dtype=torch.int32) if counts else None
+    n_samples = float(S * max_len if samples is None else samples)
+    _note("loudness_hops_kernel", f"S{S} sr{sr}", 40.0 * n_samples, 4.0 * n_samples)    # two passes of 9 fma, 2 fma for y^2
+    L.call("bsed_loudness", L.ptr(x), x.numel(), L.ptr(seg_off, torch.int64), L.ptr(seg_len, torch.int64), S, max_len, sr,
+           L.ptr(ws, torch.float64), nbytes, L.ptr(loud, torch.float64), L.ptr(cnt, torch.int32), L.stream())
+    return (loud, cnt) if counts else loud

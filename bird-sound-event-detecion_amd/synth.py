@@ -13,9 +13,13 @@ flat array (``SoundBank``); a batch of soundscapes is drawn on the host as a few
                           synth_data_preprocess.py:44-61)
   Synthesizer.write_dataset  <- syn_preprocess (synth_data_preprocess.py:82-114): the offline counterpart
 
-NOT pinned to the reference's tools: the loudness model is RMS-based (scaper normalises by LUFS), and the sampler's draws
-are this project's own (a numpy ``Generator``), not desed's.  Clips made here have the reference's structure and
-annotation format, not its sample values -- as ``features.load_audio`` says about librosa's resampler.
+Levels: ``loudness="rms"`` (the default) reads ``ref_db`` and the SNR against each item's plain RMS; ``loudness="lufs"``
+reads them, as scaper does, against the item's BS.1770-4 integrated loudness, measured on the device by
+``bsed_loudness`` under the rules include/bsed.h states (K-weighting, gated 400 ms blocks, a short snippet tiled to half a
+second; the whole item is measured, also where a plan cuts a stretch out of it).  NOT pinned to the reference's tools:
+scaper's (pyloudnorm's) values were not compared against, and the sampler's draws are this project's own (a numpy
+``Generator``), not desed's.  Clips made here have the reference's structure and annotation format, not its sample values
+-- as ``features.load_audio`` says about librosa's resampler.
 """
 import glob
 import os
@@ -47,11 +51,15 @@ class SoundBank:
       bank.offset / .length        int64 per item, in samples
       bank.cls                     int32 per item: index into ``labels``, -1 for a background
       bank.rms                     float64 per item (computed once, on the device, in float64)
+      bank.lufs                    float64 per item with ``loudness="lufs"`` (-inf: no block above -70 LUFS), else None:
+                                   all items measured by ONE ``bsed_loudness`` call over ``flat``
       bank.items(label)            item indices of a label's snippets;  bank.backgrounds: those of the backgrounds
     """
 
-    def __init__(self, events, backgrounds, labels, sr=32000):
+    def __init__(self, events, backgrounds, labels, sr=32000, loudness="rms"):
         from .features import resampler
+        if loudness not in ("rms", "lufs"):
+            raise L.BsedError(f'SoundBank: loudness must be "rms" or "lufs", got {loudness!r}')
         L._require_gpu()
         self.labels, self.sr = list(labels), int(sr)
         to_f32 = resampler(self.sr, self.sr)          # the convert-only case: int16 -> float32 in one launch
@@ -76,15 +84,27 @@ class SoundBank:
                 raise L.BsedError(f"SoundBank: {what} is empty")
             dev.append(to_f32(w))
         self.flat = torch.cat(dev).contiguous()
-        rms = torch.stack([w.double().pow(2).mean().sqrt() for w in dev]).cpu().numpy()           # the one host sync
-        self._set_tables([int(w.shape[0]) for w in dev], cls, rms)
+        length = [int(w.shape[0]) for w in dev]
+        levels = torch.stack([w.double().pow(2).mean().sqrt() for w in dev])
+        if loudness == "lufs":
+            ln = torch.tensor(length, dtype=torch.int64)
+            off = torch.cumsum(ln, 0) - ln
+            lufs = ops.loudness(self.flat, off.to(self.flat.device), ln.to(self.flat.device), self.sr, max(length),
+                                samples=sum(length))
+            levels = torch.cat([levels, lufs])
+        levels = levels.cpu().numpy()                                                             # the one host sync
+        self._set_tables(length, cls, levels[:len(dev)], levels[len(dev):] if loudness == "lufs" else None)
 
-    def _set_tables(self, length, cls, rms):
+    def _set_tables(self, length, cls, rms, lufs=None):
         self.length = np.asarray(length, dtype=np.int64).reshape(-1)
         self.cls = np.asarray(cls, dtype=np.int32).reshape(-1)
         self.rms = np.asarray(rms, dtype=np.float64).reshape(-1)
         if not len(self.length) == len(self.cls) == len(self.rms) or len(self.length) < 1:
             raise L.BsedError("SoundBank: one length, class and RMS per item, and at least one item")
+        self.lufs = None if lufs is None else np.asarray(lufs, dtype=np.float64).reshape(-1)
+        if self.lufs is not None and (len(self.lufs) != len(self.length) or np.isnan(self.lufs).any() or
+                                      np.isposinf(self.lufs).any()):
+            raise L.BsedError("SoundBank: one loudness per item, each a number or -inf")
         if (self.length < 1).any() or (self.cls >= len(self.labels)).any():
             raise L.BsedError("SoundBank: an empty item or a class outside the labels")
         self.offset = np.concatenate([[0], np.cumsum(self.length)[:-1]]).astype(np.int64)
@@ -92,12 +112,13 @@ class SoundBank:
         self._by_class = [np.nonzero(self.cls == c)[0] for c in range(len(self.labels))]
 
     @classmethod
-    def layout(cls, labels, length, item_class, rms, sr=32000):
+    def layout(cls, labels, length, item_class, rms, sr=32000, lufs=None):
         """A bank described by its host tables alone (``flat`` is None): enough to draw and validate plans -- which is
-        host work -- on a machine without the samples or without a GPU.  item_class: label index, -1 = background."""
+        host work -- on a machine without the samples or without a GPU.  item_class: label index, -1 = background;
+        lufs: the items' integrated loudness, for plans drawn with ``loudness="lufs"``."""
         self = cls.__new__(cls)
         self.labels, self.sr, self.flat = list(labels), int(sr), None
-        self._set_tables(length, item_class, rms)
+        self._set_tables(length, item_class, rms, lufs)
         return self
 
     def __len__(self):
@@ -117,10 +138,11 @@ class SoundBank:
         return self.flat[int(self.offset[item]):int(self.offset[item] + self.length[item])]
 
     @classmethod
-    def from_folders(cls, fg_folder, bg_folder, labels, sr=32000):
+    def from_folders(cls, fg_folder, bg_folder, labels, sr=32000, loudness="rms"):
         """scaper's layout: ``<fg_folder>/<LABEL>/*.wav`` and ``<bg_folder>/**/*.wav`` (``bg_folder`` may be None).  Files
         are read with ``features.load_audio``: any rate and channel count, mixed to mono and resampled to ``sr`` on the
-        GPU.  Files are taken in sorted order, so the bank does not depend on the directory's listing order."""
+        GPU.  Files are taken in sorted order, so the bank does not depend on the directory's listing order.
+        ``loudness`` is the bank's."""
         from .features import load_audio
         labels = list(labels)
         events = []
@@ -135,7 +157,7 @@ class SoundBank:
         if bg_folder is not None:
             for path in sorted(glob.glob(os.path.join(bg_folder, "**", "*.wav"), recursive=True)):
                 bgs.append(load_audio(path, sr)[0])
-        return cls(events, bgs, labels, sr)
+        return cls(events, bgs, labels, sr, loudness)
 
 
 class SoundscapePlan:
@@ -262,7 +284,7 @@ def _polyphony_with(intervals, on, off):
 
 def plan_soundscapes(bank, B, rng, clip_seconds=10.0, n_events=(1, 6), class_probs=None, co_occurrence=None,
                      snr_db=(6.0, 30.0), ref_db=-55.0, max_polyphony=4, min_event_seconds=0.2, fade_seconds=0.01,
-                     n_samples=None, hop_size=255, pooling_time_ratio=4, max_events=MAX_EVENTS, names=None):
+                     n_samples=None, hop_size=255, pooling_time_ratio=4, max_events=MAX_EVENTS, names=None, loudness="rms"):
     """Draw B soundscapes over ``bank`` on the host -> ``SoundscapePlan``.  ``rng`` is a ``numpy.random.Generator``; no
     global state is read and the same generator state gives the same plan.
 
@@ -279,10 +301,15 @@ def plan_soundscapes(bank, B, rng, clip_seconds=10.0, n_events=(1, 6), class_pro
     number of simultaneously active events above ``max_polyphony`` (the reference's ``rm_high_polyphony``) is redrawn up
     to 20 times, then dropped.  ``fade_seconds``: linear fade-in and fade-out of every event.
 
-    Loudness (RMS-based, this project's own; scaper normalises by LUFS and no parity with its levels is claimed):
-    ``bg_gain = 10^(ref_db / 20) / rms(background)`` and ``g = 10^((ref_db + snr) / 20) / rms(snippet)`` with ``snr``
-    uniform over ``snr_db``; ``ref_db = -55`` is the reference's (src/synth_data/data_config.py:5).  A silent item gets
-    gain 0.  Without backgrounds in the bank every clip has ``bg_len = 0`` (silence under the events).
+    Levels, with ``snr`` uniform over ``snr_db`` and ``ref_db = -55`` the reference's (src/synth_data/data_config.py:5):
+    ``loudness="rms"``: ``bg_gain = 10^(ref_db / 20) / rms(background)`` and ``g = 10^((ref_db + snr) / 20) / rms(snippet)``;
+    ``loudness="lufs"`` (scaper's reading of the two numbers; the bank must carry ``lufs``):
+    ``bg_gain = 10^((ref_db - lufs(background)) / 20)`` and ``g = 10^((ref_db + snr - lufs(snippet)) / 20)``, formed in
+    float64 and rounded to float32.  ``lufs`` is ``bsed_loudness``'s value of the WHOLE item (include/bsed.h), so a
+    background alone in a clip measures ``ref_db`` and an event ``ref_db + snr`` when it is placed whole; scaper's own
+    values are not pinned.  A silent item (RMS 0, or -inf LUFS) gets gain 0.  The draws do not depend on ``loudness``: the
+    two plans of one generator state differ in ``g`` and ``bg_gain`` alone.  Without backgrounds in the bank every clip has
+    ``bg_len = 0`` (silence under the events).
 
     ``n_samples`` overrides ``clip_seconds * sr``; ``hop_size`` / ``pooling_time_ratio`` are the encoder's, for the
     frame tables."""
@@ -298,6 +325,10 @@ def plan_soundscapes(bank, B, rng, clip_seconds=10.0, n_events=(1, 6), class_pro
         raise L.BsedError(f"plan_soundscapes: a clip of {n} samples is shorter than min_event_seconds = {min_event_seconds}")
     if B < 1 or max_polyphony < 1:
         raise L.BsedError("plan_soundscapes: B and max_polyphony must be at least 1")
+    if loudness not in ("rms", "lufs"):
+        raise L.BsedError(f'plan_soundscapes: loudness must be "rms" or "lufs", got {loudness!r}')
+    if loudness == "lufs" and getattr(bank, "lufs", None) is None:
+        raise L.BsedError('plan_soundscapes: loudness="lufs" needs a bank that carries lufs (SoundBank(..., loudness="lufs"))')
     C = len(bank.labels)
     have = np.array([len(bank._by_class[c]) > 0 for c in range(C)])
     if co_occurrence is None:
@@ -328,11 +359,17 @@ def plan_soundscapes(bank, B, rng, clip_seconds=10.0, n_events=(1, 6), class_pro
              on=np.zeros((B, K), np.int64), length=np.ones((B, K), np.int64), g=np.zeros((B, K), np.float32),
              inv_fade=np.full((B, K), inv_fade_v, np.float32), cls=np.zeros((B, K), np.int32))
     safe_rms = np.where(bank.rms > 0, bank.rms, np.inf)          # a silent item: gain 0
+
+    def lufs_gain(items, level_db):
+        """float32 gains that bring the items' integrated loudness to level_db (a scalar, or one level per item)"""
+        lufs = bank.lufs[items]
+        quiet = np.isneginf(lufs)                                # a silent item: gain 0
+        return np.where(quiet, 0.0, 10.0 ** ((level_db - np.where(quiet, 0.0, lufs)) / 20.0)).astype(np.float32)
     if len(bank.backgrounds):
         it = bank.backgrounds[rng.integers(len(bank.backgrounds), size=B)]
         P["bg_off"], P["bg_len"] = bank.offset[it], bank.length[it]
         P["bg_phase"] = np.minimum((rng.random(B) * bank.length[it]).astype(np.int64), bank.length[it] - 1)
-        P["bg_gain"] = (ref_amp / safe_rms[it]).astype(np.float32)
+        P["bg_gain"] = lufs_gain(it, ref_db) if loudness == "lufs" else (ref_amp / safe_rms[it]).astype(np.float32)
     if co_occurrence is None:
         count = np.minimum(rng.integers(lo, hi + 1, size=B), K)
         classes = rng.choice(C, size=int(count.sum()), p=p) if count.sum() else np.zeros(0, np.int64)
@@ -362,7 +399,12 @@ def plan_soundscapes(bank, B, rng, clip_seconds=10.0, n_events=(1, 6), class_pro
     start = np.minimum((u_start * (full - length + 1)).astype(np.int64), full - length)
     room = (n - length + 1)[:, None]
     onsets = np.minimum((u_on * room).astype(np.int64), room - 1)
-    gain = (ref_amp * 10.0 ** (snr / 20.0) / safe_rms[item]).astype(np.float32) if E else np.zeros(0, np.float32)
+    if not E:
+        gain = np.zeros(0, np.float32)
+    elif loudness == "lufs":
+        gain = lufs_gain(item, ref_db + snr)
+    else:
+        gain = (ref_amp * 10.0 ** (snr / 20.0) / safe_rms[item]).astype(np.float32)
     keep_on = np.full(E, -1, np.int64)
     slot = np.zeros(E, np.int64)
     placed, cur = [], -1

@@ -705,8 +705,9 @@ int bsed_resample_poly(const void* in, int format, long n_in, int channels, cons
 /* ------------------------------------------------------------------------------------------------
  * Soundscape synthesis (csrc/synth.hip).  stands in for the reference's offline desed / scaper generation of the SYN set
  * (src/synth_data/synth_data_preprocess.py:116-188): strongly labelled clips are mixed on the device from a resident bank
- * of event snippets and backgrounds.  The sampling and the loudness model are this project's own (synth.py): no parity
- * with scaper's LUFS levels or desed's draws is claimed.
+ * of event snippets and backgrounds.  The sampling is this project's own (synth.py): no parity with desed's draws is
+ * claimed.  The gains come from the items' RMS or from their integrated loudness (bsed_loudness below), as the caller
+ * of synth.py chooses.
  * ---------------------------------------------------------------------------------------------- */
 #define BSED_SYNTH_MAX_EVENTS 16
 /* bank: (bank_len) float32, every snippet and background back to back -> out (B, n) float32.  Clip b has a background
@@ -735,6 +736,55 @@ int bsed_synth_mix(const float* bank, long bank_len, const long* bg_off, const l
  * Refused before any launch: null pointers; B, T or C < 1; K outside 0..BSED_SYNTH_MAX_EVENTS; misaligned pointers. */
 int bsed_synth_targets(const int* n_ev, const int* cls, const int* on_f, const int* off_f, int B, int K, int T, int C,
                        float* strong, float* weak, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Integrated loudness (ABI 15; csrc/loudness.hip).  ITU-R BS.1770-4 for one channel: what scaper (through pyloudnorm)
+ * levels the reference's SYN set by (ref_db and the SNR range of src/synth_data/data_config.py:5 are LUFS there).  The
+ * rules below are the whole definition; neither pyloudnorm nor scaper was at hand when this was written, so parity with
+ * their values is not pinned.
+ *
+ * Coefficients, on the host in double, from sr, with K = tan(pi * f0 / sr):
+ *   stage 1 (shelf):      f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196,
+ *                         Vh = 10^(G / 20), Vb = Vh^0.4996667741545416, a0 = 1 + K / Q + K^2,
+ *                         b = (Vh + Vb K / Q + K^2) / a0, 2 (K^2 - Vh) / a0, (Vh - Vb K / Q + K^2) / a0,
+ *                         a1 = 2 (K^2 - 1) / a0, a2 = (1 - K / Q + K^2) / a0
+ *   stage 2 (high-pass):  f0 = 38.13547087602444, Q = 0.5003270373238773, b = 1, -2, 1, a1 and a2 as above from this K, Q
+ * (at 48 kHz the table of BS.1770-4 to its printed digits).  bsed_kweight_coefs writes b0 b1 b2 a1 a2 of stage 1, then
+ * of stage 2, to out (HOST, 10 doubles); it makes no HIP call and refuses sr outside 1000..384000.
+ *
+ * Signal of segment s = (seg_off[s], seg_len[s]) of the flat float32 buffer x (x_len samples), len = min(seg_len[s],
+ * max_len), half = (sr + 1) / 2:  n_eff = len if len >= half, else len * ceil(half / len) -- a short snippet is measured
+ * over whole repetitions of itself up to at least 0.5 s, scaper's practice for events shorter than a block;
+ * v[i] = (double)x[seg_off + i % len], 0 where that index lies outside 0 .. x_len - 1; filter state zero at i = 0; stage 1
+ * then stage 2, each   y[i] = b0 v[i] + b1 v[i-1] + b2 v[i-2] - a1 y[i-1] - a2 y[i-2]   in double.
+ * Blocks: l_j = (j * sr) / 10 in 64-bit integer division; block j is [l_j, l_(j+4)) and exists while l_(j+4) <= n_eff;
+ * z_j = the mean of y^2 over the block's own length (for rates divisible by 10: 400 ms at 75 % overlap).
+ * Gates: L_j = -0.691 + 10 log10 z_j;  A = {j : L_j > -70};  A empty: the result is -infinity; otherwise
+ * Gamma = -0.691 + 10 log10(mean_A z) - 10,  G = {j in A : L_j > Gamma},  loud = -0.691 + 10 log10(mean_G z).
+ * A segment with seg_len < 1 gives -infinity and zero counts.
+ * -> loud (S) float64;  counts (S, 3) int32 or NULL: the number of blocks, |A|, |G|.
+ *
+ * Accuracy: the result is not bitwise-defined (the kernel splits a segment, and how depends on S and max_len).  It is
+ * within 1e-6 LU of the sequential recurrence above for every segment whose L_j all lie more than 1e-3 LU from both
+ * gates, and counts are equal for those segments.  Inside a workgroup the split is exact (a scan of the 4-value filter
+ * state); across workgroups a piece starts ceil(50 / -ln r) samples early from zero state, r the largest pole radius
+ * (0.21 s at every rate), which leaves less than e^-50 times its length of the input's size behind: below double
+ * round-off for anything a float32 input can hold.  Repeatability: bitwise from launch to launch for the same arguments;
+ * every sum has a fixed order and there are no floating-point atomics.
+ *
+ * seg_off and seg_len are DEVICE int64 tables and are not validated: whatever they hold, no index outside
+ * 0 .. x_len - 1 is dereferenced and nothing outside loud, counts and the workspace is written.  ws: caller-owned device
+ * memory of at least bsed_loudness_ws_bytes(S, max_len, sr) bytes (the per-hop sums of y^2: 8 * S * the hops of the
+ * longest effective length; -1 for arguments bsed_loudness would refuse), 8-byte aligned, contents irrelevant before and
+ * after.  Two launches, no host synchronisation.
+ * Refused before any HIP call: null pointers (counts may be NULL); S < 1; x_len < 1; max_len < 1 (either above 2^40);
+ * sr outside 1000..384000, or below 3364 (the shelf's centre frequency would lie above sr / 2, where the recurrence is
+ * not stable); ws_bytes too small; a pointer not aligned to its element size.
+ * ---------------------------------------------------------------------------------------------- */
+int bsed_kweight_coefs(int sr, double* out /*host: 10*/);
+long bsed_loudness_ws_bytes(int S, long max_len, int sr);
+int bsed_loudness(const float* x, long x_len, const long* seg_off, const long* seg_len, int S, long max_len, int sr,
+                  void* ws, long ws_bytes, double* loud, int* counts, void* stream);
 
 typedef struct BsedHeadBwdDesc {
   const float* x;            /* (B,T,K) encoder output */
