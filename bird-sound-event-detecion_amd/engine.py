@@ -17,6 +17,7 @@ but the first two CNN blocks' has been enqueued, and overlaps the rest of it; th
 the optimizer kernel.
 """
 import contextlib
+from typing import Any, NamedTuple
 
 import numpy as np
 
@@ -66,6 +67,13 @@ def adjust_learning_rate(optimizer, rampup_value, rampdown_value=1, optimizer_d=
     return lr
 
 
+def _state_arenas(module):
+    """A module's whole state as flat arenas: ([parameters, float buffers (BatchNorm running statistics) if it has any],
+    the int64 num_batches_tracked counters or None)."""
+    floats = [module.flat] + ([module.flat_buf] if getattr(module, "flat_buf", None) is not None else [])
+    return floats, getattr(module, "nbt", None)
+
+
 @torch.no_grad()
 def update_ema_variables(model, ema_model, alpha, global_step):
     """ema = ema*alpha' + model*(1-alpha'), alpha' = min(1 - 1/(step+1), alpha), over EVERY state entry
@@ -73,41 +81,54 @@ def update_ema_variables(model, ema_model, alpha, global_step):
     flat arena.  (The reference implementation raises for a plain CRNN because of its "cnn." key quirk --
     DESIGN.md D8 -- this is the update it intends.)"""
     alpha = min(1 - 1 / (global_step + 1), alpha)
-    ops.ema_update(ema_model.flat, model.flat, alpha)
-    if getattr(model, "flat_buf", None) is not None:
-        ops.ema_update(ema_model.flat_buf, model.flat_buf, alpha)
-    if getattr(model, "nbt", None) is not None:
-        ops.ema_update_i64(ema_model.nbt, model.nbt, alpha)
+    (floats, nbt), (ema_floats, ema_nbt) = _state_arenas(model), _state_arenas(ema_model)
+    for dst, src in zip(ema_floats, floats):
+        ops.ema_update(dst, src, alpha)
+    if nbt is not None:
+        ops.ema_update_i64(ema_nbt, nbt, alpha)
 
 
 # ----------------------------------------------------------------------------- optimizers on flat arenas
 def _ref_params(modules):
-    """[(module, name, offset, numel, shape)] in the reference optimizer's parameter order
+    """[(module index, offset, numel, shape)] in the reference optimizer's parameter order
     (``list(crnn.parameters()) + list(predictor.parameters())``, src/main_baseline.py:865)"""
     out = []
-    for m in modules:
+    for k, m in enumerate(modules):
         names = m.reference_param_names() if hasattr(m, "reference_param_names") else [n for n, _ in m.named_parameters()]
         for n in names:
             p = m.P(n)
-            out.append((m, n, m._poff[n], p.numel(), tuple(p.shape)))
+            out.append((k, m._poff[n], p.numel(), tuple(p.shape)))
     return out
 
 
-class FlatAdam:
+class _FlatOptimizer:
+    """What FlatAdam and FlatSGD share: the modules, and the table that maps the reference's per-parameter optimizer
+    state onto per-module arenas."""
+
+    def __init__(self, modules):
+        self.modules = list(modules)
+        self._params = _ref_params(self.modules)
+        self.step_count = 0
+
+    def zero_grad(self, set_to_none=False):
+        for m in self.modules:
+            m.flat_grad.zero_()
+
+    def _slices(self, *arenas):
+        """per parameter, in reference order: (shape, its slice of each of ``arenas``, lists of one tensor per module)"""
+        return [(shape, [a[k][off:off + n] for a in arenas]) for k, off, n, shape in self._params]
+
+
+class FlatAdam(_FlatOptimizer):
     """torch.optim.Adam(lr, betas, eps, weight_decay) over the flat arenas of several modules.  ``state_dict`` /
     ``load_state_dict`` speak torch.optim.Adam's format (per-parameter ``step`` / ``exp_avg`` / ``exp_avg_sq`` in
     the reference's parameter order, CPU tensors), so the ``optimizer`` entry of a checkpoint loads on either side."""
 
     def __init__(self, modules, lr=0.001, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
-        self.modules = list(modules)
+        super().__init__(modules)
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
-        self.step_count = 0
         self.m = [torch.zeros_like(m.flat) for m in self.modules]
         self.v = [torch.zeros_like(m.flat) for m in self.modules]
-
-    def zero_grad(self, set_to_none=False):
-        for m in self.modules:
-            m.flat_grad.zero_()
 
     def step(self, grad_scale=1.0):
         self.step_count += 1
@@ -117,15 +138,14 @@ class FlatAdam:
 
     def state_dict(self):
         state = {}
-        for i, (mod, _, off, n, shape) in enumerate(_ref_params(self.modules)):
-            k = self.modules.index(mod)
-            if self.step_count > 0:
+        if self.step_count > 0:
+            for i, (shape, (m, v)) in enumerate(self._slices(self.m, self.v)):
                 state[i] = {"step": torch.tensor(float(self.step_count)),
-                            "exp_avg": self.m[k][off:off + n].view(shape).detach().cpu().clone(),
-                            "exp_avg_sq": self.v[k][off:off + n].view(shape).detach().cpu().clone()}
+                            "exp_avg": m.view(shape).detach().cpu().clone(),
+                            "exp_avg_sq": v.view(shape).detach().cpu().clone()}
         group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.weight_decay,
                  "amsgrad": False, "maximize": False, "foreach": None, "capturable": False, "differentiable": False,
-                 "fused": None, "params": list(range(len(_ref_params(self.modules))))}
+                 "fused": None, "params": list(range(len(self._params)))}
         return {"state": state, "param_groups": [group]}
 
     def load_state_dict(self, sd):
@@ -137,37 +157,30 @@ class FlatAdam:
         g = sd["param_groups"][0]
         self.lr, self.betas, self.eps = g["lr"], tuple(g["betas"]), g["eps"]
         self.weight_decay = g.get("weight_decay", 0.0)
-        params = _ref_params(self.modules)
-        if len(g["params"]) != len(params):
-            raise L.BsedError(f"optimizer state has {len(g['params'])} parameters, the modules have {len(params)}")
+        if len(g["params"]) != len(self._params):
+            raise L.BsedError(f"optimizer state has {len(g['params'])} parameters, the modules have {len(self._params)}")
         steps = set()
-        for idx, (mod, _, off, n, shape) in zip(g["params"], params):
+        for idx, (_, (m, v)) in zip(g["params"], self._slices(self.m, self.v)):
             st = sd["state"].get(idx)
-            k = self.modules.index(mod)
             if st is None:
-                self.m[k][off:off + n].zero_(); self.v[k][off:off + n].zero_()
+                m.zero_(); v.zero_()
                 continue
-            self.m[k][off:off + n].copy_(torch.as_tensor(st["exp_avg"]).reshape(-1))
-            self.v[k][off:off + n].copy_(torch.as_tensor(st["exp_avg_sq"]).reshape(-1))
+            m.copy_(torch.as_tensor(st["exp_avg"]).reshape(-1))
+            v.copy_(torch.as_tensor(st["exp_avg_sq"]).reshape(-1))
             steps.add(int(st["step"]))
         if len(steps) > 1:
             raise L.BsedError(f"per-parameter step counts differ ({sorted(steps)}): one flat Adam step cannot hold them")
         self.step_count = steps.pop() if steps else 0
 
 
-class FlatSGD:
+class FlatSGD(_FlatOptimizer):
     """torch.optim.SGD(lr, momentum, nesterov=True, weight_decay) (reference main_scmt_ada_weak.py:854-866);
     state_dict in torch.optim.SGD's format (``momentum_buffer`` per parameter)."""
 
     def __init__(self, modules, lr=0.001, momentum=0.9, weight_decay=1e-4, nesterov=True):
-        self.modules = list(modules)
+        super().__init__(modules)
         self.lr, self.momentum, self.weight_decay, self.nesterov = lr, momentum, weight_decay, nesterov
-        self.step_count = 0
         self.buf = [torch.zeros_like(m.flat) for m in self.modules]
-
-    def zero_grad(self, set_to_none=False):
-        for m in self.modules:
-            m.flat_grad.zero_()
 
     def step(self, grad_scale=1.0):
         for mod, buf in zip(self.modules, self.buf):
@@ -177,31 +190,189 @@ class FlatSGD:
 
     def state_dict(self):
         state = {}
-        params = _ref_params(self.modules)
-        for i, (mod, _, off, n, shape) in enumerate(params):
-            k = self.modules.index(mod)
-            state[i] = {"momentum_buffer": (self.buf[k][off:off + n].view(shape).detach().cpu().clone()
-                                            if self.step_count > 0 else None)}
+        for i, (shape, (buf,)) in enumerate(self._slices(self.buf)):
+            state[i] = {"momentum_buffer": buf.view(shape).detach().cpu().clone() if self.step_count > 0 else None}
         group = {"lr": self.lr, "momentum": self.momentum, "dampening": 0, "weight_decay": self.weight_decay,
                  "nesterov": self.nesterov, "maximize": False, "foreach": None, "differentiable": False, "fused": None,
-                 "params": list(range(len(params)))}
+                 "params": list(range(len(self._params)))}
         return {"state": state, "param_groups": [group]}
 
     def load_state_dict(self, sd):
         g = sd["param_groups"][0]
         self.lr, self.momentum, self.weight_decay = g["lr"], g["momentum"], g.get("weight_decay", 0.0)
         self.nesterov = g.get("nesterov", True)
-        params = _ref_params(self.modules)
         seen = False
-        for idx, (mod, _, off, n, shape) in zip(g["params"], params):
-            st = sd["state"].get(idx) or {}
-            k = self.modules.index(mod)
-            mb = st.get("momentum_buffer")
+        for idx, (_, (buf,)) in zip(g["params"], self._slices(self.buf)):
+            mb = (sd["state"].get(idx) or {}).get("momentum_buffer")
             if mb is None:
-                self.buf[k][off:off + n].zero_()
+                buf.zero_()
             else:
-                self.buf[k][off:off + n].copy_(torch.as_tensor(mb).reshape(-1)); seen = True
+                buf.copy_(torch.as_tensor(mb).reshape(-1)); seen = True
         self.step_count = 1 if seen else 0      # only "first step or not" matters to the kernel
+
+
+# ----------------------------------------------------------------------------- waveform inputs, one step ahead
+class _Prefetched(NamedTuple):
+    """features of ``wav`` made on the feature stream for step ``step``; ``event`` follows the transform"""
+    wav: torch.Tensor
+    noisy: bool
+    step: int
+    feats: Any
+    event: torch.cuda.Event
+
+
+class _Uploaded(NamedTuple):
+    """the host batch ``wav`` copied into the device tensor ``slot`` for step ``step``; ``event`` follows the copy"""
+    wav: torch.Tensor
+    slot: torch.Tensor
+    event: torch.cuda.Event
+    step: int
+
+
+class _WaveInputs:
+    """The ahead-of-time staging of ``from_wave`` inputs: a feature stream on which the NEXT step's waveform -> dB-mel
+    transforms run, a copy stream on which its host waveforms are uploaded into two alternating device slots, and the
+    two tables (keyed by ``id`` of the caller's tensor) that hand the results to the step they were made for.  The
+    caller passes the step number; ``step`` always names the step that trains on the input."""
+
+    def __init__(self, frontend, device, seed, rank):
+        self.frontend, self.device, self.seed, self.rank = frontend, device, seed, rank
+        self.prefetched, self.feat_stream = {}, None
+        self.uploaded, self.copy_stream, self.slots = {}, None, {}
+
+    def device_wave(self, wav):
+        """A waveform batch as a device tensor.  Device tensors pass through.  A HOST tensor (pinned memory, if the
+        upload is to overlap anything) that ``upload_ahead`` was given was uploaded on the copy stream one step ago: the
+        current stream waits for that copy's event.  An unannounced host tensor is uploaded
+        here, on the current stream, in front of its consumer (blocking upload: the PCIe time is then inside the step)."""
+        if wav.is_cuda:
+            return wav
+        up = self.uploaded.pop(id(wav), None)
+        if up is not None and up.wav is wav:
+            cur = torch.cuda.current_stream()
+            cur.wait_event(up.event)
+            up.slot.record_stream(cur)
+            return up.slot
+        return wav.to(self.device, non_blocking=True)
+
+    def upload_ahead(self, waves, step):
+        """Start the host -> device copies of step ``step``'s waveforms, the NEXT step's, on the copy stream (the copy
+        engine works beside this step's kernels: 226 MB per 256 clips = ~4 ms of PCIe at 57 GB/s).
+        Device tensors and ``None`` are skipped.  Two device slots per
+        shape alternate: the slot refilled now held the batch of two steps ago, whose transform was enqueued on the feature
+        stream during the step before last."""
+        host = [w for w in waves if w is not None and not w.is_cuda]
+        if not host:
+            return
+        if self.copy_stream is None:
+            self.copy_stream = torch.cuda.Stream()
+        self.copy_stream.wait_stream(torch.cuda.current_stream())
+        if self.feat_stream is not None:
+            self.copy_stream.wait_stream(self.feat_stream)
+        with torch.cuda.stream(self.copy_stream):
+            for k, w in enumerate(host):
+                slots = self.slots.setdefault((k, tuple(w.shape), w.dtype), [None, None])
+                i = step % 2
+                if slots[i] is None:
+                    slots[i] = torch.empty(w.shape, dtype=w.dtype, device=self.device)
+                slots[i].copy_(w, non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record()
+                self.uploaded[id(w)] = _Uploaded(w, slots[i], ev, step)
+
+    def _transform(self, wav, step, noisy, views=None):
+        dwav = self.device_wave(wav)
+        T = self.frontend.num_frames(dwav.shape[1])
+        return self.frontend.transform(dwav, max_frames=T, noisy=noisy, views=views,
+                                       seed=parallel.rank_seed(self.seed, step, self.rank))
+
+    def features(self, wav, step, noisy=False, views=None):
+        """The dB-mel input of step ``step`` (with ``noisy``: the pair of it and its noisy twin).
+        views: (shift_frames, shift_bins) of the ISP step -- every input comes back as the triple (x, x time-rolled,
+        x frequency-rolled); such inputs are never prefetched"""
+        pre = self.prefetched.pop(id(wav), None) if views is None else None
+        if pre is not None and pre.wav is wav and (pre.noisy, pre.step) == (noisy, step):
+            # computed on the feature stream during the previous step (prefetch): same kernels, same seed, same values
+            cur = torch.cuda.current_stream()
+            cur.wait_event(pre.event)
+            for t in (pre.feats if isinstance(pre.feats, tuple) else (pre.feats,)):
+                t.record_stream(cur)
+            return pre.feats
+        return self._transform(wav, step, noisy, views)
+
+    def prefetch(self, waves, step):
+        """Enqueue the waveform -> dB-mel transforms of step ``step``, the NEXT one, on the feature stream.  Called from
+        the CRNN's recurrence hook: the two GRU layers are latency-bound and occupy half the chip (one workgroup per 4 batch
+        rows), the mel kernels run beside them.  waves: [(wav, noisy), ...]; the caller must leave the waveform tensors
+        untouched until that step has consumed them.  Host waveforms were put on the copy stream at the start
+        of this step (upload_ahead); the feature stream waits for their events."""
+        if self.feat_stream is None:
+            self.feat_stream = torch.cuda.Stream()
+        self.feat_stream.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(self.feat_stream):
+            for wav, noisy in waves:
+                feats = self._transform(wav, step, noisy)
+                ev = torch.cuda.Event()
+                ev.record()
+                self.prefetched[id(wav)] = _Prefetched(wav, noisy, step, feats, ev)
+
+    def drop_stale(self, step):
+        """Entries announced for step ``step`` or an earlier one that nobody consumed (the caller passed other tensors:
+        last batch of an epoch, a skipped batch, an exception between steps) would otherwise pin a waveform batch, its
+        feature tensors and an event forever."""
+        for table in (self.prefetched, self.uploaded):
+            for k in [k for k, v in table.items() if v.step <= step]:
+                del table[k]
+
+
+# ----------------------------------------------------------------------------- the captured step
+class _CapturedStep:
+    """Everything a held HIP graph of the plain step owns: the graph, its static inputs, the device-resident step state
+    its nodes read, and the dict of loss tensors they write.  Dropping the object returns all of it."""
+    SEED, STEP = 0, 1       # elements of ``state``: the addend of every dropout seed (uint64), of Adam's step count (int32)
+
+    def __init__(self, x, y, from_wave, device, lr, seed_inc):
+        """zero addends: the scalars the capture bakes are those of the captured step itself"""
+        self.graph = torch.cuda.CUDAGraph()
+        self.x, self.y, self.from_wave, self.seed_inc = x, y, from_wave, seed_inc
+        self.state = torch.zeros(4, device=device, dtype=torch.int64)
+        self.lr_host = float(lr)
+        self.lr = torch.full((1,), self.lr_host, device=device, dtype=torch.float32)
+        self.out = None
+
+    def _addends(self):
+        return self.state[self.SEED:self.SEED + 1].data_ptr(), self.state[self.STEP:self.STEP + 1].data_ptr()
+
+    @contextlib.contextmanager
+    def bound(self):
+        """the library reads this step state inside the block (the capture, on the capturing thread), and nowhere else"""
+        L.check(L.lib().bsed_set_step_state(*self._addends(), self.lr.data_ptr()), "bsed_set_step_state")
+        try:
+            yield
+        finally:
+            L.check(L.lib().bsed_set_step_state(None, None, None), "bsed_set_step_state")
+
+    def advance(self):
+        """one step further, in stream order: the last node of the graph, and what an eager step between replays enqueues"""
+        L.check(L.lib().bsed_step_state_advance(*self._addends(), self.seed_inc, 1, L.stream()), "bsed_step_state_advance")
+
+    def check_inputs(self, x, y):
+        for name, t, g in (("syn_x", x, self.x), ("syn_y", y, self.y)):
+            if not isinstance(t, torch.Tensor) or t.shape != g.shape or t.dtype != g.dtype or \
+                    (t.device != g.device and t.device.type != "cpu"):
+                got = (tuple(t.shape), t.dtype, t.device) if isinstance(t, torch.Tensor) else type(t).__name__
+                raise L.BsedError(f"replay_step: {name} must be {tuple(g.shape)} {g.dtype} on {g.device} as captured, "
+                                  f"got {got}")
+
+    def replay(self, x, y, lr):
+        """copy the inputs into the static tensors, refresh the device learning rate if it changed, replay"""
+        if lr != self.lr_host:
+            self.lr.fill_(lr)
+            self.lr_host = lr
+        self.x.copy_(x, non_blocking=True)
+        self.y.copy_(y, non_blocking=True)
+        self.graph.replay()
+        return self.out
 
 
 # ----------------------------------------------------------------------------- the train step
@@ -227,8 +398,6 @@ class SEDTrainer:
         self.global_step = 0
         self.seed = seed
         self.pg = process_group
-        self._prefetched, self._feat_stream = {}, None   # train_step(..., next_waves=...): features one step ahead
-        self._uploaded, self._copy_stream, self._slots = {}, None, {}   # host waveforms: uploads one step ahead
         # mean teacher: the EMA pair's forward on its own stream beside the student's passes (False: inline)
         self.teacher_overlap = True
         self._teacher_stream = None
@@ -236,16 +405,22 @@ class SEDTrainer:
         # the packed weight copies a step needs, made in ONE launch at its start from the second step on
         # (ops.PackPlan; None: one launch per weight at first use, the pre-plan behaviour)
         self._pack_plans = {}
-        self._graph = None          # capture_step / replay_step / release_graph
+        self._graph = None          # a _CapturedStep: capture_step / replay_step / release_graph
         self.world = 1
         self.rank = 0
         if process_group is not None or (torch.distributed.is_available() and torch.distributed.is_initialized()):
             self.world = torch.distributed.get_world_size(process_group)
             self.rank = torch.distributed.get_rank(process_group)
+        # from_wave inputs: features and host uploads one step ahead (train_step(..., next_waves=...)); the staging keeps
+        # the front end, seed and rank it is given here and is told the step number per call: it never reads the trainer
+        self._inputs = _WaveInputs(frontend, crnn.flat.device, seed, self.rank)
         # one gradient arena for everything this rank differentiates: [CRNN (first blocks lead) | Predictor | D]
-        disc = domain_loss.domain_discriminator if domain_loss is not None else None
-        self.arena = parallel.GradArena([crnn, predictor, disc], tail_floats=crnn.tail_grad_floats(),
+        self.arena = parallel.GradArena([crnn, predictor, self._disc], tail_floats=crnn.tail_grad_floats(),
                                         group=process_group)
+
+    @property
+    def _disc(self):
+        return self.domain_loss.domain_discriminator if self.domain_loss is not None else None
 
     def _plan(self, which):
         if self._pack_plans is None:
@@ -256,108 +431,60 @@ class SEDTrainer:
         """identical initial weights / statistics on every rank"""
         if self.world == 1:
             return
-        disc = self.domain_loss.domain_discriminator if self.domain_loss is not None else None
-        for m in (self.crnn, self.predictor, self.ema_crnn, self.ema_predictor, disc):
+        for m in (self.crnn, self.predictor, self.ema_crnn, self.ema_predictor, self._disc):
             if m is None:
                 continue
-            bufs = [m.flat] + ([m.flat_buf] if getattr(m, "flat_buf", None) is not None else [])
-            parallel.broadcast_flat(bufs, src, self.pg)
-            if getattr(m, "nbt", None) is not None:
-                parallel.broadcast_flat([m.nbt], src, self.pg)
+            floats, nbt = _state_arenas(m)
+            parallel.broadcast_flat(floats, src, self.pg)
+            if nbt is not None:
+                parallel.broadcast_flat([nbt], src, self.pg)
 
-    def _device_wave(self, wav):
-        """A waveform batch as a device tensor.  Device tensors pass through.  A HOST tensor (pinned memory, if the
-        upload is to overlap anything) that a previous ``train_step(next_waves=...)`` announced was uploaded on the copy
-        stream one step ago: the current stream waits for that copy's event.  An unannounced host tensor is uploaded
-        here, on the current stream, in front of its consumer (blocking upload: the PCIe time is then inside the step)."""
-        if wav.is_cuda:
-            return wav
-        up = self._uploaded.pop(id(wav), None)
-        if up is not None and up[0] is wav:
-            cur = torch.cuda.current_stream()
-            cur.wait_event(up[2])
-            up[1].record_stream(cur)
-            return up[1]
-        return wav.to(self.crnn.flat.device, non_blocking=True)
+    # ------------------------------------------------------------------ the frame every step shares
+    def _wave_features(self, syn_x, real_x, real_x_ema, views=None):
+        """The dB-mel inputs ``(syn, real, real_ema)`` of this step from its waveforms (prefetched ones are picked up),
+        then the staging entries nobody consumed are dropped.  With the EMA teacher and no ``real_x_ema`` the noisy twin
+        of the real batch is drawn with the step's rank seed; a given ``real_x_ema`` passes through.  views: the ISP
+        step's (shift_frames, shift_bins) -- every transformed input is then the triple (x, time-rolled, frequency-rolled)."""
+        features, step = self._inputs.features, self.global_step
+        syn_x = features(syn_x, step, views=views)
+        if real_x is not None and self.ema_crnn is not None and real_x_ema is None:
+            real_x, real_x_ema = features(real_x, step, noisy=True, views=views)
+        elif real_x is not None:
+            real_x = features(real_x, step, views=views)
+        self._inputs.drop_stale(step)
+        return syn_x, real_x, real_x_ema
 
-    def _upload_ahead(self, waves, step):
-        """Start the host -> device copies of the NEXT step's waveforms on the copy stream (the copy engine works beside
-        this step's kernels: 226 MB per 256 clips = ~4 ms of PCIe at 57 GB/s).  Two device slots per
-        shape alternate: the slot refilled now held the batch of two steps ago, whose transform was enqueued on the feature
-        stream during the step before last."""
-        host = [w for w in waves if w is not None and not w.is_cuda]
-        if not host:
-            return
-        if self._copy_stream is None:
-            self._copy_stream = torch.cuda.Stream()
-        dev = self.crnn.flat.device
-        cs = self._copy_stream
-        cs.wait_stream(torch.cuda.current_stream())
-        if self._feat_stream is not None:
-            cs.wait_stream(self._feat_stream)
-        with torch.cuda.stream(cs):
-            for k, w in enumerate(host):
-                key = (k, tuple(w.shape), w.dtype)
-                slots = self._slots.setdefault(key, [None, None])
-                i = step % 2
-                if slots[i] is None:
-                    slots[i] = torch.empty(w.shape, dtype=w.dtype, device=dev)
-                slots[i].copy_(w, non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record()
-                self._uploaded[id(w)] = (w, slots[i], ev, step)
+    def _begin_step(self, adv):
+        """every module the step uses in train mode (host flags only), the gradient arena zeroed; returns the step seed"""
+        for m in (self.crnn, self.predictor, self.ema_crnn, self.ema_predictor, self._disc if adv else None):
+            if m is not None:
+                m.train()
+        self.arena.zero_()
+        return parallel.rank_seed(self.seed, self.global_step, self.rank)
 
-    def _features(self, wav, noisy=False, step=None, views=None):
-        """views: (shift_frames, shift_bins) of the ISP step -- every input comes back as the triple (x, x time-rolled,
-        x frequency-rolled); such inputs are never prefetched"""
-        pre = self._prefetched.pop(id(wav), None) if views is None else None
-        if pre is not None and pre[0] is wav and pre[1] == (noisy, self.global_step):
-            # computed on the feature stream during the previous step (train_step(..., next_waves=...)): same kernels,
-            # same seed, same values
-            torch.cuda.current_stream().wait_event(pre[3])
-            for t in (pre[2] if isinstance(pre[2], tuple) else (pre[2],)):
-                t.record_stream(torch.cuda.current_stream())
-            return pre[2]
-        dwav = self._device_wave(wav)
-        T = self.frontend.num_frames(dwav.shape[1])
-        return self.frontend.transform(dwav, max_frames=T, noisy=noisy, views=views,
-                                       seed=parallel.rank_seed(self.seed, self.global_step if step is None else step, self.rank))
-
-    def _drop_stale_inputs(self):
-        """Entries announced for this step or an earlier one that nobody consumed (the caller passed other tensors: last
-        batch of an epoch, a skipped batch, an exception between steps) would otherwise pin a waveform batch, its
-        feature tensors and an event forever."""
-        for table, tag in ((self._prefetched, lambda v: v[1][1]), (self._uploaded, lambda v: v[3])):
-            for k in [k for k, v in table.items() if tag(v) <= self.global_step]:
-                del table[k]
-
-    def _prefetch_features(self, waves):
-        """Enqueue the NEXT step's waveform -> dB-mel transforms on the feature stream.  Called from the CRNN's
-        recurrence hook: the two GRU layers are latency-bound and occupy half the chip (one workgroup per 4 batch rows),
-        the mel kernels run beside them.  waves: [(wav, noisy), ...]; the caller must leave the waveform tensors
-        untouched until the next train_step has consumed them.  Host waveforms were put on the copy stream at the start
-        of this step (_upload_ahead); the feature stream waits for their events."""
-        if self._feat_stream is None:
-            self._feat_stream = torch.cuda.Stream()
-        main = torch.cuda.current_stream()
-        self._feat_stream.wait_stream(main)
-        with torch.cuda.stream(self._feat_stream):
-            for wav, noisy in waves:
-                feats = self._features(wav, noisy=noisy, step=self.global_step + 1)
-                ev = torch.cuda.Event()
-                ev.record()
-                self._prefetched[id(wav)] = (wav, (noisy, self.global_step + 1), feats, ev)
-
-    def _teacher_forward(self, x, step_seed):
-        self.ema_crnn.train(); self.ema_predictor.train()
-        self.ema_crnn.set_seed(step_seed * 4 + 2)
+    def _teacher_forward(self, x, seed):
+        self.ema_crnn.set_seed(seed)
         enc_e, _ = self.ema_crnn.run_forward(x, save=False)
         strong_e, _, weak_e, _ = self.ema_predictor.run_forward(enc_e)
         return strong_e, weak_e
 
-    def _all_reduce_grads(self):
-        """wait for the early segment's all-reduce (started inside the last backward pass), exchange the tail"""
+    def _domain_grads(self, enc_s, enc_r, out):
+        """the domain loss on the encodings of the synthetic and the real batch; returns its feature gradients
+        (d enc_s, d enc_r), which arrive through the gradient-reverse layer"""
+        out["domain"] = self.domain_loss(None, enc_s, None, enc_r)
+        return self.domain_loss.backward_features()
+
+    def _finish_step(self, adv, ema):
+        """data-parallel gradient exchange (wait for the early segment's all-reduce, started inside the last backward
+        pass, and exchange the tail), the optimizer steps, the EMA update"""
         self.arena.finish()
+        self.optimizer.step(grad_scale=1.0 / self.world)
+        if adv:
+            self.optimizer_d.step(grad_scale=1.0 / self.world)
+        self.global_step += 1
+        if ema:
+            update_ema_variables(self.crnn, self.ema_crnn, self.ema_alpha, self.global_step)
+            update_ema_variables(self.predictor, self.ema_predictor, self.ema_alpha, self.global_step)
 
     def train_step(self, syn_x, syn_y, real_x=None, real_y_weak=None, real_x_ema=None, consistency_cost=None,
                    from_wave=False, next_waves=None):
@@ -375,7 +502,7 @@ class SEDTrainer:
                 # an eager step of a trainer that holds a graph is one step of ITS sequence: the advance the graph ends
                 # with is enqueued behind it, so the next replay continues one step later (no EMA teacher here: a
                 # trainer that has one cannot capture)
-                self._advance_step_state()
+                self._graph.advance()
             return out
         caller = torch.cuda.current_stream()
         if self._step_stream is None:
@@ -412,26 +539,18 @@ class SEDTrainer:
                 nxt = [(next_waves[0], False)]
                 if len(next_waves) > 1 and next_waves[1] is not None:
                     nxt.append((next_waves[1], mt and real_x_ema is None))
-                crnn.rnn_hook = lambda: self._prefetch_features(nxt)   # one-shot: fires at the first recurrence
-            syn_x = self._features(syn_x)
-            if real_x is not None:
-                if mt and real_x_ema is None:
-                    real_x, real_x_ema = self._features(real_x, noisy=True)
-                else:
-                    real_x = self._features(real_x)
-            self._drop_stale_inputs()
+                # one-shot: fires at the first recurrence
+                crnn.rnn_hook = lambda: self._inputs.prefetch(nxt, self.global_step + 1)
+            syn_x, real_x, real_x_ema = self._wave_features(syn_x, real_x, real_x_ema)
             if next_waves is not None:
-                self._upload_ahead(next_waves, self.global_step + 1)     # host tensors only; device tensors: no-op
-        step_seed = parallel.rank_seed(self.seed, self.global_step, self.rank)
-        crnn.train(); pred.train()
-        self.arena.zero_()
+                self._inputs.upload_ahead(next_waves, self.global_step + 1)
         adv = self.domain_loss is not None and real_x is not None
-        if adv:
-            self.domain_loss.domain_discriminator.train()
+        step_seed = self._begin_step(adv)
         out = {}
         B, Tp, C = syn_y.shape
         # (weights are constant until the optimizer step: packed / split copies of a weight tensor are made once and
         #  shared by the forward and backward passes of the step's batches -- ops.pack_cache)
+        x_ema = real_x_ema if real_x_ema is not None else real_x      # the teacher's input
         teacher = None
         if mt and self.teacher_overlap:
             # The EMA teacher's forward depends on nothing the student computes in this step: it is enqueued on its own
@@ -442,7 +561,7 @@ class SEDTrainer:
             main = torch.cuda.current_stream()
             self._teacher_stream.wait_stream(main)       # features and last step's EMA update are ordered before it
             with torch.cuda.stream(self._teacher_stream), torch.no_grad(), ops.pack_cache(self._plan("teacher")):
-                strong_e, weak_e = self._teacher_forward(real_x_ema if real_x_ema is not None else real_x, step_seed)
+                strong_e, weak_e = self._teacher_forward(x_ema, step_seed * 4 + 2)
                 ev = torch.cuda.Event()
                 ev.record()
             teacher = (strong_e, weak_e, ev)
@@ -460,8 +579,7 @@ class SEDTrainer:
                 # dropout is 0 -- SURVEY.md 8d); its feature gradients arrive through the gradient-reverse layer
                 crnn.set_seed(step_seed * 4 + 1)
                 enc_r, ctx_r = crnn.run_forward(real_x, save=True)
-                out["domain"] = self.domain_loss(None, enc_s, None, enc_r)
-                dfs, dft = self.domain_loss.backward_features()
+                dfs, dft = self._domain_grads(enc_s, enc_r, out)
                 ops.axpy(dx, dfs)
             # the gradient exchange starts inside the LAST backward pass of the step
             last_is_syn = real_x is None or not (mt or dft is not None)
@@ -482,8 +600,7 @@ class SEDTrainer:
                         weak_e.record_stream(torch.cuda.current_stream())
                     else:
                         with torch.no_grad():
-                            strong_e, weak_e = self._teacher_forward(real_x_ema if real_x_ema is not None else real_x,
-                                                                     step_seed)
+                            strong_e, weak_e = self._teacher_forward(x_ema, step_seed * 4 + 2)
                     dx, lp = pred.run_backward(enc_r, saved_r, y_weak=real_y_weak.contiguous(), ema_strong=strong_e,
                                                ema_weak=weak_e, w_cons_s=w, w_cons_w=w)
                     if dft is not None:
@@ -494,15 +611,7 @@ class SEDTrainer:
                 elif dft is not None:
                     crnn.run_backward(ctx_r, dft.contiguous(), on_early_grads=self.arena.begin_early)
                     del ctx_r
-        # ---- data-parallel gradient exchange + update
-        self._all_reduce_grads()
-        self.optimizer.step(grad_scale=1.0 / self.world)
-        if adv:
-            self.optimizer_d.step(grad_scale=1.0 / self.world)
-        self.global_step += 1
-        if mt:
-            update_ema_variables(crnn, self.ema_crnn, self.ema_alpha, self.global_step)
-            update_ema_variables(pred, self.ema_predictor, self.ema_alpha, self.global_step)
+        self._finish_step(adv, ema=mt)
         out["shape"] = (B, Tp, C)
         return out
 
@@ -518,7 +627,8 @@ class SEDTrainer:
         both advanced by the last node of the graph, and the learning rate, which ``replay_step`` refreshes from
         ``optimizer.lr``; inputs are copied into the graph's static tensors.  The library is pointed at that memory
         (``bsed_set_step_state``) only while the step is being captured, on the capturing thread: the graph's nodes carry
-        the pointers they were captured with, the trainer keeps the memory for as long as it keeps the graph, and after
+        the pointers they were captured with, the trainer keeps the memory for exactly as long as it keeps the graph (one
+        ``_CapturedStep`` owns both, and ``release_graph`` drops it), and after
         ``capture_step`` has returned or raised the library holds no pointer.  Any number of trainers of a process may
         hold a graph.  The contract,
         for every ``conv_mode`` and A/B switch of the model (tests/test_graph_step_gpu.py): a sequence of steps gives the
@@ -537,48 +647,22 @@ class SEDTrainer:
             raise L.BsedError("capture_step needs a FlatAdam optimizer: only its step count and learning rate are read "
                               "from device memory by a replayed step")
         self.release_graph()
-        dev = self.crnn.flat.device
-        self._g_x = syn_x.clone()
-        self._g_y = syn_y.clone()
-        self._g_from_wave = from_wave
+        x, y = syn_x.clone(), syn_y.clone()
         for _ in range(warmup):
-            self._train_step(self._g_x, self._g_y, from_wave=from_wave)
-        # device-resident step state: zero addends now, the baked scalars are those of THIS step
-        self._g_state = torch.zeros(4, device=dev, dtype=torch.int64)     # [0] seed addend (uint64), [1] step addend (int32)
-        self._g_lr_host = float(self.optimizer.lr)
-        self._g_lr = torch.full((1,), self._g_lr_host, device=dev, dtype=torch.float32)
-        self._g_seed_inc = (parallel.rank_seed(self.seed, 1, self.rank) - parallel.rank_seed(self.seed, 0, self.rank)) * 4
-        self._g_base_step = self.global_step
-        base_count = self.optimizer.step_count
+            self._train_step(x, y, from_wave=from_wave)
+        seed_inc = (parallel.rank_seed(self.seed, 1, self.rank) - parallel.rank_seed(self.seed, 0, self.rank)) * 4
+        step = _CapturedStep(x, y, from_wave, self.crnn.flat.device, self.optimizer.lr, seed_inc)
+        base_step, base_count = self.global_step, self.optimizer.step_count
         torch.cuda.synchronize()
-        graph = torch.cuda.CUDAGraph()
         try:
-            with self._step_state_bound(), torch.cuda.graph(graph):
-                out = self._train_step(self._g_x, self._g_y, from_wave=from_wave)
-                self._advance_step_state()
+            with step.bound(), torch.cuda.graph(step.graph):
+                step.out = self._train_step(x, y, from_wave=from_wave)
+                step.advance()
         finally:
             # the capture ran no kernel: undo its host-side bookkeeping (the first replay IS that step)
-            self.global_step = self._g_base_step
-            self.optimizer.step_count = base_count
-        self._graph, self._g_out = graph, out
+            self.global_step, self.optimizer.step_count = base_step, base_count
+        self._graph = step
         return self
-
-    @contextlib.contextmanager
-    def _step_state_bound(self):
-        """the library reads this trainer's device-resident step state inside the block (the capture), and nowhere else"""
-        s = self._g_state
-        L.check(L.lib().bsed_set_step_state(s[0:1].data_ptr(), s[1:2].data_ptr(), self._g_lr.data_ptr()),
-                "bsed_set_step_state")
-        try:
-            yield
-        finally:
-            L.check(L.lib().bsed_set_step_state(None, None, None), "bsed_set_step_state")
-
-    def _advance_step_state(self):
-        """one step further, in stream order: the last node of the graph, and what an eager step between replays enqueues"""
-        s = self._g_state
-        L.check(L.lib().bsed_step_state_advance(s[0:1].data_ptr(), s[1:2].data_ptr(), self._g_seed_inc, 1, L.stream()),
-                "bsed_step_state_advance")
 
     def replay_step(self, syn_x, syn_y):
         """One captured step on new inputs: tensors of exactly the captured shapes and dtypes, on the captured device (or
@@ -588,26 +672,15 @@ class SEDTrainer:
         if self._graph is None:
             raise L.BsedError("replay_step: this trainer holds no captured graph (capture_step makes one, release_graph "
                               "drops it)")
-        for name, t, g in (("syn_x", syn_x, self._g_x), ("syn_y", syn_y, self._g_y)):
-            if not isinstance(t, torch.Tensor) or t.shape != g.shape or t.dtype != g.dtype or \
-                    (t.device != g.device and t.device.type != "cpu"):
-                got = (tuple(t.shape), t.dtype, t.device) if isinstance(t, torch.Tensor) else type(t).__name__
-                raise L.BsedError(f"replay_step: {name} must be {tuple(g.shape)} {g.dtype} on {g.device} as captured, "
-                                  f"got {got}")
-        lr = float(self.optimizer.lr)
-        if lr != self._g_lr_host:
-            self._g_lr.fill_(lr)
-            self._g_lr_host = lr
-        self._g_x.copy_(syn_x, non_blocking=True)
-        self._g_y.copy_(syn_y, non_blocking=True)
-        self._graph.replay()
+        self._graph.check_inputs(syn_x, syn_y)
+        out = self._graph.replay(syn_x, syn_y, float(self.optimizer.lr))
         self.global_step += 1
         self.optimizer.step_count += 1
-        return self._g_out
+        return out
 
     def release_graph(self):
-        """back to eager steps only: the graph is dropped (its step state and static tensors go with the next capture or
-        with the trainer)"""
+        """back to eager steps only: the graph is dropped, and its static input tensors, its device-resident step state
+        and its output tensors go with it (a dict ``replay_step`` returned keeps its own tensors alive)"""
         self._graph = None
 
     # ------------------------------------------------------------------ ISP (shift-consistency) iteration
@@ -640,7 +713,7 @@ class SEDTrainer:
         if real_x_ema is None and not from_wave:
             raise L.BsedError("train_step_isp on dB-mel tensors needs real_x_ema (the noisy twin of the real batch); "
                               "from_wave=True draws it from the waveforms")
-        crnn, pred, ema_c, ema_p = self.crnn, self.predictor, self.ema_crnn, self.ema_predictor
+        crnn, pred = self.crnn, self.predictor
         cc = self.max_consistency_cost if consistency_cost is None else consistency_cost
         dev = crnn.flat.device
         B, Tp, C = syn_y.shape
@@ -651,21 +724,12 @@ class SEDTrainer:
         # the three inputs and their rolled views: written by the mel stage (waveforms), or rolled where they are used
         views = {}
         if from_wave:
-            views["syn"] = self._features(syn_x, views=(sh, sf))
-            if real_x_ema is None:
-                views["real"], views["ema"] = self._features(real_x, noisy=True, views=(sh, sf))
-            else:
-                views["real"] = self._features(real_x, views=(sh, sf))
-            self._drop_stale_inputs()
+            views["syn"], views["real"], ema = self._wave_features(syn_x, real_x, real_x_ema, views=(sh, sf))
             syn_x, real_x = views["syn"][0], views["real"][0]
-            if "ema" in views:
-                real_x_ema = views["ema"][0]
-        step_seed = parallel.rank_seed(self.seed, self.global_step, self.rank)
-        crnn.train(); pred.train(); ema_c.train(); ema_p.train()
-        self.arena.zero_()
+            if real_x_ema is None:
+                views["ema"], real_x_ema = ema, ema[0]
         adv = self.domain_loss is not None
-        if adv:
-            self.domain_loss.domain_discriminator.train()
+        step_seed = self._begin_step(adv)
         syn_x, real_x, real_x_ema = syn_x.contiguous(), real_x.contiguous(), real_x_ema.contiguous()
         T, F = syn_x.shape[2], syn_x.shape[3]
         base = {"syn": syn_x, "real": real_x, "ema": real_x_ema}
@@ -690,14 +754,9 @@ class SEDTrainer:
             enc_s, sv_s, ctx_s = fwd(syn_x, 0)
             enc_r, sv_r, ctx_r = fwd(real_x, 1)
             with torch.no_grad():
-                def teacher(x, slot):
-                    ema_c.set_seed(step_seed * 16 + slot)
-                    e, _ = ema_c.run_forward(x, save=False)
-                    st, _, wk, _ = ema_p.run_forward(e)
-                    return st, wk
-                strong_e, weak_e = teacher(real_x_ema, 8)
-                strong_e_sh, _ = teacher(view("ema", "t"), 9)
-                strong_e_fs, _ = teacher(view("ema", "f"), 10)
+                strong_e, weak_e = self._teacher_forward(real_x_ema, step_seed * 16 + 8)
+                strong_e_sh, _ = self._teacher_forward(view("ema", "t"), step_seed * 16 + 9)
+                strong_e_fs, _ = self._teacher_forward(view("ema", "f"), step_seed * 16 + 10)
             strong_r_roll = ops.roll(sv_r[0], B, Tp, C, sh=sp)      # detached by construction
             strong_s_roll = ops.roll(sv_s[0], B, Tp, C, sh=sp)
             y_s_roll = ops.roll(syn_y, B, Tp, C, sh=sp)
@@ -705,8 +764,7 @@ class SEDTrainer:
             if adv:
                 # domain loss on the base passes' encodings; its feature gradients arrive through the gradient-reverse
                 # layer and join the class-loss gradients of those two passes
-                out["domain"] = self.domain_loss(None, enc_s, None, enc_r)
-                dfs, dft = self.domain_loss.backward_features()
+                dfs, dft = self._domain_grads(enc_s, enc_r, out)
             dx, out["syn"] = pred.run_backward(enc_s, sv_s, y_strong=syn_y, y_weak=y_weak_syn)
             if dfs is not None:
                 ops.axpy(dx, dfs)
@@ -742,13 +800,7 @@ class SEDTrainer:
             dx, out["syn_fshift"] = pred.run_backward(enc, sv, y_strong=syn_y, y_weak=y_weak_syn)
             crnn.run_backward(ctx, dx, on_early_grads=self.arena.begin_early)
         del ctx
-        self._all_reduce_grads()
-        self.optimizer.step(grad_scale=1.0 / self.world)
-        if adv:
-            self.optimizer_d.step(grad_scale=1.0 / self.world)
-        self.global_step += 1
-        update_ema_variables(crnn, ema_c, self.ema_alpha, self.global_step)
-        update_ema_variables(pred, ema_p, self.ema_alpha, self.global_step)
+        self._finish_step(adv, ema=True)
         out["isp"] = (cc, half)
         return out
 

@@ -145,14 +145,14 @@ def test_feature_pipeline_gives_the_same_steps(mt):
             out = tr.train_step(ws, ys, wr, yw, from_wave=True, next_waves=(nxt[0], nxt[2]) if pipelined else None)
             trace.append((SEDTrainer.loss_value(out), crnn.flat.clone(), pred.flat.clone()))
         if pipelined:
-            assert len(tr._prefetched) == (2 if mt else 1)    # the fourth step's features are waiting
-            assert len(tr._uploaded) == 0                      # every announced upload was consumed by its transform
+            assert len(tr._inputs.prefetched) == (2 if mt else 1)    # the fourth step's features are waiting
+            assert len(tr._inputs.uploaded) == 0                      # every announced upload was consumed by its transform
         if pipelined == "host":
-            assert tr._copy_stream is not None and len(tr._slots) == (2 if mt else 1)
+            assert tr._inputs.copy_stream is not None and len(tr._inputs.slots) == (2 if mt else 1)
             # a step whose inputs were never announced (other tensors): the stale entries go, nothing leaks
             other = tuple(t.clone() if t is not None else None for t in data[0])
             tr.train_step(other[0], other[1], other[2], other[3], from_wave=True)
-            assert len(tr._prefetched) == 0 and len(tr._uploaded) == 0
+            assert len(tr._inputs.prefetched) == 0 and len(tr._inputs.uploaded) == 0
         runs.append(trace)
     for other_run in runs[1:]:
         for (la, ca, pa), (lb, cb, pb) in zip(runs[0], other_run):

@@ -15,6 +15,7 @@ What the cases cover (each one states the failure it would catch):
   a. every kernel route that carries a dropout seed (exact-fp32 mode, both A/B switches, the waveform front end);
   b. the masks really advance from replay to replay (guards a. against a seed frozen on BOTH sides);
   c. eager steps of the same trainer between replays (the smaller last batch of an epoch), release, re-capture;
+     release_graph frees the static inputs and the step state with the graph;
   d. a learning-rate schedule (engine.adjust_learning_rate before every step);
   e. what a held graph must not touch (the step state is bound for the capture only): a second trainer's eager steps,
      its own capture and replays interleaved with the first's, direct calls of ops.dropout / ops.adam_step, and
@@ -266,6 +267,29 @@ def test_eager_steps_between_replays_release_and_recapture(mode):
     assert [s["step_count"] for s in graph] == [4, 5, 6, 7, 8, 9, 10, 11, 12]
 
 
+def test_release_graph_frees_what_the_captured_step_owned():
+    """The static inputs and the device-resident step state belong to the captured step: release_graph drops them with
+    the graph (not the next capture, not the death of the trainer).  Weak references to the three tensors are dead after
+    the release and a collection.  The eager step after it equals the third step of the all-eager trainer: the freed
+    state took nothing the trainer steps on with it."""
+    import weakref
+    d = _batches(4)
+    script = _standard_script(d[:3]) + [("release",), ("eager", *d[3])]
+    eager = _run(_trainer(), script, graph=False)
+    tr = _trainer()
+    try:
+        for entry in script[:3]:                        # capture, replay, replay
+            _apply(tr, entry, graph=True)
+        refs = [weakref.ref(t) for t in (tr._graph.x, tr._graph.y, tr._graph.state)]
+        assert all(r() is not None for r in refs)
+        tr.release_graph()
+        gc.collect()
+        assert all(r() is None for r in refs) and tr._graph is None
+        _assert_same(_apply(tr, script[4], graph=True), eager[2], "the eager step after the release")
+    finally:
+        tr.release_graph()
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # d. learning-rate schedule
 # ------------------------------------------------------------------------------------------------------------------
@@ -357,7 +381,8 @@ def test_direct_op_calls_do_not_see_a_held_graphs_step_state():
         tr.capture_step(*d[0], warmup=3)
         for k in (1, 2):
             _assert_same(_snap(tr, SEDTrainer.loss_value(tr.replay_step(*d[k]))), eager[k - 1], f"replay {k}")
-        assert bool((tr._g_state[:2] != 0).all())       # seed addend, step addend
+        step = tr._graph
+        assert bool((step.state[[step.SEED, step.STEP]] != 0).all())       # seed addend, step addend
         during = direct()
         for k, w in before.items():
             assert torch.equal(during[k], w), f"{k} of a direct call differs in {int((during[k] != w).sum())} of " \

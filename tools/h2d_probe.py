@@ -66,8 +66,8 @@ def step_async_upload():
     # batch being trained now is free (its features were made during the previous step): refill it for step i+2.
     i = cnt[0]; cnt[0] += 1
     main = torch.cuda.current_stream()
-    if tr._feat_stream is not None:
-        copy_stream.wait_stream(tr._feat_stream)          # the previous transform of this slot has been enqueued there
+    if tr._inputs.feat_stream is not None:
+        copy_stream.wait_stream(tr._inputs.feat_stream)          # the previous transform of this slot has been enqueued there
     copy_stream.wait_stream(main)
     with torch.cuda.stream(copy_stream):
         slots[i % 2].copy_(host_pinned[i % 2], non_blocking=True)
