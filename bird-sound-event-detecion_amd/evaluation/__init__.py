@@ -17,7 +17,10 @@ counts travel to the host.  One module per subject, each importing only from tho
                 ``tag_counts_gpu``, ``validate_weak``, ``get_f_measure_by_class``, ``pseudo_label``
   validation    ``validate`` <- the reference's per-epoch validation (src/main_baseline.py:1010-1032) over a threshold
                 sweep, ``score_recording`` for a ``detect_recording`` result, and the DataFrame drop-ins ``compute_metrics``
-                and ``compute_psds_from_operating_points``; the segment-based metric stays external
+                and ``compute_psds_from_operating_points``
+
+sed_eval's segment-based metric lives beside the package, in ``bsed_amd.segment_metrics`` (``segment_counts_gpu``,
+``SegmentResult``, ``compute_sed_eval_metrics``); ``validate`` and ``score_recording`` call it on request (``segment=``).
 """
 from .._lib import BsedError
 # the private helpers that tools/ and earlier tests import from here keep resolving; they are not part of __all__

@@ -3,11 +3,14 @@
 macro average) and its threshold sweep, with -- on request -- the clip-level counts of ``tagging`` and the intersection
 counts of ``intersection`` from the same pass; ``score_recording`` applies the same counts to a ``detect_recording``
 result; ``compute_metrics`` (src/evaluation_measures.py:518-526) and ``compute_psds_from_operating_points`` (:505-510)
-are the drop-ins for DataFrames.  The segment-based metric stays external."""
+are the drop-ins for DataFrames.  sed_eval's segment-based metric, the other half of the reference's
+``compute_sed_eval_metrics`` (:318-325), is counted from the same event lists on request (``segment=``; the scorer itself
+is ``bsed_amd.segment_metrics``, beside this package)."""
 import numpy as np
 import torch
 
 from .._lib import BsedError
+from ..segment_metrics import SegmentResult, _resolution, segment_counts_gpu
 from ._common import _EVENT_COLUMNS, _batches, _check_form, _eval_mode, _forward, _required_labels
 from .clips import _learned_windows
 from .events import (MATCH_MAX_REF, EventLists, EventReference, _annotation_reference, _frame_lists, _grouped_lists, _sweep,
@@ -64,9 +67,11 @@ class ValidationResult:
     threshold; NaN counts as lowest), ``labels``, and -- on request -- ``predictions`` (one DataFrame per threshold) and
     ``groundtruth_df``; ``tagging``: the ``TaggingResult`` of the same pass when ``validate`` was given
     ``tagging_thresholds``, else None; ``intersection``: the ``PsdsResult`` of the same pass when ``validate`` was given
-    ``intersection``, else None."""
+    ``intersection``, else None; ``segment``: the ``SegmentResult`` of the same pass when ``validate`` was given ``segment``,
+    else None."""
 
-    def __init__(self, thresholds, counts, labels, predictions=None, groundtruth_df=None, tagging=None, intersection=None):
+    def __init__(self, thresholds, counts, labels, predictions=None, groundtruth_df=None, tagging=None, intersection=None,
+                 segment=None):
         self.thresholds, self.counts, self.labels = list(thresholds), counts, list(labels)
         f = event_f1(counts)
         self.class_f1, self.macro_f1, self.micro_f1 = f["class_f1"], f["macro"], f["micro"]
@@ -78,12 +83,13 @@ class ValidationResult:
         self.predictions, self.groundtruth_df = predictions, groundtruth_df
         self.tagging = tagging
         self.intersection = intersection
+        self.segment = segment
 
 
 def validate(model, dataloader, decoder, predictor=None, fpn=False, thresholds=(0.5,), median_window=1, learned_post=False,
              t_collar=0.2, percentage_of_length=0.2, pooling_time_ratio=1, sr=32000, hop_size=255, max_len_seconds=10.0,
              classwise_median_window=None, return_predictions=False, require_annotations=False, ignore_unknown=False,
-             tagging_thresholds=None, intersection=None):
+             tagging_thresholds=None, intersection=None, segment=None):
     """One validation pass, scored on the GPU: the eval-mode forward of ``get_predictions`` (same ``dataloader``, ``decoder``,
     ``predictor`` / ``fpn`` forms and the same ``annotation/<name>.txt`` files), every batch swept over ALL ``thresholds``
     (``sweep_events_gpu``: one host sync per batch) and matched against its reference (``event_counts_gpu``), the counts
@@ -98,10 +104,15 @@ def validate(model, dataloader, decoder, predictor=None, fpn=False, thresholds=(
     scored by the intersection criteria (``intersection_counts_gpu``, one more call per batch, accumulated on the device
     and read once at the end) and the ``PsdsResult`` -- counts, cross-trigger matrix, class and macro intersection F1 per
     threshold, ``.psds(...)`` over the thresholds as operating points -- hangs on ``.intersection``; every evaluated clip
-    counts ``max_len_seconds`` in the total duration.  With None the pass launches and returns what it did without it."""
+    counts ``max_len_seconds`` in the total duration.  With None the pass launches and returns what it did without it.
+    ``segment`` (opt-in): True (time resolution 1.0 s, the reference's value) or a positive resolution in seconds: the same
+    event lists are also scored by sed_eval's segment-based metric as the reference calls it, with no evaluated length
+    (``segment_counts_gpu``, one more call per batch, accumulated on the device and read once at the end) and the
+    ``SegmentResult`` hangs on ``.segment``.  With None the pass launches and returns what it did without it."""
     import pandas as pd
     _check_form("validate", predictor, fpn)
     criteria = _criteria(intersection, "validate")
+    resolution, seg_acc = _resolution(segment, "validate"), None
     isect_acc, ref_duration, n_evaluated = None, None, 0
     labels = _required_labels(decoder, "decode_strong", "validate", "decodes and scores")
     thresholds = [float(t) for t in thresholds]
@@ -134,6 +145,9 @@ def validate(model, dataloader, decoder, predictor=None, fpn=False, thresholds=(
                 durations = reference.class_durations()
                 ref_duration = durations if ref_duration is None else ref_duration + durations
                 n_evaluated += int(reference.evaluated.sum())
+            if resolution is not None:
+                seg_acc = segment_counts_gpu(events, reference, resolution, out=seg_acc,
+                                             expected_seconds=max(float(max_len_seconds), resolution))
             if return_predictions:
                 gts += dfs
                 for s, df in enumerate(events.frames(labels, names)):
@@ -149,7 +163,9 @@ def validate(model, dataloader, decoder, predictor=None, fpn=False, thresholds=(
     if criteria is not None:
         isect = PsdsResult(isect_acc[0], isect_acc[1], ref_duration, n_evaluated * float(max_len_seconds),
                            labels[:acc.shape[1]], thresholds, criteria)
-    return ValidationResult(thresholds, acc.cpu().numpy(), labels[:acc.shape[1]], predictions, groundtruth_df, tagging, isect)
+    seg = None if resolution is None else SegmentResult(*seg_acc, resolution, labels[:acc.shape[1]], thresholds)
+    return ValidationResult(thresholds, acc.cpu().numpy(), labels[:acc.shape[1]], predictions, groundtruth_df, tagging, isect,
+                            seg)
 
 
 _SEGMENT_SLACK = 1e-6       # seconds; far above the rounding of second-valued float64 differences, far below any collar
@@ -205,7 +221,7 @@ def recording_problem(events_df, groundtruth_df, labels, t_collar=0.2, ignore_un
 
 
 def score_recording(events_df, groundtruth_df, labels, t_collar=0.2, percentage_of_length=0.2, ignore_unknown=False,
-                    intersection=None, duration=None):
+                    intersection=None, duration=None, segment=None):
     """The event counts of ``validate`` for ONE recording: ``events_df`` is what ``detect_recording`` returns (a DataFrame,
     or a list of them, one per threshold), ``groundtruth_df`` has onset / offset / event_label rows in seconds of the
     recording (rows with NaN are dropped).  Returns the (S,C,3) int64 numpy counts (Ntp, Nsys, Nref); ``event_f1`` turns
@@ -216,17 +232,33 @@ def score_recording(events_df, groundtruth_df, labels, t_collar=0.2, percentage_
     ``intersection`` (opt-in, as for ``validate``): True or a ``(dtc, gtc, cttc)`` tuple returns ``(counts, PsdsResult)``
     instead: the recording scored as ONE clip by the intersection criteria (``intersection_counts_gpu``; no pieces and no
     cap: nothing is matched), each estimated list in the order of its frame, the reference sorted by onset.  ``duration``:
-    the recording's length in seconds, which only ``PsdsResult.psds`` and the false-positive rates need."""
+    the recording's length in seconds, which only ``PsdsResult.psds`` and the false-positive rates need.
+    ``segment`` (opt-in, as for ``validate``): True or a positive time resolution in seconds adds a ``SegmentResult``: the
+    recording scored as ONE clip by sed_eval's segment-based metric (``segment_counts_gpu``; no pieces and no cap), with
+    ``duration``, when given, as the evaluated length (else the recording ends with its last event of either side).
+    The return value by what was asked for:
+      neither                       ``counts``
+      ``intersection``              ``(counts, PsdsResult)``
+      ``segment``                   ``(counts, SegmentResult)``
+      ``intersection``, ``segment``  ``(counts, PsdsResult, SegmentResult)``"""
     counts, seconds, reference = recording_problem(events_df, groundtruth_df, labels, t_collar, ignore_unknown)
     events = EventLists.from_host(counts, seconds)
     event_counts = event_counts_gpu(events, reference, t_collar, percentage_of_length).cpu().numpy()
     criteria = _criteria(intersection, "score_recording")
-    if criteria is None:
+    resolution = _resolution(segment, "score_recording")
+    if criteria is None and resolution is None:
         return event_counts
     labels = list(labels)
     dfs = [df.assign(filename="recording") for df in (events_df if isinstance(events_df, (list, tuple)) else [events_df])]
     gt = None if groundtruth_df is None or len(groundtruth_df) == 0 else groundtruth_df.assign(filename="recording")
     whole = EventReference.from_frame(gt, labels, ["recording"], ignore_unknown)
     whole.evaluated[:] = True                           # a recording without a reference event is still scored
-    acc, ct = intersection_counts_gpu(_frame_lists(dfs, labels, ["recording"], "score_recording"), whole, *criteria)
-    return event_counts, PsdsResult(acc, ct, whole.class_durations(), duration, labels, None, criteria)
+    lists, out = _frame_lists(dfs, labels, ["recording"], "score_recording"), (event_counts,)
+    if criteria is not None:
+        acc, ct = intersection_counts_gpu(lists, whole, *criteria)
+        out += (PsdsResult(acc, ct, whole.class_durations(), duration, labels, None, criteria),)
+    if resolution is not None:
+        last = max(resolution, float(whole.seconds.max(initial=0.0)))       # sizes the launch when no duration is given
+        out += (SegmentResult(*segment_counts_gpu(lists, whole, resolution, duration, expected_seconds=last), resolution,
+                              labels),)
+    return out

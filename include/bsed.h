@@ -652,6 +652,45 @@ int bsed_intersection_counts(const int* est_offsets, const double* est_seconds, 
                              double gtc, double cttc, uint8_t* dtc_flags, long long* acc, long long* ct, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Segment-based counts (csrc/segment_metrics.hip, ABI 16): what sed_eval's SegmentBasedMetrics -- the second metric of
+ * the reference's compute_sed_eval_metrics (src/evaluation_measures.py:87-120, :318-325; time_resolution 1.0, no
+ * evaluated length) -- computes its F1 and error rate from.  sed_eval is not installed where this project is developed:
+ * the rules below are sed_eval's SegmentBasedMetrics AS THIS PROJECT STATES THEM, parity with sed_eval not pinned; the
+ * integer counts are the primary result, the arithmetic on them is float64 numpy on the host (segment_metrics.py).
+ *
+ * The lists are those of bsed_event_match and bsed_intersection_counts: est_offsets (S*B*C + 1), est_seconds (E,2),
+ * ref_offsets (B*C + 1), ref_seconds (R,2), float64 [onset, offset] (finite); they may overlap and need not be sorted.
+ *   segments an event covers   [max(0, floor(onset / resolution)), ceil(offset / resolution)), each quotient ONE float64
+ *                       division; when the upper end is not above the lower end the event is active nowhere: a
+ *                       zero-length event exactly on a boundary covers nothing, [1.0, 2.0] at resolution 1 covers
+ *                       segment 1 only, a negative onset starts in segment 0
+ *   segments of (s, b)  length_seconds > 0: ceil(length_seconds / resolution) for every clip, activity beyond it is cut
+ *                       off;  length_seconds == 0: the largest ceil(offset / resolution) over ALL events of both sides of
+ *                       that (threshold, clip), all classes, 0 when both sides are empty (how the reference calls
+ *                       sed_eval: no evaluated length)
+ * With A[t] / E[t] the sets of classes active in segment t in the reference / in the estimate, over the segments of the
+ * evaluated clips:
+ *   class_acc (S,C,4) int64 += (Ntp, Nfp, Nfn, Ntn): c in both / in E[t] only / in A[t] only / in neither -- the order of
+ *                       bsed_tag_counts
+ *   overall (S,4) int64 += (sum Sub, sum Del, sum Ins, number of segments), per segment with Nref = |A[t]|, Nsys = |E[t]|,
+ *                       Ntp = |A[t] & E[t]|:  Sub = min(Nref, Nsys) - Ntp,  Del = max(0, Nref - Nsys),
+ *                       Ins = max(0, Nsys - Nref)
+ * evaluated: (B) uint8 on the device, or NULL = every clip; a clip with evaluated[b] == 0 is skipped whole, both sides.
+ * Integer atomics, at most one 64-bit add per workgroup per (s, c, kind): the accumulators persist across calls (zero
+ * them first), two runs give the same bits.  expected_seconds is a host-side HINT (the list lengths are device data): it
+ * only sizes the grid's dimension over tiles of segments, which the workgroups walk with a grid stride, so every value
+ * gives the same counts; pass the length of a typical clip.  No cap on the length of a list or of a clip.  One launch, no
+ * host sync, no workspace.  Refused before any launch: null pointers (evaluated may be NULL), non-positive S, B or C,
+ * C > BSED_SEGMENT_MAX_CLASSES, a resolution or expected_seconds that is not a positive finite number, a negative or
+ * non-finite length_seconds, S*B*C beyond int32, ceil(length_seconds / resolution) beyond int32.
+ * ---------------------------------------------------------------------------------------------- */
+#define BSED_SEGMENT_MAX_CLASSES 64
+int bsed_segment_counts(const int* est_offsets, const double* est_seconds, const int* ref_offsets,
+                        const double* ref_seconds, const uint8_t* evaluated, int S, int B, int C, double resolution,
+                        double length_seconds, double expected_seconds, long long* class_acc, long long* overall,
+                        void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Clip-level tagging (csrc/tagging.hip, ABI 7): the counts behind the reference's per-class weak F1
  * (get_f_measure_by_class, src/evaluation_measures.py:346-427, intermediate_at_measures :430-446) for a whole threshold
  * sweep, and the pseudo weak labels of a batch (src/audio_tagging_inference.py:289-316).
