@@ -691,6 +691,44 @@ int bsed_segment_counts(const int* est_offsets, const double* est_seconds, const
                         void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * All-pairs statistics of an embedding (csrc/pair_stats.hip, ABI 17): what the domain gap between two sets of
+ * recordings is computed from -- the silhouette of the synth / real labelling (the number src/visualize.py prints, there
+ * on a t-SNE projection), the leave-one-out nearest-neighbour domain accuracy and the multi-kernel MMD^2
+ * (domain_gap.py does that arithmetic in float64 numpy).  The definitions are this project's own; parity with sklearn is
+ * shown only through the float64 restatement of tests/domain_gap_reference.py.
+ *
+ * x (N,D) float32, rows x_pitch >= D elements apart, base on any 4-byte boundary;  group (N) int32: a label in [0, G)
+ * or anything else = MASKED: such a point is summed into nothing and is nobody's neighbour, its own row is still
+ * produced (no label is used as an index before it is range-checked);  scale (S) float32.
+ *   d2(i,j)           = sum_k (x_ik - x_jk)^2: each difference rounded once to float32, accumulated in float32 in any
+ *                       order, FMA allowed.  The direct-difference form, NOT |x|^2 + |y|^2 - 2 x.y: embeddings of one
+ *                       model lie close together, and the cancellation of the Gram form has no bound in terms of d2
+ *   d(i,j)            = the correctly rounded float32 square root of d2(i,j)
+ *   dist_sum (N,G) float64      [i][g]    = sum over j != i with group[j] == g of (double)d(i,j)
+ *   kern_sum (N,G,S) float64    [i][g][s] = the same sum of (double)expf(-(d2(i,j) * scale[s])); not touched when S == 0
+ *   nn_d2 (N) float32, nn_index (N) int32 = the smallest d2(i,j) over the unmasked j != i and its j, the smallest j on an
+ *                       exact tie; +infinity and -1 when there is no candidate
+ * All sums over j are float64, in an order fixed by (N, D, G, S, splits): two launches with the same arguments give the
+ * same bits; no floating-point atomics.  The grid is (tiles of 64 rows) x splits: a workgroup walks its own contiguous
+ * range of the tiles of 64 columns and writes its partial sums to the workspace, a second launch adds them in split
+ * order.  splits == 0: the library's choice, bsed_pair_stats_splits(N, D) (>= 1); another value gives the same results
+ * to float64 round-off.  workspace: caller-owned device memory of at least bsed_pair_stats_workspace(N, G, S, splits)
+ * bytes (0 for arguments bsed_pair_stats would refuse; splits == 0 sizes it for the automatic choice), 8-byte aligned,
+ * contents irrelevant before and after.  Two launches, no host synchronisation.
+ * Refused before any HIP call, with a message that starts "bsed_pair_stats:": null pointers (scale and kern_sum may be
+ * NULL only when S == 0); N < 1 or above 2^30; D < 1; G outside 1..BSED_PAIR_MAX_GROUPS; S outside
+ * 0..BSED_PAIR_MAX_SCALES; x_pitch < D; splits < 0 or above 65535; a workspace smaller than the query says or not
+ * 8-byte aligned.
+ * ---------------------------------------------------------------------------------------------- */
+#define BSED_PAIR_MAX_GROUPS 8
+#define BSED_PAIR_MAX_SCALES 8
+int bsed_pair_stats_splits(int N, int D);
+size_t bsed_pair_stats_workspace(int N, int G, int S, int splits);
+int bsed_pair_stats(const float* x, long long x_pitch, int N, int D, const int* group, int G, const float* scale,
+                    int S, int splits, double* dist_sum, double* kern_sum, float* nn_d2, int* nn_index,
+                    void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Clip-level tagging (csrc/tagging.hip, ABI 7): the counts behind the reference's per-class weak F1
  * (get_f_measure_by_class, src/evaluation_measures.py:346-427, intermediate_at_measures :430-446) for a whole threshold
  * sweep, and the pseudo weak labels of a batch (src/audio_tagging_inference.py:289-316).
