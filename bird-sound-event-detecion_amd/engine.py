@@ -376,6 +376,57 @@ class _CapturedStep:
 
 
 # ----------------------------------------------------------------------------- the train step
+# ----------------------------------------------------------------------------- interpolation consistency (mixup)
+class IctPlan:
+    """The draws of one ISP iteration's interpolation consistency (mixup) passes, on the host: a mixing weight and a
+    permutation of the clips for each of the three mixed batches (reference src/main.py:387,427,460) --
+      lam_weak,   perm_weak    the weakly labelled half of the real batch, ``real[:half]``
+      lam_strong, perm_strong  the synthetic (strongly labelled) batch
+      lam_unl,    perm_unl     the unlabelled half of the real batch, ``real[half:]``
+    Checked here, without a GPU: every perm is a permutation of ``range(len(perm))`` and every lam lies in [0, 1]
+    (``BsedError`` otherwise).  ``check_sizes`` holds the perms against the batch a step is given."""
+
+    def __init__(self, lam_weak, perm_weak, lam_strong, perm_strong, lam_unl, perm_unl):
+        for name, lam, perm in (("weak", lam_weak, perm_weak), ("strong", lam_strong, perm_strong), ("unl", lam_unl, perm_unl)):
+            try:
+                lam, perm = float(lam), tuple(int(v) for v in perm)
+            except (TypeError, ValueError):
+                raise L.BsedError(f"IctPlan: lam_{name} must be a number and perm_{name} a sequence of integers") from None
+            if not 0.0 <= lam <= 1.0:          # false for NaN too
+                raise L.BsedError(f"IctPlan: lam_{name} = {lam} lies outside [0, 1]")
+            if not perm or sorted(perm) != list(range(len(perm))):
+                raise L.BsedError(f"IctPlan: perm_{name} = {list(perm)} is not a permutation of range({len(perm)})")
+            setattr(self, "lam_" + name, lam)
+            setattr(self, "perm_" + name, perm)
+
+    def check_sizes(self, n_weak, n_strong, n_unl):
+        for name, n in (("weak", n_weak), ("strong", n_strong), ("unl", n_unl)):
+            if len(getattr(self, "perm_" + name)) != n:
+                raise L.BsedError(f"IctPlan: perm_{name} permutes {len(getattr(self, 'perm_' + name))} clips, the batch "
+                                  f"has {n}")
+        return self
+
+    @property
+    def lams(self):
+        return self.lam_weak, self.lam_strong, self.lam_unl
+
+
+def draw_ict(rng, n_weak, n_strong, n_unl, sup_alpha=1.0, usup_alpha=2.0):
+    """An ``IctPlan`` drawn on the host from ``rng``, a ``numpy.random.Generator``, in the order of the reference's
+    calls (src/main.py:387,427,460): the weak half, the synthetic batch, then the unlabelled half, and for each
+    ``beta(alpha, alpha)`` then ``permutation(n)`` (mixup_data_sup / mixup_data, src/main.py:127-156; alpha =
+    mixup_sup_alpha 1.0 for the two labelled batches and mixup_usup_alpha 2.0 for the unlabelled one, :368-369).
+    ``alpha <= 0`` draws no beta and gives lam = 1, as mixup_data_sup does.  The draws are this project's own stream: the
+    reference draws from ``np.random``'s global state, and parity with that state is not claimed."""
+    draws = []
+    for n, alpha in ((n_weak, sup_alpha), (n_strong, sup_alpha), (n_unl, usup_alpha)):
+        if n < 1:
+            raise L.BsedError(f"draw_ict: every mixed batch needs at least one clip (got {n_weak}, {n_strong}, {n_unl})")
+        draws.append(float(rng.beta(alpha, alpha)) if alpha > 0.0 else 1.0)
+        draws.append(rng.permutation(n))
+    return IctPlan(*draws)
+
+
 class SEDTrainer:
     """One object = the state of a training run on ONE GPU (rank).  ``train_step`` is one iteration of the
     reference's ``train_mt`` loop body.  The dataset scaler needs no argument here: every ``from_wave`` input (prefetched
@@ -686,7 +737,7 @@ class SEDTrainer:
     # ------------------------------------------------------------------ ISP (shift-consistency) iteration
     # (no step-state advance as in train_step: ISP needs the EMA teacher, and a trainer that has one cannot hold a graph)
     def train_step_isp(self, syn_x, syn_y, real_x, real_y_weak, real_x_ema=None, shift_frames=None, shift_bins=None,
-                       consistency_cost=None, pooling_time_ratio=4, from_wave=False):
+                       consistency_cost=None, pooling_time_ratio=4, from_wave=False, ict=None):
         """One iteration of ``train_mt`` with ``-mt -ISP`` (reference src/main_baseline.py:229-277,337-420,431-529):
         on top of the mean-teacher step, time-rolled and frequency-rolled views of the synthetic and the real batch go
         through the student (4 extra forward/backward passes) and of the noisy real batch through the teacher (2 extra
@@ -703,7 +754,23 @@ class SEDTrainer:
         With a ``domain_loss`` (src/main_scmt_ada_weak.py:318-339,527-528,568-574: the script's full mode) the domain
         loss is evaluated once, on the encodings of the two base passes, its feature gradients join the base passes'
         backward through the gradient-reverse layer, and ``optimizer_d`` steps the discriminator -- the convention of
-        ``train_step``: one forward pair serves the class losses and the domain loss."""
+        ``train_step``: one forward pair serves the class losses and the domain loss.
+
+        ict: an ``IctPlan`` (``draw_ict``) adds the interpolation consistency (mixup) passes of src/main.py:366-372,
+        385-392,425-432,451-470,483 -- three more student passes and one more teacher pass.  The reference's
+        ``[weak | unlabel | strong]`` masks (main.py:367,373) map onto this step's batches: the synthetic batch is the
+        strongly labelled one, ``real[:half]`` the weakly labelled and ``real[half:]`` the unlabelled half.
+          ict_weak    student on the mix of ``real_x[:half]``: weak BCE against the mix of ``real_y_weak[:half]``
+          ict_strong  student on the mix of ``syn_x``: strong BCE against the mix of ``syn_y``
+          ict_unl     student on the mix of ``real_x[half:]``: cc * MSE(strong) + cc * MSE(weak) against the mix of the
+                      teacher's predictions on the CLEAN ``real_x[half:]`` (main.py:453-457), each mean over that pass
+        BCE is linear in its target, so BCE against the mixed target is the reference's ``mixup_criterion``.  The mixes
+        are ``ops.mix_rows`` launches: one at the start of the step (three inputs, two label tensors), one after the
+        teacher passes (its two targets); with ``from_wave`` they read the dB-mel tensors the mel stage wrote.
+        Dropout seed slots (``step_seed * 16 + slot``): student passes 0-5 as before, 6 ict_weak, 7 ict_strong,
+        11 ict_unl; teacher passes 8-10 as before, 12 the ICT teacher pass.  ``ict=None``: the step without them, launch
+        for launch.  Both halves of the real batch must then hold a clip and the perms fit the batches (``BsedError``
+        before anything is launched).  ``out`` gains "ict_weak", "ict_strong", "ict_unl" and "ict" = the three lams."""
         if self.ema_crnn is None:
             raise L.BsedError("ISP needs the EMA teacher (the reference's consistency_cost only exists with -mt)")
         if shift_frames is None or shift_bins is None:
@@ -718,6 +785,11 @@ class SEDTrainer:
         dev = crnn.flat.device
         B, Tp, C = syn_y.shape
         half = real_y_weak.shape[0] // 2
+        if ict is not None:
+            if half < 1 or B - half < 1:
+                raise L.BsedError(f"train_step_isp(ict=...) mixes the weakly labelled and the unlabelled half of the "
+                                  f"real batch: both need a clip (got {half} and {B - half})")
+            ict.check_sizes(half, B, B - half)
         sh = torch.as_tensor(list(shift_frames), dtype=torch.int32, device=dev)
         sf = torch.as_tensor(list(shift_bins), dtype=torch.int32, device=dev)
         sp = torch.as_tensor([int(v / pooling_time_ratio) for v in shift_frames], dtype=torch.int32, device=dev)
@@ -743,6 +815,14 @@ class SEDTrainer:
         y_weak_syn = ops.max_over_time(syn_y)
         n_s, n_w = B * Tp * C, B * C
         out = {"shape": (B, Tp, C)}
+        if ict is not None:
+            # the three mixed inputs and the two mixed label tensors, in one launch
+            perms = torch.as_tensor(ict.perm_weak + ict.perm_strong + ict.perm_unl, dtype=torch.int32, device=dev)
+            p_weak, p_strong, p_unl = perms[:half], perms[half:half + B], perms[half + B:]
+            real_unl = real_x[half:]
+            mix_x_weak, mix_x_syn, mix_x_unl, mix_y_weak, mix_y_syn = ops.mix_rows([
+                (real_x[:half], p_weak, ict.lam_weak), (syn_x, p_strong, ict.lam_strong), (real_unl, p_unl, ict.lam_unl),
+                (real_y_weak[:half].contiguous(), p_weak, ict.lam_weak), (syn_y, p_strong, ict.lam_strong)])
 
         def fwd(x, slot):
             crnn.set_seed(step_seed * 16 + slot)
@@ -757,6 +837,11 @@ class SEDTrainer:
                 strong_e, weak_e = self._teacher_forward(real_x_ema, step_seed * 16 + 8)
                 strong_e_sh, _ = self._teacher_forward(view("ema", "t"), step_seed * 16 + 9)
                 strong_e_fs, _ = self._teacher_forward(view("ema", "f"), step_seed * 16 + 10)
+                if ict is not None:
+                    # the teacher on the CLEAN unlabelled half (the student's input, not the noisy twin); its two
+                    # outputs mixed like the input: the targets of the ict_unl pass
+                    mix_e_strong, mix_e_weak = ops.mix_rows([(t, p_unl, ict.lam_unl) for t in
+                                                             self._teacher_forward(real_unl, step_seed * 16 + 12)])
             strong_r_roll = ops.roll(sv_r[0], B, Tp, C, sh=sp)      # detached by construction
             strong_s_roll = ops.roll(sv_s[0], B, Tp, C, sh=sp)
             y_s_roll = ops.roll(syn_y, B, Tp, C, sh=sp)
@@ -795,6 +880,20 @@ class SEDTrainer:
             enc, sv, ctx = fwd(view("syn", "t"), 4)
             dx, out["syn_shift"] = pred.run_backward(enc, sv, y_strong=y_s_roll, ema_strong=strong_s_roll, w_cons_s=0.5 * cc)
             crnn.run_backward(ctx, dx)
+            if ict is not None:
+                # interpolation consistency: the mixed weak half (weak BCE), the mixed synthetic batch (strong BCE), the
+                # mixed unlabelled half (MSE vs the mixed teacher predictions); means over each pass's own elements
+                enc, sv, ctx = fwd(mix_x_weak, 6)
+                dx, out["ict_weak"] = pred.run_backward(enc, sv, y_weak=mix_y_weak)
+                crnn.run_backward(ctx, dx)
+                enc, sv, ctx = fwd(mix_x_syn, 7)
+                dx, out["ict_strong"] = pred.run_backward(enc, sv, y_strong=mix_y_syn)
+                crnn.run_backward(ctx, dx)
+                enc, sv, ctx = fwd(mix_x_unl, 11)
+                dx, out["ict_unl"] = pred.run_backward(enc, sv, ema_strong=mix_e_strong, ema_weak=mix_e_weak,
+                                                       w_cons_s=cc, w_cons_w=cc)
+                crnn.run_backward(ctx, dx)
+                out["ict"] = ict.lams
             # synthetic, frequency shift: strong + weak BCE vs the unshifted targets
             enc, sv, ctx = fwd(view("syn", "f"), 5)
             dx, out["syn_fshift"] = pred.run_backward(enc, sv, y_strong=syn_y, y_weak=y_weak_syn)
@@ -819,9 +918,26 @@ class SEDTrainer:
         loss += 0.5 * cc * (g["syn_shift"][2] / n_s + g["real_shift"][4] / n_s)        # consistency_loss_shift
         fs = g["real_fshift_weak_half"][2] + (g["real_fshift_rest"][2] if half < B else 0.0)
         loss += 0.5 * cc * (g["real_shift"][2] / n_s + fs / n_s)                         # 1/2 (strong shift + freq shift vs EMA)
+        if "ict" in out:                                  # the four mixup terms of src/main.py:483
+            t = SEDTrainer.ict_loss_terms(out)
+            loss += t["mixup_weak_class_loss"] + t["mixup_strong_class_loss"]
+            loss += cc * (t["mixup_cons_weak_loss"] + t["mixup_cons_strong_loss"])
         if "domain" in out:
             loss += float(out["domain"])
         return float(loss)
+
+    @staticmethod
+    def ict_loss_terms(out):
+        """the four interpolation consistency terms of an ISP iteration run with an ``IctPlan``, under the names the
+        reference logs them by (src/main.py:392,432,464-470; host sync).  The two consistency terms are the plain means,
+        BEFORE the multiplication by the consistency cost, as the reference logs them."""
+        B, Tp, C = out["shape"]
+        _, half = out["isp"]
+        w, s, u = (out[k].double().sum(0).cpu() for k in ("ict_weak", "ict_strong", "ict_unl"))
+        return {"mixup_weak_class_loss": float(w[1] / (half * C)),
+                "mixup_strong_class_loss": float(s[0] / (B * Tp * C)),
+                "mixup_cons_weak_loss": float(u[3] / ((B - half) * C)),
+                "mixup_cons_strong_loss": float(u[2] / ((B - half) * Tp * C))}
 
     @staticmethod
     def loss_value(out, consistency_cost=1.0):

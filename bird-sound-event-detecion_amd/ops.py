@@ -16,6 +16,7 @@ EPI_PLAIN, EPI_STATS, EPI_GLU_POOL, EPI_GLU_BWD, EPI_ADD_STATS2 = (
 PACK_MAX_JOBS = L.CONSTANTS["BSED_PACK_MAX_JOBS"]
 REDUCE_MAX_JOBS = L.CONSTANTS["BSED_REDUCE_MAX_JOBS"]
 BN_EVAL_MAX_JOBS = L.CONSTANTS["BSED_BN_EVAL_MAX_JOBS"]
+MIX_MAX_JOBS = L.CONSTANTS["BSED_MIX_MAX_JOBS"]
 IgemmDesc, WgradDesc, HeadBwdDesc, PackJob, ReduceJob, BnEvalJob, GluDesc, GluPlan, ContractPlan = (
     L.STRUCTS["Bsed" + n] for n in ("IgemmDesc", "WgradDesc", "HeadBwdDesc", "PackJob", "ReduceJob", "BnEvalJob", "GluDesc",
                                     "GluPlan", "ContractPlan"))
@@ -1176,6 +1177,31 @@ def roll(x, B, H, W, sh=None, sw=None):
     _note("roll_kernel", "", 0.0, 8.0 * x.numel())
     L.call("bsed_roll", L.ptr(x), L.ptr(out), B, H, W, L.ptr(sh, torch.int32), L.ptr(sw, torch.int32), L.stream())
     return out
+
+
+def mix_rows(jobs):
+    """jobs: [(x, perm, lam), ...] (at most MIX_MAX_JOBS) -> [lam * x + (1 - lam) * x[perm], ...] over the rows of every
+    x, in ONE launch (the inputs, labels or teacher targets of the mixup passes; rounding rule: include/bsed.h).  x: a
+    contiguous fp32 tensor, viewed as (x.shape[0], -1); perm: an int32 device tensor of x.shape[0] entries."""
+    n = len(jobs)
+    ins, outs, perms = ((ctypes.c_void_p * n)() for _ in range(3))
+    lam, oml = (ctypes.c_float * n)(), (ctypes.c_float * n)()
+    rows, row_len = (ctypes.c_int * n)(), (ctypes.c_long * n)()
+    res, total = [], 0
+    for i, (x, perm, l) in enumerate(jobs):
+        if x.dim() < 1 or x.shape[0] < 1 or x.numel() < 1:
+            raise L.BsedError(f"mix_rows: job {i} has no rows or empty rows (shape {tuple(x.shape)})")
+        if perm.numel() != x.shape[0]:
+            raise L.BsedError(f"mix_rows: job {i} has {x.shape[0]} rows but {perm.numel()} perm entries")
+        out = torch.empty_like(x)
+        ins[i], outs[i], perms[i] = L.ptr(x).value, L.ptr(out).value, L.ptr(perm, torch.int32).value
+        lam[i], oml[i] = l, 1.0 - l          # rounded to float32 here; the subtraction is done in double
+        rows[i], row_len[i] = x.shape[0], x.numel() // x.shape[0]
+        total += x.numel()
+        res.append(out)
+    _note("mix_rows_kernel", f"{n} jobs", 3.0 * total, 12.0 * total)
+    L.call("bsed_mix_rows", ins, outs, perms, lam, oml, rows, row_len, n, L.stream())
+    return res
 
 
 def axpy(y, x, a=1.0):

@@ -904,6 +904,28 @@ int bsed_scale(float* x, long n, float s, void* stream);
 /* per-sample circular shift (torch.roll) of a (B,H,W) tensor: out[b][h][w] = in[b][(h-sh[b]) mod H][(w-sw[b]) mod W];
  * sh / sw are DEVICE int32 arrays (B) or NULL.  Reference src/main_baseline.py:229-277,374-401 (ISP views). */
 int bsed_roll(const float* in, float* out, int B, int H, int W, const int* sh, const int* sw, void* stream);
+/* Row mixing for interpolation consistency training, "mixup" (csrc/mix.hip).  replaces mixup_data_sup / mixup_data of
+ * the reference (src/main.py:127-137,143-156; called at :387,427,460), whose mixup_data takes its three tensors to the
+ * host and back.  One launch serves njobs (1..BSED_MIX_MAX_JOBS) jobs; job i mixes the rows of one (rows[i], row_len[i])
+ * tensor with the rows a permutation names:
+ *   out[r][j] = fl32( fl32(lam * in[r][j]) + fl32(oml * in[perm[r]][j]) )      r < rows, j < row_len
+ * The two products are rounded separately, then the sum -- no fused multiply-add, which would round once and give other
+ * bits.  With lam = (float)l and oml = (float)(1.0 - l), the subtraction in double, this is bit for bit what
+ * `l * x + (1 - l) * x[index, :]` gives in torch and numpy float32 on the host.  Every element of out is written once;
+ * bitwise repeatable and independent of the launch partition.
+ * The job table is seven parallel HOST arrays of njobs entries, copied into the kernel's arguments (no device allocation,
+ * no host synchronisation): in / out / perm hold DEVICE pointers (const float*, float*, const int*), perm[i] an int32
+ * array of rows[i] entries.  A job whose in, out and row_len * 4 are all multiples of 16 bytes moves 16 bytes per load
+ * and store, any other one 4; both give the same bits.
+ * perm is not validated on the device: whatever it holds, an entry outside 0 .. rows - 1 is clamped into that range, so
+ * nothing outside the job's in is dereferenced and nothing outside its out is written.
+ * Refused before any HIP call: a null table or a null pointer in a job; njobs outside 1..BSED_MIX_MAX_JOBS; rows < 1 or
+ * row_len < 1; rows * ceil(row_len / 4) of 2^31 or more; a pointer not aligned to 4 bytes; in == out or overlapping in /
+ * out ranges within a job (the gather makes mixing in place a race). */
+#define BSED_MIX_MAX_JOBS 8
+int bsed_mix_rows(const void* in /*host*/, const void* out /*host*/, const void* perm /*host*/, const float* lam /*host*/,
+                  const float* oml /*host*/, const int* rows /*host*/, const long* row_len /*host*/, int njobs,
+                  void* stream);
 /* y += a * x  (sums the class-loss and domain-loss gradients at the encoder output) */
 int bsed_axpy(float* y, const float* x, long n, float a, void* stream);
 
