@@ -11,10 +11,9 @@ embeddings (``pair_stats_gpu``; the sums as include/bsed.h states them, ``bsed_p
 The arithmetic on the sums is float64 numpy on the host and works on arrays without a GPU.  ``embed`` collects the
 embeddings of a loader on the GPU, ``load_embedded_features`` reads the dumps of ``get_predictions(saved_feature_dir=
 ...)``, ``domain_gap`` scores two sets and ``domain_gap_of`` composes the two.  The silhouette here is taken on the
-embedding itself; the reference takes it on a t-SNE projection made with a random seed, which is not rebuilt: parity
-with the number the reference prints is neither pinned nor claimed.  ``domain_gap`` takes any ``(n, D)``, so a
-projection made elsewhere can be scored too.  It lives beside the ``evaluation`` package; what it needs from the
-package is imported inside the functions that use it."""
+embedding itself; the reference takes it on a t-SNE map of the two domains, which ``bsed_amd.tsne`` makes
+(``tsne.domain_map`` scores its map with this module's silhouette: ``domain_gap`` takes any ``(n, D)``).  It lives beside
+the ``evaluation`` package; what it needs from the package is imported inside the functions that use it."""
 import ctypes
 import os
 import re

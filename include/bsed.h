@@ -729,6 +729,75 @@ int bsed_pair_stats(const float* x, long long x_pitch, int N, int D, const int* 
                     void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Exact t-SNE of an embedding at two components (csrc/tsne.hip, ABI 19): the map src/visualize.py draws of the synth and
+ * the real embeddings, by the rules of sklearn 1.7's TSNE(method="exact") -- the algorithm its default Barnes-Hut method
+ * approximates; the tree is not rebuilt.  tsne.py drives the three entry points; tests/tsne_reference.py restates them in
+ * float64 and is pinned to sklearn's own functions.  No atomics; every sum has an order fixed by the arguments, so the
+ * same arguments give the same bits.  Every entry point refuses bad arguments before any HIP call with a message that
+ * starts with its own name, and makes no host synchronisation.
+ *
+ * bsed_tsne_affinities: x (N,D) float32, rows x_pitch >= D elements apart, base on any 4-byte boundary -> P (N,N)
+ * float32 dense, beta (N) float32, sum_p one float64.  Four launches.
+ *   d2(i,j)   exactly as bsed_pair_stats defines it (direct differences in float32, the same chain over k: the same
+ *             bits); symmetric bit for bit, 0 on the diagonal.  It is written to P first.
+ *   search    per row i over the N - 1 other points, sklearn's _binary_search_perplexity in float64 (d2 converted):
+ *             beta starts at 1 with no lower and no upper bound; at most 100 steps; a step evaluates
+ *             sum = SUM_j exp(-d2 beta) (a sum of exactly 0 is read as 1e-8, rounded to float32 as sklearn's constant is)
+ *             and H = log(sum) + beta SUM_j d2 exp(-d2 beta) / sum; it stops when |H - log(perplexity)| <= 1e-5 (the
+ *             float32 value of 1e-5, likewise); otherwise, H too large: beta becomes the lower bound and is doubled
+ *             while the upper bound is infinite, else replaced by its mean with the upper bound; H too small: beta becomes
+ *             the upper bound and is halved while the lower bound is infinite, else replaced by its mean with the lower
+ *             bound.  p(j|i) = exp(-d2 beta_i) / sum at the last beta that was EVALUATED (after 100 steps that is not
+ *             the beta of the 101st), rounded to float32; beta[i] is that beta_i rounded to float32.
+ *   P_ij      = p(j|i) + p(i|j) in float32 (commutative: symmetric bit for bit), 0 on the diagonal, in place.  It is NOT
+ *             divided by its sum: sum_p = SUM_ij P_ij in float64 in a fixed order, and the gradient takes 1 / sum_p.
+ *             sklearn also clamps P_ij / sum_p from below at 2.2e-16; that is left out.
+ * The sums over a row are float64 in a fixed order (256 strided partials, a fixed tree); the row of d2 stays in LDS up to
+ * N = 32768 and is re-read from P beyond.  workspace: bsed_tsne_affinities_workspace(N) bytes (0 for an N that is
+ * refused), 8-byte aligned, caller-owned, contents irrelevant before and after.
+ * Refused: null pointers; N < 2 or N > BSED_TSNE_MAX_POINTS; D < 1; x_pitch < D; a perplexity outside (0, N); x, P or
+ * beta off a 4-byte boundary, sum_p or the workspace off an 8-byte one; a workspace smaller than the query says.
+ *
+ * bsed_tsne_gradient: sklearn's _kl_divergence at one degree of freedom.  y (N,2) float32, P as above ->
+ * grad (N,2) float32, stats three float64.  Three launches, five with want_error.
+ *   w_ij   = 1 / (1 + |y_i - y_j|^2) (float32 per pair),  Z = SUM_{i != j} w_ij,
+ *   grad_i = 4 SUM_j (exaggeration inv_sum_p P_ij - w_ij / Z) w_ij (y_i - y_j), formed as
+ *            4 (exaggeration inv_sum_p SUM_j P_ij w_ij (y_i - y_j) - (1 / Z) SUM_j w_ij^2 (y_i - y_j)): the products per
+ *            pair in float32, the four columns a thread owns added in float32, everything above that in float64;
+ *   stats[0] = Z;  stats[1] = |grad|^2, the float64 sum of the squares of the float32 values returned;
+ *   stats[2] = with want_error = 1: KL = SUM_{i != j} p log(max(p, 2.2e-16) / max(q, 2.2e-16)), q = w_ij / Z,
+ *            p = exaggeration inv_sum_p P_ij (the exaggerated P while exaggeration is not 1, as sklearn reports it), in
+ *            float64 throughout, by a second pass over P once Z is known; the logarithm is evaluated on such a launch
+ *            only.  With want_error = 0: NaN (what sklearn returns).
+ *   sklearn clamps q from below at 2.2e-16 inside the gradient too; that is left out: a gradient element differs by at
+ *   most 4 * 2.2e-16 * SUM_j w_ij |y_i - y_j| from the clamped one.
+ * The grid is (tiles of 64 rows) x splits; a workgroup streams its contiguous range of the tiles of 64 columns of P once
+ * and writes per-row partials (attraction, repulsion, sum of w) to the workspace; a second launch adds them in split
+ * order, a third forms Z in row order, the gradient and the stats.  splits == 0: the library's choice,
+ * bsed_tsne_gradient_splits(N); any other value gives the same results to float64 round-off.  workspace:
+ * bsed_tsne_gradient_workspace(N, splits) bytes (0 for arguments that are refused), 8-byte aligned.
+ * Refused: null pointers; N < 2 or N > BSED_TSNE_MAX_POINTS; inv_sum_p or exaggeration not positive and finite;
+ * want_error outside {0, 1}; splits < 0 or above 65535; misaligned pointers; a workspace too small or off an 8-byte
+ * boundary.
+ *
+ * bsed_tsne_update: sklearn's _gradient_descent step on n = 2 N elements, every operation rounded to float32 on its own
+ * (no fused multiply-add), bit for bit what numpy computes:
+ *   inc = update * grad < 0;  gains = inc ? gains + 0.2f : gains * 0.8f;  gains = gains < min_gain ? min_gain : gains;
+ *   update = momentum * update - learning_rate * (grad * gains);  y = y + update.        grad is left as it is.
+ * Refused: null pointers; n < 1 or n > 2 * BSED_TSNE_MAX_POINTS; a pointer off a 4-byte boundary.
+ * ---------------------------------------------------------------------------------------------- */
+#define BSED_TSNE_MAX_POINTS 65536
+size_t bsed_tsne_affinities_workspace(int N);
+int bsed_tsne_affinities(const float* x, long long x_pitch, int N, int D, float perplexity, float* P, float* beta,
+                         double* sum_p, void* workspace, size_t workspace_bytes, void* stream);
+int bsed_tsne_gradient_splits(int N);
+size_t bsed_tsne_gradient_workspace(int N, int splits);
+int bsed_tsne_gradient(const float* y, const float* P, int N, double inv_sum_p, double exaggeration, int want_error,
+                       int splits, float* grad, double* stats, void* workspace, size_t workspace_bytes, void* stream);
+int bsed_tsne_update(float* y, const float* grad, float* update, float* gains, long n, float momentum,
+                     float learning_rate, float min_gain, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Clip-level tagging (csrc/tagging.hip, ABI 7): the counts behind the reference's per-class weak F1
  * (get_f_measure_by_class, src/evaluation_measures.py:346-427, intermediate_at_measures :430-446) for a whole threshold
  * sweep, and the pseudo weak labels of a batch (src/audio_tagging_inference.py:289-316).
