@@ -15,7 +15,7 @@ void bsed_set_error(const char* fmt, ...) {
 extern "C" const char* bsed_last_error(void) { return g_err; }
 extern "C" const char* bsed_build_info(void) { return "libbsed gfx950: fp32 storage/accumulation, split-fp32 (bf16x3) contractions on v_mfma_f32_32x32x16_bf16 by default, "
          "exact-fp32 v_mfma_f32_32x32x2_f32 kernels selectable (hand-written HIP)"; }
-extern "C" int bsed_abi_version(void) { return 19; }   // 19: exact t-SNE of an embedding, bsed_tsne_affinities / bsed_tsne_gradient / bsed_tsne_update and their workspace queries (csrc/tsne.hip); 18: row mixing for interpolation consistency training, bsed_mix_rows (csrc/mix.hip); 17: all-pairs statistics of an embedding for the domain gap, bsed_pair_stats / bsed_pair_stats_splits / bsed_pair_stats_workspace (csrc/pair_stats.hip); 16: segment-based counts for sed_eval's segment F1 and error rate, bsed_segment_counts (csrc/segment_metrics.hip); 15: integrated loudness in LUFS, bsed_loudness / bsed_loudness_ws_bytes / bsed_kweight_coefs (csrc/loudness.hip); 14: both gradients of the HBM-bound 3 x 3 convolutions in one pass, bsed_conv_bwd3 / bsed_conv_bwd_plan, BsedWgradDesc.w3s / d_in / din_pitch (csrc/conv_bwd.hip); 13: intersection-based counts for psds_eval's macro F1 and PSDS (csrc/intersect.hip); 12: BsedContractPlan + bsed_igemm_plan / bsed_wgrad_plan for the six contraction entry points, BsedIgemmDesc.G (csrc/igemm*.hip); 11: BsedGluDesc + bsed_glu_plan for the GLU / first-block entry points (csrc/glu*.hip, csrc/block0.hip); 10: dataset scaler statistics + normalised dB kernels (csrc/scaler.hip, csrc/mel.hip); 9: soundscape synthesis (csrc/synth.hip); 8: Predictor head for 1..64 classes + bsed_head_lds_bytes (csrc/head.hip); 7: clip-level tagging counts + pseudo-label masks (csrc/tagging.hip); 6: threshold sweep + event F1 counts (csrc/metrics.hip); 5: resampling (csrc/resample.hip); 4: recording-level detection (csrc/detect.hip)
+extern "C" int bsed_abi_version(void) { return 20; }   // 20: the domain classifier, an RBF C-SVC by libsvm's rules, bsed_svc_d2 / bsed_svc_solve / bsed_svc_decision and bsed_svc_solve_workspace (csrc/svc.hip); 19: exact t-SNE of an embedding, bsed_tsne_affinities / bsed_tsne_gradient / bsed_tsne_update and their workspace queries (csrc/tsne.hip); 18: row mixing for interpolation consistency training, bsed_mix_rows (csrc/mix.hip); 17: all-pairs statistics of an embedding for the domain gap, bsed_pair_stats / bsed_pair_stats_splits / bsed_pair_stats_workspace (csrc/pair_stats.hip); 16: segment-based counts for sed_eval's segment F1 and error rate, bsed_segment_counts (csrc/segment_metrics.hip); 15: integrated loudness in LUFS, bsed_loudness / bsed_loudness_ws_bytes / bsed_kweight_coefs (csrc/loudness.hip); 14: both gradients of the HBM-bound 3 x 3 convolutions in one pass, bsed_conv_bwd3 / bsed_conv_bwd_plan, BsedWgradDesc.w3s / d_in / din_pitch (csrc/conv_bwd.hip); 13: intersection-based counts for psds_eval's macro F1 and PSDS (csrc/intersect.hip); 12: BsedContractPlan + bsed_igemm_plan / bsed_wgrad_plan for the six contraction entry points, BsedIgemmDesc.G (csrc/igemm*.hip); 11: BsedGluDesc + bsed_glu_plan for the GLU / first-block entry points (csrc/glu*.hip, csrc/block0.hip); 10: dataset scaler statistics + normalised dB kernels (csrc/scaler.hip, csrc/mel.hip); 9: soundscape synthesis (csrc/synth.hip); 8: Predictor head for 1..64 classes + bsed_head_lds_bytes (csrc/head.hip); 7: clip-level tagging counts + pseudo-label masks (csrc/tagging.hip); 6: threshold sweep + event F1 counts (csrc/metrics.hip); 5: resampling (csrc/resample.hip); 4: recording-level detection (csrc/detect.hip)
 
 // the plan of a GLU / first-block entry point (bsed_common.h): the query the callers size their buffers with
 extern "C" int bsed_glu_plan(const BsedGluDesc* desc, int kernel, BsedGluPlan* out) {

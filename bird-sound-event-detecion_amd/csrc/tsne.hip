@@ -4,12 +4,8 @@
 // include/bsed.h; tsne.py drives them.  No atomics, no fence: every sum has an order fixed by its arguments.
 //
 // Affinities, four launches:
-//   tsne_d2_kernel          grid (tiles, tiles), 256 threads: the 64 x 64 squared distances of a tile pair, 4 x 4 per
-//                           thread, through the staging loop of pair_stats.hip (its own copy here: chunks of 32 features
-//                           through LDS, rows 36 floats apart, the next chunk's loads in flight, the tail of D zero-filled;
-//                           16-byte loads when base and pitch allow it, 4-byte ones otherwise) -> P[i][j] = d2(i, j).
-//                           (a - b)^2 and (b - a)^2 have the same bits and the chain over k has one order, so d2 is
-//                           symmetric bit for bit and its diagonal is exactly 0.
+//   d2_tile_kernel          (d2_tile.h, shared with svc.hip) grid (tiles, tiles), 256 threads: the 64 x 64 squared
+//                           distances of a tile pair -> P[i][j] = d2(i, j), symmetric bit for bit, 0 on the diagonal.
 //   tsne_search_kernel      one workgroup per row.  The row of d2 stays in LDS while it fits (N <= 32768: 128 KB of the
 //                           160 KB; the sums take 128 B); past that the row is re-read from P, which the L2 holds.  Per
 //                           step every thread adds exp(-d2 beta) and d2 exp(-d2 beta) of its columns in float64, in
@@ -34,12 +30,11 @@
 // Update: one elementwise launch, products unfused (bit for bit what numpy computes in float32).
 #include "../../include/bsed.h"
 #include "bsed_common.h"
+#include "d2_tile.h"
 #include <math.h>
 
-#define TSNE_TILE 64
-#define TSNE_KC 32
-#define TSNE_LD 36                       // floats between two rows of a staged chunk
-#define TSNE_THREADS 256
+#define TSNE_TILE D2_TILE
+#define TSNE_THREADS D2_THREADS
 #define TSNE_ROW_LDS_MAX 32768           // the longest row of d2 that stays in LDS
 #define TSNE_TARGET_WORKGROUPS 1024      // what the automatic split aims at: 4 workgroups on each of 256 CUs
 #define TSNE_MAX_SPLITS 65535            // grid.y
@@ -54,20 +49,6 @@ static int tsne_auto_splits(int N) {
   if (want > tiles) want = tiles;
   if (want > TSNE_MAX_SPLITS) want = TSNE_MAX_SPLITS;
   return want < 1 ? 1 : (int)want;
-}
-
-// four features k .. k + 3 of one point; zero beyond D and for a point that does not exist
-template <bool VEC>
-__device__ __forceinline__ f32x4 tsne_load4(const float* __restrict__ x, long long pitch, int row, int N, int k, int D) {
-  f32x4 v = {0.f, 0.f, 0.f, 0.f};
-  if (row >= N || k >= D) return v;
-  const float* p = x + (size_t)row * (size_t)pitch + k;
-  if (VEC && k + 4 <= D) return *reinterpret_cast<const f32x4*>(p);
-  v[0] = p[0];
-  if (k + 1 < D) v[1] = p[1];
-  if (k + 2 < D) v[2] = p[2];
-  if (k + 3 < D) v[3] = p[3];
-  return v;
 }
 
 template <int CTRL>
@@ -102,63 +83,6 @@ __device__ __forceinline__ double tsne_block_sum(double v, double* red) {
 }
 
 // ---------------------------------------------------------------------------------------------- affinities
-template <bool VEC>
-__global__ __launch_bounds__(TSNE_THREADS) void tsne_d2_kernel(const float* __restrict__ x, long long pitch, int N, int D,
-                                                               float* __restrict__ P) {
-  __shared__ __attribute__((aligned(16))) float As[TSNE_TILE * TSNE_LD];
-  __shared__ __attribute__((aligned(16))) float Bs[TSNE_TILE * TSNE_LD];
-  const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
-  const int i0 = blockIdx.x * TSNE_TILE, j0 = blockIdx.y * TSNE_TILE;
-  const int chunks = (D + TSNE_KC - 1) / TSNE_KC;
-  const int s_row = tid >> 3, s_k = (tid & 7) * 4;
-  float acc[4][4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) acc[r][c] = 0.f;
-  f32x4 pa0 = tsne_load4<VEC>(x, pitch, i0 + s_row, N, s_k, D), pa1 = tsne_load4<VEC>(x, pitch, i0 + s_row + 32, N, s_k, D);
-  f32x4 pb0 = tsne_load4<VEC>(x, pitch, j0 + s_row, N, s_k, D), pb1 = tsne_load4<VEC>(x, pitch, j0 + s_row + 32, N, s_k, D);
-  for (int c = 0; c < chunks; ++c) {
-    __syncthreads();
-    *reinterpret_cast<f32x4*>(&As[s_row * TSNE_LD + s_k]) = pa0;
-    *reinterpret_cast<f32x4*>(&As[(s_row + 32) * TSNE_LD + s_k]) = pa1;
-    *reinterpret_cast<f32x4*>(&Bs[s_row * TSNE_LD + s_k]) = pb0;
-    *reinterpret_cast<f32x4*>(&Bs[(s_row + 32) * TSNE_LD + s_k]) = pb1;
-    __syncthreads();
-    if (c + 1 < chunks) {
-      const int k = (c + 1) * TSNE_KC + s_k;
-      pa0 = tsne_load4<VEC>(x, pitch, i0 + s_row, N, k, D); pa1 = tsne_load4<VEC>(x, pitch, i0 + s_row + 32, N, k, D);
-      pb0 = tsne_load4<VEC>(x, pitch, j0 + s_row, N, k, D); pb1 = tsne_load4<VEC>(x, pitch, j0 + s_row + 32, N, k, D);
-    }
-#pragma unroll 2
-    for (int kk = 0; kk < TSNE_KC; kk += 4) {
-      f32x4 a[4], b[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) a[r] = *reinterpret_cast<const f32x4*>(&As[(ty * 4 + r) * TSNE_LD + kk]);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) b[q] = *reinterpret_cast<const f32x4*>(&Bs[(tx + 16 * q) * TSNE_LD + kk]);
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float diff = a[r][e] - b[q][e];
-            acc[r][q] = fmaf(diff, diff, acc[r][q]);
-          }
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int row = i0 + ty * 4 + r;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int col = j0 + tx + 16 * q;
-      if (row < N && col < N) P[(size_t)row * N + col] = acc[r][q];
-    }
-  }
-}
-
 template <bool LDSROW>
 __global__ __launch_bounds__(TSNE_THREADS) void tsne_search_kernel(float* __restrict__ P, int N, double log_perplexity,
                                                                    float* __restrict__ beta_out) {
@@ -438,10 +362,7 @@ extern "C" int bsed_tsne_affinities(const float* x, long long x_pitch, int N, in
   hipStream_t s = (hipStream_t)stream;
   const int tiles = tsne_tiles(N);
   double* partial = (double*)workspace;
-  if (((uintptr_t)x % 16) == 0 && (x_pitch % 4) == 0)
-    hipLaunchKernelGGL(tsne_d2_kernel<true>, dim3(tiles, tiles), dim3(TSNE_THREADS), 0, s, x, x_pitch, N, D, P);
-  else
-    hipLaunchKernelGGL(tsne_d2_kernel<false>, dim3(tiles, tiles), dim3(TSNE_THREADS), 0, s, x, x_pitch, N, D, P);
+  d2_launch(x, x_pitch, N, D, P, s);
   BSED_LAUNCH_CHECK();
   const double log_perplexity = log((double)perplexity);
   if (N <= TSNE_ROW_LDS_MAX) {

@@ -4,8 +4,9 @@ training (src/visualize.py: ``visualization`` prints sklearn's ``silhouette_scor
 embeddings (``pair_stats_gpu``; the sums as include/bsed.h states them, ``bsed_pair_stats``):
 
 - the silhouette of the two domains (``silhouette_samples`` / ``silhouette_score``, sklearn's rules);
-- the leave-one-out nearest-neighbour domain accuracy (``nn_accuracy``) -- the cheap stand-in for the reference's SVC
-  cross-validation -- and the proxy A-distance made from it (``proxy_a_distance``);
+- the leave-one-out nearest-neighbour domain accuracy (``nn_accuracy``) -- the cheap measure that needs no training; the
+  reference's SVC cross-validation itself is ``bsed_amd.svc`` -- and the proxy A-distance made from it
+  (``proxy_a_distance``);
 - the multi-kernel MMD^2 of the domain-adaptation literature (``mmd_scales``, ``mk_mmd2``).
 
 The arithmetic on the sums is float64 numpy on the host and works on arrays without a GPU.  ``embed`` collects the

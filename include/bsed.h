@@ -798,6 +798,91 @@ int bsed_tsne_update(float* y, const float* grad, float* update, float* gains, l
                      float learning_rate, float min_gain, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Domain classifier (csrc/svc.hip, ABI 20): the cross-validated RBF support vector classifier of src/visualize.py
+ * (svm_classfication: cross_val_score(SVC(), features, target, cv=5)) by the rules of libsvm's C-SVC Solver as sklearn
+ * 1.7 runs it, restated below; shrinking is left out (it changes the path, not the optimum).  svc.py drives the three
+ * entry points; tests/svc_reference.py restates them in float64 and is pinned to sklearn.  No floating-point atomics;
+ * every sum and every choice has an order fixed by the arguments, so the same arguments give the same bits.  Every entry
+ * point refuses bad arguments before any HIP call with a message that starts with its own name, and makes no host
+ * synchronisation.  All pointers are device pointers except gamma, which is read on the HOST (that is where it is
+ * checked) and handed to the kernels by value.
+ *
+ * bsed_svc_d2: x (N,D) float32, rows x_pitch >= D elements apart, base on any 4-byte boundary -> d2 (N,N) float32
+ * dense: exactly the d2(i,j) bsed_pair_stats defines (direct differences, each rounded once to float32, one float32
+ * chain over k; not the Gram form) -- the device code bsed_tsne_affinities starts with (csrc/d2_tile.h): symmetric bit
+ * for bit, 0 on the diagonal.  One launch.
+ * Refused: null pointers; N < 1 or N > BSED_SVC_MAX_POINTS (1 GiB of d2); D < 1; x_pitch < D; x or d2 off a 4-byte
+ * boundary.
+ *
+ * bsed_svc_solve: P independent C-SVC duals  min 1/2 a^T Q a - SUM a,  0 <= a_t <= C,  SUM y_t a_t = 0,
+ * Q_ts = y_t y_s K(t,s), in ONE launch, one workgroup of 256 threads per problem.  Problem p trains on the points
+ * train_index[train_offsets[p] .. train_offsets[p+1]) (global point numbers in [0, N), any order, gaps allowed; a
+ * position t below is a place in that list); y (N) int32 holds the label +1 / -1 of every global point.
+ *   kernel    K(i,j) = (double)expf(-(gamma[p] * d2(i,j))): product and expf in float32, evaluated on the fly for the
+ *             two rows an iteration needs (nothing of K is stored); so K(i,i) = 1.
+ *   state     alpha and the gradient G = Q alpha - 1 are float64; alpha starts at 0 and G at -1.
+ *   sets      I_up = {t: y_t = +1 and alpha_t < C, or y_t = -1 and alpha_t > 0};
+ *             I_low = {t: y_t = +1 and alpha_t > 0, or y_t = -1 and alpha_t < C}  (libsvm's).
+ *   i         = argmax over I_up of -y_t G_t; Gmax is that maximum.  Gmax2 = max over I_low of y_t G_t.
+ *   stop      converged (BSED_SVC_CONVERGED) when Gmax + Gmax2 < tol; that sum, at the last evaluation, is gap[p].
+ *             Otherwise, after max_iter pair updates: BSED_SVC_NOT_CONVERGED.  info[p] = {pair updates made, status}.
+ *   j         = argmin over the t of I_low with b_t = Gmax + y_t G_t > 0 of -b_t^2 / a_t, a_t = 2 - 2 K(i,t), replaced
+ *             by TAU = 1e-12 when not positive (second-order working-set selection).
+ *   ties      in both choices go to the smallest position t.  This is this project's rule: libsvm's loops keep the
+ *             first maximum for i and the LAST minimum for j, and the path is not pinned to that.
+ *   update    libsvm's: with q = 2 - 2 K(i,j) (TAU when not positive); y_i != y_j: delta = (-G_i - G_j) / q, both alphas
+ *             plus delta, then clipped to the box along alpha_i - alpha_j = const; y_i == y_j: delta = (G_i - G_j) / q,
+ *             alpha_i minus and alpha_j plus delta, clipped along alpha_i + alpha_j = const -- the four clipping cases
+ *             of each in libsvm's order.  Then G_t += Q_ti dalpha_i + Q_tj dalpha_j for every t.
+ *   rho       libsvm's calculate_rho: the mean of y_t G_t over the free points (0 < alpha_t < C), summed in a fixed
+ *             order; without a free point (ub + lb) / 2, ub = the minimum of y_t G_t over {alpha_t = C, y_t = -1} and
+ *             {alpha_t = 0, y_t = +1}, lb = the maximum over {alpha_t = C, y_t = +1} and {alpha_t = 0, y_t = -1}.
+ *   alpha     (total_train) float64, in the order of train_index.
+ * Bad problems.  No offset or index is used as an address before it is range-checked.  A problem whose offsets do not
+ * satisfy 0 <= begin <= end <= total_train and end - begin <= max_train (BSED_SVC_BAD_OFFSETS), with an index outside
+ * [0, N) (BSED_SVC_BAD_INDEX), with a label that is not +1 / -1 (BSED_SVC_BAD_LABEL) or with one class only
+ * (BSED_SVC_ONE_CLASS; an empty list is one) writes info[p] = {0, status} and rho[p] = NaN and touches nothing else: not
+ * its alpha, not gap[p].  The other problems of the launch are unaffected.
+ * The loop is bounded by max_iter; a workgroup waits for nothing but its own barriers.
+ * Memory: alpha, G and the (index, label) of every position live in LDS while max_train <= BSED_SVC_LDS_POINTS (20 bytes
+ * a point: 120 KB of the 160 KB) and in global memory beyond (alpha in its output, the rest in the workspace); the
+ * arithmetic is the same, and so are the bits.  workspace: bsed_svc_solve_workspace(P, total_train) bytes (0 for
+ * arguments that are refused), 8-byte aligned, caller-owned, contents irrelevant before and after; it is asked for
+ * whatever max_train is and written only beyond BSED_SVC_LDS_POINTS.
+ * Refused: null pointers; N < 2 or N > BSED_SVC_MAX_POINTS; P outside 1..BSED_SVC_MAX_PROBLEMS; total_train outside
+ * 1..P * BSED_SVC_MAX_POINTS; max_train outside 1..BSED_SVC_MAX_POINTS; C, tol or a gamma[p] not positive and finite;
+ * max_iter outside 1..10 000 000; d2, y, the offsets, the indices, gamma or info off a 4-byte boundary; alpha, rho, gap
+ * or the workspace off an 8-byte one; a workspace smaller than the query says.
+ *
+ * bsed_svc_decision: for every entry e of test_index (total_test of them; problem p owns test_offsets[p] ..
+ * test_offsets[p+1]) the float64 decision value of its problem,
+ *   dec[e] = SUM_j alpha_j y_j K(test_index[e], train_index[j]) - rho[p]   over the training list of p,
+ * with the same K; the sum has a fixed order (64 partial sums over the positions j = lane, lane + 64, ..., folded by a
+ * fixed tree).  One launch for all problems, one wavefront per entry.  alpha, rho and info are bsed_svc_solve's.  NaN for
+ * an entry of a problem that solve marked bad (status above BSED_SVC_NOT_CONVERGED), of a problem whose training offsets
+ * or indices are out of range, for a test index outside [0, N) and for an entry no problem owns; no index is used as an
+ * address before it is range-checked.
+ * Refused: null pointers; N < 2 or N > BSED_SVC_MAX_POINTS; P outside 1..BSED_SVC_MAX_PROBLEMS; total_train or
+ * total_test outside 1..P * BSED_SVC_MAX_POINTS; a gamma[p] not positive and finite; misaligned pointers as above (dec
+ * on an 8-byte boundary).
+ * ---------------------------------------------------------------------------------------------- */
+#define BSED_SVC_MAX_POINTS 16384
+#define BSED_SVC_MAX_PROBLEMS 64
+#define BSED_SVC_LDS_POINTS 6144
+#define BSED_SVC_MAX_ITER 10000000
+enum { BSED_SVC_CONVERGED = 0, BSED_SVC_NOT_CONVERGED = 1, BSED_SVC_BAD_INDEX = 2, BSED_SVC_BAD_LABEL = 3,
+       BSED_SVC_ONE_CLASS = 4, BSED_SVC_BAD_OFFSETS = 5 };
+int bsed_svc_d2(const float* x, long long x_pitch, int N, int D, float* d2, void* stream);
+size_t bsed_svc_solve_workspace(int P, int total_train);
+int bsed_svc_solve(const float* d2, int N, const int* y, const int* train_offsets, const int* train_index, int P,
+                   int total_train, int max_train, const float* gamma, double C, double tol, int max_iter, double* alpha,
+                   double* rho, double* gap, int* info, void* workspace, size_t workspace_bytes, void* stream);
+int bsed_svc_decision(const float* d2, int N, const int* y, const int* train_offsets, const int* train_index,
+                      const int* test_offsets, const int* test_index, int P, int total_train, int total_test,
+                      const float* gamma, const double* alpha, const double* rho, const int* info, double* dec,
+                      void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Clip-level tagging (csrc/tagging.hip, ABI 7): the counts behind the reference's per-class weak F1
  * (get_f_measure_by_class, src/evaluation_measures.py:346-427, intermediate_at_measures :430-446) for a whole threshold
  * sweep, and the pseudo weak labels of a batch (src/audio_tagging_inference.py:289-316).

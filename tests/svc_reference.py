@@ -1,0 +1,231 @@
+"""Float64 numpy restatement of the domain classifier as include/bsed.h states it (``bsed_svc_solve``,
+``bsed_svc_decision``) and as bsed_amd/svc.py drives it: libsvm's C-SVC dual by SMO with second-order working-set
+selection and without shrinking, on a GIVEN float32 kernel matrix; the decision sum; sklearn's ``gamma="scale"``; its
+unshuffled ``StratifiedKFold``.  Nothing here is shared with the product.  tests/test_svc_reference_cpu.py pins it to
+sklearn's ``SVC`` and ``cross_val_score``; tests/test_svc_gpu.py compares the kernels with it on the GPU's own kernel
+values."""
+import numpy as np
+
+TAU = 1e-12
+CONVERGED, NOT_CONVERGED = 0, 1
+
+
+def fixture(name):
+    """the five fixtures of the issue -> (X (N, D) float32, target (N) float64: 1 for the first set, 0 for the second)"""
+    n, D, shift, drop = {"overlap": (100, 16, 1.0, 0), "apart": (100, 16, 6.0, 0), "same": (100, 16, 0.0, 0),
+                         "wide": (60, 300, 2.0, 0), "uneven": (83, 7, 1.5, 31)}[name]
+    rng = np.random.default_rng(7)
+    a = rng.normal(0, 1, (n, D))
+    b = rng.normal(0, 1, (n, D)) + shift / np.sqrt(D)
+    a, b = a.astype(np.float32), b.astype(np.float32)
+    if drop:
+        b = b[:n - drop]
+    return np.concatenate([a, b]), np.concatenate([np.ones(len(a)), np.zeros(len(b))])
+
+
+FIXTURES = ("overlap", "apart", "same", "wide", "uneven")
+
+
+SOLVER_SIZES = (2, 63, 64, 65, 255, 256, 257)             # around the wavefront (64) and the workgroup (256)
+SOLVER_CASES = tuple(f"n{n}" for n in SOLVER_SIZES) + ("fold160", "fold96", "fold108", "C0.01", "C100", "duplicates")
+
+
+def solver_case(name):
+    """one problem for the solver tests -> dict(x (N, D) float32, y (N) +-1 int, train (n) the training points in the
+    order the problem lists them (unsorted, with gaps), test (m) the points to evaluate, C, gamma float32).
+    ``n<k>``: k training points out of k + 8, the labels alternating along the list; ``fold<k>``: fold 0 of a fixture whose
+    training set has k points (overlap, wide, uneven); ``C0.01`` / ``C100``: 120 points at that C (at 0.01 every alpha ends
+    at C: no free point); ``duplicates``: 100 points, rows copied onto others of the same and of the other label."""
+    if name.startswith("fold"):
+        X, t = fixture({"fold160": "overlap", "fold96": "wide", "fold108": "uneven"}[name])
+        fold = stratified_folds(t, 5)
+        train, test = np.nonzero(fold != 0)[0], np.nonzero(fold == 0)[0]
+        assert len(train) == int(name[4:])
+        y = np.where(t == 1, 1, -1)
+        C = 1.0
+    else:
+        n, C = {"C0.01": (120, 0.01), "C100": (120, 100.0), "duplicates": (100, 1.0)}.get(name) or (int(name[1:]), 1.0)
+        rng = np.random.default_rng(1000 + n + (0 if name.startswith("n") else len(name)))
+        N, D = n + 8, 8
+        held = np.linspace(0, N - 1, 8).astype(np.int64)
+        train = rng.permutation(np.setdiff1d(np.arange(N), held))
+        y = np.empty(N, np.int64)
+        y[train] = np.where(np.arange(n) % 2 == 0, 1, -1)
+        y[held] = np.where(np.arange(8) % 2 == 0, 1, -1)
+        X = (rng.normal(0, 1, (N, D)) + (y[:, None] > 0) * (2.0 / np.sqrt(D))).astype(np.float32)
+        if name == "duplicates":
+            same = [t for t in train if y[t] == y[train[0]]][1:4]
+            other = [t for t in train if y[t] != y[train[0]]][:3]
+            X[same] = X[train[0]]                         # three copies with the label of the original
+            X[other[0]] = X[train[0]]                     # one with the other label
+            X[other[2]] = X[other[1]]
+        test = np.arange(N)
+    return dict(x=X, y=y, train=train, test=test, C=C, gamma=np.float32(scale_gamma(X[train])))
+
+
+def d2_matrix(x):
+    """(N, D) float32 -> (N, N) float64 squared distances by direct differences"""
+    x = np.asarray(x, np.float32).astype(np.float64)
+    out = np.empty((x.shape[0], x.shape[0]))
+    for i in range(x.shape[0]):
+        diff = x - x[i]
+        out[i] = np.einsum("nd,nd->n", diff, diff)
+    return out
+
+
+def kernel_matrix(d2_32, gamma):
+    """float32 d2, float32 gamma -> float32 K = exp(-(gamma * d2)), product and exponential in float32 (numpy's)"""
+    return np.exp(-(np.float32(gamma) * np.asarray(d2_32, np.float32))).astype(np.float32)
+
+
+def scale_gamma(x_train):
+    """sklearn's gamma="scale": 1 / (D * var of all elements) in float64, 1.0 for a zero variance"""
+    x = np.asarray(x_train, np.float64)
+    var = x.var()
+    return 1.0 / (x.shape[1] * var) if var != 0 else 1.0
+
+
+def stratified_folds(y, k=5):
+    """(N) labels -> (N) int fold of every point: sklearn's unshuffled StratifiedKFold.  The classes are numbered by
+    first appearance; the sorted class numbers are dealt round-robin to the k folds, which fixes how many points of each
+    class a fold tests; each class then hands its points out in their order, fold 0's share first."""
+    y = np.asarray(y)
+    classes, first = np.unique(y, return_index=True)
+    order = classes[np.argsort(first)]
+    enc = np.empty(len(y), np.int64)
+    for c, v in enumerate(order):
+        enc[y == v] = c
+    sorted_enc = np.sort(enc)
+    fold = np.empty(len(y), np.int64)
+    for c in range(len(order)):
+        share = [int((sorted_enc[f::k] == c).sum()) for f in range(k)]
+        fold[enc == c] = np.repeat(np.arange(k), share)
+    return fold
+
+
+def solve(K, y, C=1.0, tol=1e-3, max_iter=10_000_000):
+    """K (n, n) float32 kernel values, y (n) +-1 -> dict(alpha, rho, gap, iterations, status).  The rules of
+    include/bsed.h, one after the other; ties go to the smallest position (numpy's argmax / argmin)."""
+    Kd = np.asarray(K, np.float32).astype(np.float64)
+    y = np.asarray(y, np.float64)
+    n = len(y)
+    alpha, G = np.zeros(n), -np.ones(n)
+    pos = y > 0
+    it = 0
+    while True:
+        up = np.where(pos, alpha < C, alpha > 0)
+        low = np.where(pos, alpha > 0, alpha < C)
+        v = -y * G
+        vi = np.where(up, v, -np.inf)
+        i = int(np.argmax(vi))
+        gmax = vi[i]
+        gmax2 = np.where(low, -v, -np.inf).max()
+        gap = gmax + gmax2
+        if not gap >= tol:
+            status = CONVERGED
+            break
+        if it == max_iter:
+            status = NOT_CONVERGED
+            break
+        b = gmax + y * G
+        a = 2.0 - 2.0 * Kd[i]
+        a = np.where(a > 0, a, TAU)
+        obj = np.where(low & (b > 0), -(b * b) / a, np.inf)
+        j = int(np.argmin(obj))
+        quad = 2.0 - 2.0 * Kd[i, j]
+        if not quad > 0:
+            quad = TAU
+        ai, aj = alpha[i], alpha[j]
+        if y[i] != y[j]:
+            delta = (-G[i] - G[j]) / quad
+            diff = ai - aj
+            ai += delta
+            aj += delta
+            if diff > 0:
+                if aj < 0:
+                    aj, ai = 0.0, diff
+            elif ai < 0:
+                ai, aj = 0.0, -diff
+            if diff > 0:                                 # C_i - C_j = 0
+                if ai > C:
+                    ai, aj = C, C - diff
+            elif aj > C:
+                aj, ai = C, C + diff
+        else:
+            delta = (G[i] - G[j]) / quad
+            total = ai + aj
+            ai -= delta
+            aj += delta
+            if total > C:
+                if ai > C:
+                    ai, aj = C, total - C
+            elif aj < 0:
+                aj, ai = 0.0, total
+            if total > C:
+                if aj > C:
+                    aj, ai = C, total - C
+            elif ai < 0:
+                ai, aj = 0.0, total
+        dai, daj = ai - alpha[i], aj - alpha[j]
+        alpha[i], alpha[j] = ai, aj
+        G += (y * y[i]) * Kd[i] * dai + (y * y[j]) * Kd[j] * daj
+        it += 1
+    yg = y * G
+    upper, lower = alpha >= C, alpha <= 0
+    free = ~upper & ~lower
+    if free.any():
+        rho = yg[free].sum() / free.sum()
+    else:
+        ub_set = (upper & ~pos) | (lower & ~upper & pos)
+        lb_set = (upper & pos) | (lower & ~upper & ~pos)
+        ub = yg[ub_set].min() if ub_set.any() else np.inf
+        lb = yg[lb_set].max() if lb_set.any() else -np.inf
+        rho = (ub + lb) / 2.0
+    return dict(alpha=alpha, rho=float(rho), gap=float(gap), iterations=it, status=status)
+
+
+def kkt_gap(alpha, y, K, C):
+    """Gmax + Gmax2 of the stop rule, from the gradient formed afresh in float64: G = (y y^T * K) alpha - 1"""
+    Kd = np.asarray(K, np.float32).astype(np.float64)
+    y = np.asarray(y, np.float64)
+    alpha = np.asarray(alpha, np.float64)
+    G = y * (Kd @ (y * alpha)) - 1.0
+    pos = y > 0
+    up = np.where(pos, alpha < C, alpha > 0)
+    low = np.where(pos, alpha > 0, alpha < C)
+    v = -y * G
+    return float(np.where(up, v, -np.inf).max() + np.where(low, -v, -np.inf).max())
+
+
+def decision(alpha, y, rho, K_test_train):
+    """K_test_train (m, n) float32 -> (m) float64: SUM_j alpha_j y_j K(t, j) - rho"""
+    coef = np.asarray(alpha, np.float64) * np.asarray(y, np.float64)
+    return np.asarray(K_test_train, np.float32).astype(np.float64) @ coef - rho
+
+
+def cross_validate(X, target, cv=5, C=1.0, tol=1e-3, max_iter=10_000_000, d2_32=None, kernel=None):
+    """the whole of ``domain_svc``: target 1 -> y = +1, anything else -> -1 -> dict(scores, decision, fold, gamma,
+    iterations, n_support, status).  ``d2_32``: the float32 squared distances to use (default: the float64 ones rounded);
+    ``kernel(d2_32, gamma)`` -> the float32 kernel matrix of all points (default ``kernel_matrix``)."""
+    X = np.asarray(X, np.float32)
+    target = np.asarray(target)
+    y = np.where(target == 1, 1.0, -1.0)
+    if d2_32 is None:
+        d2_32 = d2_matrix(X).astype(np.float32)
+    fold = stratified_folds(target, cv)
+    dec = np.empty(len(y))
+    out = dict(scores=[], gamma=[], iterations=[], n_support=[], status=[], gap=[])
+    for f in range(cv):
+        tr, te = np.nonzero(fold != f)[0], np.nonzero(fold == f)[0]
+        gamma = np.float32(scale_gamma(X[tr]))
+        K = (kernel or kernel_matrix)(d2_32, gamma)
+        fit = solve(K[np.ix_(tr, tr)], y[tr], C, tol, max_iter)
+        dec[te] = decision(fit["alpha"], y[tr], fit["rho"], K[np.ix_(te, tr)])
+        out["scores"].append(float(((dec[te] > 0) == (y[te] > 0)).mean()))
+        out["gamma"].append(float(gamma))
+        out["iterations"].append(fit["iterations"])
+        out["n_support"].append(int((fit["alpha"] > 0).sum()))
+        out["status"].append(fit["status"])
+        out["gap"].append(fit["gap"])
+    out.update(decision=dec, fold=fold, scores=np.asarray(out["scores"]))
+    return out
