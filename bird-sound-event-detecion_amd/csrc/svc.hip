@@ -2,7 +2,7 @@
 // the dense squared distances of an embedding; svc.py runs the cross-validation of src/visualize.py on it.  The rules
 // -- the kernel values, the working-set selection and its ties, the pair update, rho, what a bad problem leaves behind
 // -- are stated in include/bsed.h.  No atomics, no fence, no waiting on another workgroup.
-//   d2_tile_kernel        (d2_tile.h, shared with tsne.hip) the squared distances.
+//   d2_tile_kernel        (d2_tile.h, shared with tsne.hip; its loop also with pair_stats.hip) the squared distances.
 //   svc_solve_kernel      one workgroup of 256 threads (four waves) per problem; thread r owns the positions r, r + 256,
 //                         ...  An iteration is two scans and one update of the owned positions with three barriers:
 //                           scan 1   -y G over I_up and y G over I_low -> one workgroup arg-max (Gmax, i, Gmax2);

@@ -4,8 +4,9 @@
 // include/bsed.h; tsne.py drives them.  No atomics, no fence: every sum has an order fixed by its arguments.
 //
 // Affinities, four launches:
-//   d2_tile_kernel          (d2_tile.h, shared with svc.hip) grid (tiles, tiles), 256 threads: the 64 x 64 squared
-//                           distances of a tile pair -> P[i][j] = d2(i, j), symmetric bit for bit, 0 on the diagonal.
+//   d2_tile_kernel          (d2_tile.h, shared with svc.hip; its loop, d2_tile_acc, also with pair_stats.hip) grid
+//                           (tiles, tiles), 256 threads: the 64 x 64 squared distances of a tile pair -> P[i][j] =
+//                           d2(i, j), symmetric bit for bit, 0 on the diagonal.
 //   tsne_search_kernel      one workgroup per row.  The row of d2 stays in LDS while it fits (N <= 32768: 128 KB of the
 //                           160 KB; the sums take 128 B); past that the row is re-read from P, which the L2 holds.  Per
 //                           step every thread adds exp(-d2 beta) and d2 exp(-d2 beta) of its columns in float64, in
@@ -21,7 +22,9 @@
 //                           per tile of 64 columns, columns 4 tx .. + 3 (one 16-byte load of P per row when P allows
 //                           it).  P is streamed once; y comes from the cache.  Per pair, in float32: w, P w dy, w^2 dy;
 //                           the four columns of a thread are added in float32 in column order, tiles in float64, the
-//                           16 threads of a row by the fixed DPP tree of pair_stats.hip.  Partials per (split, row):
+//                           16 threads of a row by the fixed DPP tree of d2_tile.h (d2_row_sum), the column tiles of
+//                           a split by its d2_split_range, the split count by d2_auto_splits: pair_stats.hip's rules.
+//                           Partials per (split, row):
 //                           attraction (2), repulsion (2), sum of w.
 //   tsne_rows_kernel        adds the partials of a row in split order.
 //   tsne_finish_kernel      one workgroup of 1024: Z in row order, then the gradient, |grad|^2 and the stats.
@@ -36,37 +39,8 @@
 #define TSNE_TILE D2_TILE
 #define TSNE_THREADS D2_THREADS
 #define TSNE_ROW_LDS_MAX 32768           // the longest row of d2 that stays in LDS
-#define TSNE_TARGET_WORKGROUPS 1024      // what the automatic split aims at: 4 workgroups on each of 256 CUs
-#define TSNE_MAX_SPLITS 65535            // grid.y
 #define TSNE_SEARCH_STEPS 100
 #define TSNE_EPS 2.220446049250313e-16   // the machine epsilon of float64: sklearn's clamp inside the logarithm
-
-static int tsne_tiles(int N) { return (N + TSNE_TILE - 1) / TSNE_TILE; }
-
-static int tsne_auto_splits(int N) {
-  const long tiles = tsne_tiles(N);
-  long want = (TSNE_TARGET_WORKGROUPS + tiles - 1) / tiles;
-  if (want > tiles) want = tiles;
-  if (want > TSNE_MAX_SPLITS) want = TSNE_MAX_SPLITS;
-  return want < 1 ? 1 : (int)want;
-}
-
-template <int CTRL>
-__device__ __forceinline__ double tsne_dpp(double p) {
-  const unsigned long long b = (unsigned long long)__double_as_longlong(p);
-  const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)b, CTRL, 0xF, 0xF, false);
-  const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(b >> 32), CTRL, 0xF, 0xF, false);
-  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-
-// the sum of p over the 16 lanes of a DPP row by a fixed tree (pair_stats.hip: pair_row_sum); every lane is active
-__device__ __forceinline__ double tsne_row_sum(double p) {
-  p += tsne_dpp<0xB1>(p);
-  p += tsne_dpp<0x4E>(p);
-  p += tsne_dpp<0x141>(p);
-  p += tsne_dpp<0x140>(p);
-  return p;
-}
 
 // the sum of v over the workgroup (a multiple of 64 threads, at most 1024), the same value in every thread: a fixed
 // tree inside each wave, then the waves in order.  red: 16 doubles of LDS; two barriers
@@ -182,8 +156,8 @@ __global__ __launch_bounds__(TSNE_THREADS) void tsne_pairs_kernel(const float* _
                                                                   int N, int splits, double* __restrict__ ws_part) {
   const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
   const int i0 = blockIdx.x * TSNE_TILE, split = blockIdx.y;
-  const int tiles = (N + TSNE_TILE - 1) / TSNE_TILE;
-  const int t_begin = (int)((long)split * tiles / splits), t_end = (int)((long)(split + 1) * tiles / splits);
+  int t_begin, t_end;
+  d2_split_range(N, split, splits, t_begin, t_end);
   float yi[4][2];
   int row[4];
   double acc[4][5];
@@ -233,7 +207,7 @@ __global__ __launch_bounds__(TSNE_THREADS) void tsne_pairs_kernel(const float* _
   for (int r = 0; r < 4; ++r)
 #pragma unroll
     for (int q = 0; q < 5; ++q) {
-      const double v = tsne_row_sum(acc[r][q]);
+      const double v = d2_row_sum(acc[r][q]);
       if (tx == 0 && row[r] < N) ws_part[((size_t)split * N + row[r]) * 5 + q] = v;
     }
 }
@@ -279,8 +253,8 @@ __global__ __launch_bounds__(TSNE_THREADS) void tsne_kl_kernel(const float* __re
   __shared__ double red[16];
   const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
   const int i0 = blockIdx.x * TSNE_TILE, split = blockIdx.y;
-  const int tiles = (N + TSNE_TILE - 1) / TSNE_TILE;
-  const int t_begin = (int)((long)split * tiles / splits), t_end = (int)((long)(split + 1) * tiles / splits);
+  int t_begin, t_end;
+  d2_split_range(N, split, splits, t_begin, t_end);
   const double Z = stats[0];
   double kl = 0.0;
   for (int r = 0; r < 4; ++r) {
@@ -302,7 +276,7 @@ __global__ __launch_bounds__(TSNE_THREADS) void tsne_kl_kernel(const float* __re
     }
   }
   kl = tsne_block_sum(kl, red);
-  if (tid == 0) ws_kl[(size_t)split * tiles + blockIdx.x] = kl;
+  if (tid == 0) ws_kl[(size_t)split * d2_tiles(N) + blockIdx.x] = kl;
 }
 
 __global__ __launch_bounds__(1024) void tsne_kl_finish_kernel(const double* __restrict__ ws_kl, size_t n,
@@ -340,7 +314,7 @@ __global__ __launch_bounds__(256) void tsne_update_kernel(float* __restrict__ y,
 // ---------------------------------------------------------------------------------------------- entry points
 extern "C" size_t bsed_tsne_affinities_workspace(int N) {
   if (N < 2 || N > BSED_TSNE_MAX_POINTS) return 0;
-  const size_t tiles = (size_t)tsne_tiles(N);
+  const size_t tiles = (size_t)d2_tiles(N);
   return tiles * tiles * sizeof(double);
 }
 
@@ -360,7 +334,7 @@ extern "C" int bsed_tsne_affinities(const float* x, long long x_pitch, int N, in
   BSED_CHECK_ARG(workspace_bytes >= need, "%s: the workspace holds %zu bytes, %zu are needed (N=%d)", who, workspace_bytes,
                  need, N);
   hipStream_t s = (hipStream_t)stream;
-  const int tiles = tsne_tiles(N);
+  const int tiles = d2_tiles(N);
   double* partial = (double*)workspace;
   d2_launch(x, x_pitch, N, D, P, s);
   BSED_LAUNCH_CHECK();
@@ -381,13 +355,13 @@ extern "C" int bsed_tsne_affinities(const float* x, long long x_pitch, int N, in
   return BSED_OK;
 }
 
-extern "C" int bsed_tsne_gradient_splits(int N) { return N < 1 ? 1 : tsne_auto_splits(N); }
+extern "C" int bsed_tsne_gradient_splits(int N) { return N < 1 ? 1 : d2_auto_splits(N); }
 
 extern "C" size_t bsed_tsne_gradient_workspace(int N, int splits) {
-  if (N < 2 || N > BSED_TSNE_MAX_POINTS || splits < 0 || splits > TSNE_MAX_SPLITS) return 0;
-  if (splits == 0) splits = tsne_auto_splits(N);
+  if (N < 2 || N > BSED_TSNE_MAX_POINTS || splits < 0 || splits > D2_MAX_SPLITS) return 0;
+  if (splits == 0) splits = d2_auto_splits(N);
   // the partials per (split, row), the sums per row, one KL partial per workgroup
-  return ((size_t)splits * N * 5 + (size_t)N * 5 + (size_t)splits * tsne_tiles(N)) * sizeof(double);
+  return ((size_t)splits * N * 5 + (size_t)N * 5 + (size_t)splits * d2_tiles(N)) * sizeof(double);
 }
 
 extern "C" int bsed_tsne_gradient(const float* y, const float* P, int N, double inv_sum_p, double exaggeration,
@@ -399,26 +373,23 @@ extern "C" int bsed_tsne_gradient(const float* y, const float* P, int N, double 
   BSED_CHECK_ARG(inv_sum_p > 0.0 && inv_sum_p < INFINITY && exaggeration > 0.0 && exaggeration < INFINITY,
                  "%s: inv_sum_p and exaggeration must be positive and finite, got %g and %g", who, inv_sum_p, exaggeration);
   BSED_CHECK_ARG(want_error == 0 || want_error == 1, "%s: want_error must be 0 or 1, got %d", who, want_error);
-  BSED_CHECK_ARG(splits >= 0 && splits <= TSNE_MAX_SPLITS, "%s: splits must be 0 (automatic) to %d, got %d", who,
-                 TSNE_MAX_SPLITS, splits);
+  BSED_CHECK_ARG(splits >= 0 && splits <= D2_MAX_SPLITS, "%s: splits must be 0 (automatic) to %d, got %d", who,
+                 D2_MAX_SPLITS, splits);
   BSED_CHECK_ARG(((uintptr_t)y % 4) == 0 && ((uintptr_t)P % 4) == 0 && ((uintptr_t)grad % 4) == 0 &&
                  ((uintptr_t)stats % 8) == 0, "%s: y, P and grad must be 4-byte aligned and stats 8-byte aligned", who);
   BSED_CHECK_ARG(((uintptr_t)workspace % 8) == 0, "%s: the workspace must be 8-byte aligned", who);
-  if (splits == 0) splits = tsne_auto_splits(N);
+  if (splits == 0) splits = d2_auto_splits(N);
   const size_t need = bsed_tsne_gradient_workspace(N, splits);
   BSED_CHECK_ARG(workspace_bytes >= need, "%s: the workspace holds %zu bytes, %zu are needed (N=%d, splits=%d)", who,
                  workspace_bytes, need, N, splits);
   hipStream_t s = (hipStream_t)stream;
-  const int tiles = tsne_tiles(N);
+  const int tiles = d2_tiles(N);
   double* ws_part = (double*)workspace;
   double* ws_rows = ws_part + (size_t)splits * N * 5;
   double* ws_kl = ws_rows + (size_t)N * 5;
-  const bool vec = ((uintptr_t)P % 16) == 0 && (N % 4) == 0;
+  const bool vec = d2_vec_ok(P, N);                                 // P's rows are N floats apart
   const double p_scale = exaggeration * inv_sum_p;
-  if (vec)
-    hipLaunchKernelGGL(tsne_pairs_kernel<true>, dim3(tiles, splits), dim3(TSNE_THREADS), 0, s, y, P, N, splits, ws_part);
-  else
-    hipLaunchKernelGGL(tsne_pairs_kernel<false>, dim3(tiles, splits), dim3(TSNE_THREADS), 0, s, y, P, N, splits, ws_part);
+  D2_LAUNCH_VEC(vec, tsne_pairs_kernel, dim3(tiles, splits), 0, s, y, P, N, splits, ws_part);
   BSED_LAUNCH_CHECK();
   hipLaunchKernelGGL(tsne_rows_kernel, dim3((unsigned)(((size_t)N * 5 + 255) / 256)), dim3(256), 0, s, ws_part, N, splits,
                      ws_rows);
@@ -426,12 +397,7 @@ extern "C" int bsed_tsne_gradient(const float* y, const float* P, int N, double 
   hipLaunchKernelGGL(tsne_finish_kernel, dim3(1), dim3(1024), 0, s, ws_rows, N, p_scale, grad, stats);
   BSED_LAUNCH_CHECK();
   if (want_error) {
-    if (vec)
-      hipLaunchKernelGGL(tsne_kl_kernel<true>, dim3(tiles, splits), dim3(TSNE_THREADS), 0, s, y, P, N, splits, p_scale,
-                         stats, ws_kl);
-    else
-      hipLaunchKernelGGL(tsne_kl_kernel<false>, dim3(tiles, splits), dim3(TSNE_THREADS), 0, s, y, P, N, splits, p_scale,
-                         stats, ws_kl);
+    D2_LAUNCH_VEC(vec, tsne_kl_kernel, dim3(tiles, splits), 0, s, y, P, N, splits, p_scale, stats, ws_kl);
     BSED_LAUNCH_CHECK();
     hipLaunchKernelGGL(tsne_kl_finish_kernel, dim3(1), dim3(1024), 0, s, ws_kl, (size_t)splits * tiles, stats);
     BSED_LAUNCH_CHECK();

@@ -13,11 +13,9 @@ The arithmetic on the sums is float64 numpy on the host and works on arrays with
 embeddings of a loader on the GPU, ``load_embedded_features`` reads the dumps of ``get_predictions(saved_feature_dir=
 ...)``, ``domain_gap`` scores two sets and ``domain_gap_of`` composes the two.  The silhouette here is taken on the
 embedding itself; the reference takes it on a t-SNE map of the two domains, which ``bsed_amd.tsne`` makes
-(``tsne.domain_map`` scores its map with this module's silhouette: ``domain_gap`` takes any ``(n, D)``).  It lives beside
-the ``evaluation`` package; what it needs from the package is imported inside the functions that use it."""
+(``tsne.domain_map`` scores its map with this module's silhouette: ``domain_gap`` takes any ``(n, D)``).  ``embed``,
+``load_embedded_features`` and the checks of the point matrix are ``_points``'s, shared with ``tsne`` and ``svc``."""
 import ctypes
-import os
-import re
 from collections import namedtuple
 
 import numpy as np
@@ -25,6 +23,8 @@ import torch
 
 from . import _lib as L
 from ._lib import BsedError
+from ._points import embed, load_embedded_features  # noqa: F401  (public names of this module)
+from ._points import embed_two, gpu_points, two_domains
 
 PAIR_MAX_GROUPS = L.CONSTANTS["BSED_PAIR_MAX_GROUPS"]
 PAIR_MAX_SCALES = L.CONSTANTS["BSED_PAIR_MAX_SCALES"]
@@ -46,17 +46,8 @@ def pair_stats_gpu(x, groups, n_groups=None, scales=(), splits=0):
     gives the same sums to float64 round-off.  Two HIP launches; the definitions are include/bsed.h's.  ``counts`` comes from
     ``torch.bincount`` over the unmasked labels, which reads a size back: the one host sync besides ``n_groups=None``."""
     who = "pair_stats_gpu"
-    if not isinstance(x, torch.Tensor) or not x.is_cuda:
-        raise BsedError(f"{who}: expected a GPU tensor")
-    if x.dtype != torch.float32 or x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
-        raise BsedError(f"{who}: x must be a (N, D) float32 tensor with N, D >= 1, got {tuple(x.shape)} {x.dtype}")
-    if x.device.index != torch._C._cuda_getDevice():
-        raise BsedError(f"{who}: x lives on cuda:{x.device.index} but the current device is "
-                        f"cuda:{torch._C._cuda_getDevice()}: wrap the call in torch.cuda.device(...)")
+    x, pitch = gpu_points(x, who)
     N, D = x.shape
-    if x.stride(1) != 1 or (N > 1 and x.stride(0) < D):
-        x = x.contiguous()
-    pitch = x.stride(0) if N > 1 else D
     groups = torch.as_tensor(groups)
     if groups.dtype not in (torch.int32, torch.int64) or tuple(groups.shape) != (N,):
         raise BsedError(f"{who}: groups must be ({N},) int32 or int64 labels, got {tuple(groups.shape)} {groups.dtype}")
@@ -198,63 +189,14 @@ def mk_mmd2(kern_sum, groups, counts, a=0, b=1, unbiased=False):
     return per, float(per.sum())
 
 
-def _points(features, level):
-    if level not in ("clip", "frame"):
-        raise BsedError(f"level must be 'clip' or 'frame', got {level!r}")
-    if features.ndim != 3:
-        raise BsedError(f"embedded features must be (B, T', F), got {tuple(features.shape)}")
-    return features.reshape(features.shape[0], -1) if level == "clip" else features.reshape(-1, features.shape[2])
-
-
-def embed(model, dataloader, predictor, fpn=False, level="clip", max_points=None, seed=0):
-    """The encoder's second output (what ``saved_feature_dir`` dumps) of every batch of ``dataloader`` in eval mode ->
-    (n, D) float32 GPU tensor; the features never leave the GPU.  ``level="clip"``: one point per clip, its (T', F)
-    features flattened (src/visualize.py:153); ``level="frame"``: one point per frame, D = F.  ``max_points``: that many
-    points drawn without replacement by a torch generator seeded with ``seed``, kept in their order."""
-    from .evaluation._common import _batches, _check_form, _eval_mode, _forward
-    _check_form("embed", predictor, fpn)
-    out = []
-    with _eval_mode(model, predictor):
-        for x, _target, _paths, _names, _folders in _batches(dataloader):
-            features = _forward(model, predictor, fpn, x, features=True)[2]
-            if features is None:
-                raise BsedError("embed: the forward handed out no features (a self-contained model, predictor=None, "
-                                "does not return the encoder's output)")
-            out.append(_points(features.float(), level))
-    if not out:
-        raise BsedError("embed: the loader is empty")
-    points = torch.cat(out, dim=0)
-    if max_points is not None and points.shape[0] > int(max_points):
-        gen = torch.Generator().manual_seed(int(seed))
-        keep = torch.randperm(points.shape[0], generator=gen)[:int(max_points)].sort().values
-        points = points[keep.to(points.device)]
-    return points.contiguous()
-
-
-def load_embedded_features(folder, level="clip"):
-    """the ``<i>.npy`` batches that ``get_predictions(saved_feature_dir=folder)`` wrote -> (n, D) float32 numpy array,
-    read in the NUMERIC order of ``i`` (0, 1, 2, ..., 10: the order the batches were made in).  The reference
-    concatenates them in ``os.listdir`` order (src/visualize.py:146-153), which is arbitrary; the measures here do not
-    depend on the order of the points, only ``nn_index`` refers to it."""
-    names = [n for n in os.listdir(folder) if re.fullmatch(r"\d+\.npy", n)]
-    if not names:
-        raise BsedError(f"load_embedded_features: no <i>.npy file in {folder}")
-    names.sort(key=lambda n: int(n[:-4]))
-    return np.concatenate([_points(np.load(os.path.join(folder, n)), level) for n in names], axis=0).astype(np.float32)
-
-
 def domain_gap(synth, real, multipliers=DAN_MULTIPLIERS, splits=0):
     """Two (n, D) sets of points (arrays or tensors; group 0 = ``synth``, group 1 = ``real``) -> ``DomainGapResult``:
     ``silhouette`` of the two-domain labelling and its ``silhouette_samples`` (synth first), ``nn_accuracy`` and the
     ``proxy_a_distance`` made from it, ``mmd2`` per multiplier (biased, Gaussian kernels at ``mmd_scales`` of the pooled
     ``mean_sq_distance``) and their sum ``mk_mmd2``, ``counts``.  One all-pairs pass on the GPU (``pair_stats_gpu``),
     float64 arithmetic on its sums on the host."""
-    L._require_gpu()
-    s, r = (torch.as_tensor(v).float().cuda() for v in (synth, real))
-    if s.dim() != 2 or r.dim() != 2 or s.shape[1] != r.shape[1] or s.shape[0] < 1 or r.shape[0] < 1:
-        raise BsedError(f"domain_gap: two non-empty (n, D) sets of the same D, got {tuple(s.shape)} and {tuple(r.shape)}")
-    x = torch.cat([s, r], dim=0)
-    groups = torch.cat([torch.zeros(s.shape[0], dtype=torch.int32), torch.ones(r.shape[0], dtype=torch.int32)])
+    x, ns, nr = two_domains(synth, real, "domain_gap")
+    groups = torch.cat([torch.zeros(ns, dtype=torch.int32), torch.ones(nr, dtype=torch.int32)])
     mean_d2 = mean_sq_distance(x)
     scales = mmd_scales(mean_d2, multipliers)
     stats = pair_stats_gpu(x, groups.to(x.device), 2, scales, splits)
@@ -268,6 +210,5 @@ def domain_gap(synth, real, multipliers=DAN_MULTIPLIERS, splits=0):
 def domain_gap_of(model, synth_loader, real_loader, predictor, fpn=False, level="clip", max_points=None, seed=0,
                   multipliers=DAN_MULTIPLIERS, splits=0):
     """``domain_gap`` of the embeddings ``embed`` makes of the two loaders with ``model`` and ``predictor``"""
-    synth = embed(model, synth_loader, predictor, fpn, level, max_points, seed)
-    real = embed(model, real_loader, predictor, fpn, level, max_points, seed)
+    synth, real = embed_two(model, synth_loader, real_loader, predictor, fpn, level, max_points, seed)
     return domain_gap(synth, real, multipliers, splits)

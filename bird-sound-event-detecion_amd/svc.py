@@ -20,6 +20,9 @@ import torch
 
 from . import _lib as L
 from ._lib import BsedError
+from ._points import check_dense_fits, embed_two, gpu_points, two_domains
+from ._points import gpu_tensor as _gpu_tensor
+from .domain_gap import proxy_a_distance
 
 SVC_MAX_POINTS = L.CONSTANTS["BSED_SVC_MAX_POINTS"]
 SVC_MAX_PROBLEMS = L.CONSTANTS["BSED_SVC_MAX_PROBLEMS"]
@@ -38,34 +41,14 @@ class SvcConvergenceWarning(UserWarning):
     """a fold's solver stopped at ``max_iter`` (what sklearn reports as a ``ConvergenceWarning``)"""
 
 
-def _gpu_tensor(x, who, name, dtype, dim):
-    if not isinstance(x, torch.Tensor) or not x.is_cuda:
-        raise BsedError(f"{who}: {name} must be a GPU tensor (there is no CPU path)")
-    if x.dtype != dtype or x.dim() != dim:
-        raise BsedError(f"{who}: {name} must be a {dim}-dimensional {dtype} tensor, got {tuple(x.shape)} {x.dtype}")
-    if x.device.index != torch._C._cuda_getDevice():
-        raise BsedError(f"{who}: {name} lives on cuda:{x.device.index} but the current device is "
-                        f"cuda:{torch._C._cuda_getDevice()}: wrap the call in torch.cuda.device(...)")
-    return x
-
-
 def svc_d2_gpu(x):
     """``x`` (N, D) float32 GPU tensor (unit stride along D, any row pitch >= D) -> ``d2`` (N, N) float32: the squared
     distances as ``bsed_pair_stats`` defines them, symmetric bit for bit with a zero diagonal.  One HIP launch, no host
     sync (include/bsed.h: ``bsed_svc_d2``)."""
     who = "svc_d2_gpu"
-    x = _gpu_tensor(x, who, "x", torch.float32, 2)
+    x, pitch = gpu_points(x, who, 1, SVC_MAX_POINTS)
     N, D = x.shape
-    if not (1 <= N <= SVC_MAX_POINTS and D >= 1):
-        raise BsedError(f"{who}: x must be (N, D) with 1 <= N <= {SVC_MAX_POINTS} and D >= 1, got {tuple(x.shape)}")
-    if x.stride(1) != 1 or (N > 1 and x.stride(0) < D):
-        x = x.contiguous()
-    pitch = x.stride(0) if N > 1 else D
-    free, _total = torch.cuda.mem_get_info(x.device)
-    free += torch.cuda.memory_reserved(x.device) - torch.cuda.memory_allocated(x.device)
-    if 4 * N * N > free:
-        raise BsedError(f"{who}: the distances of {N} points need {4 * N * N} bytes of device memory, {free} are free; "
-                        "there is no host fallback: draw fewer points")
+    check_dense_fits(N, x.device, who, "distances")
     d2 = torch.empty((N, N), device=x.device, dtype=torch.float32)
     L.call("bsed_svc_d2", ctypes.c_void_p(x.data_ptr()), pitch, N, D, L.ptr(d2), L.stream())
     return d2
@@ -259,18 +242,13 @@ def domain_svc(synth, real, cv=5, C=1.0, gamma="scale", tol=1e-3, max_iter=None)
     stops at ``max_iter`` (default ``default_max_iter`` of the largest training set) raises a ``SvcConvergenceWarning``
     naming the fold and its gap; the scores are still returned."""
     who = "domain_svc"
-    L._require_gpu()
-    s, r = (torch.as_tensor(v).float().cuda() for v in (synth, real))
-    if s.dim() != 2 or r.dim() != 2 or s.shape[1] != r.shape[1] or s.shape[0] < 1 or r.shape[0] < 1:
-        raise BsedError(f"{who}: two non-empty (n, D) sets of the same D, got {tuple(s.shape)} and {tuple(r.shape)}")
+    x, ns, nr = two_domains(synth, real, who)
     cv = int(cv)
-    ns, nr = s.shape[0], r.shape[0]
     N = ns + nr
     if not 2 <= cv <= SVC_MAX_PROBLEMS or N > SVC_MAX_POINTS:
         raise BsedError(f"{who}: 2 to {SVC_MAX_PROBLEMS} folds and at most {SVC_MAX_POINTS} points, got cv={cv}, N={N}")
     target = np.concatenate([np.ones(ns, np.int64), np.zeros(nr, np.int64)])
     fold = stratified_folds(target, cv)
-    x = torch.cat([s, r], dim=0).contiguous()
     y = torch.from_numpy(np.where(target == 1, 1, -1).astype(np.int32)).to(x.device)
     train = [np.nonzero(fold != f)[0] for f in range(cv)]
     test = [np.nonzero(fold == f)[0] for f in range(cv)]
@@ -304,7 +282,6 @@ def domain_svc(synth, real, cv=5, C=1.0, gamma="scale", tol=1e-3, max_iter=None)
                           SvcConvergenceWarning)
     scores = np.array([float(((decision[t] > 0) == (target[t] == 1)).mean()) for t in test])
     n_support = np.array([int((alpha[train_offsets[f]:train_offsets[f + 1]] > 0).sum()) for f in range(cv)])
-    from .domain_gap import proxy_a_distance
     acc = float(scores.mean())
     return DomainSvcResult(scores, acc, proxy_a_distance(acc), decision, fold, n_support, info[:, 0].astype(np.int64),
                            info[:, 1] == CONVERGED, np.asarray(gammas))
@@ -313,9 +290,7 @@ def domain_svc(synth, real, cv=5, C=1.0, gamma="scale", tol=1e-3, max_iter=None)
 def domain_svc_of(model, synth_loader, real_loader, predictor, fpn=False, level="clip", max_points=None, seed=0, **kw):
     """``domain_svc`` of the embeddings ``domain_gap.embed`` makes of the two loaders with ``model`` and ``predictor``
     (the reference classifies clips: ``level="clip"``)"""
-    from . import domain_gap as DG
-    synth = DG.embed(model, synth_loader, predictor, fpn, level, max_points, seed)
-    real = DG.embed(model, real_loader, predictor, fpn, level, max_points, seed)
+    synth, real = embed_two(model, synth_loader, real_loader, predictor, fpn, level, max_points, seed)
     return domain_svc(synth, real, **kw)
 
 

@@ -19,7 +19,9 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import domain_gap as DG
 from ._lib import BsedError
+from ._points import check_dense_fits, embed_two, gpu_matrix, gpu_points, two_domains
 
 TSNE_MAX_POINTS = L.CONSTANTS["BSED_TSNE_MAX_POINTS"]
 EXPLORATION_ITER = 250                 # sklearn's TSNE._EXPLORATION_MAX_ITER
@@ -31,31 +33,9 @@ TsneResult = namedtuple("TsneResult", ["embedding", "kl_divergence", "n_iter"])
 DomainMap = namedtuple("DomainMap", ["embedding", "labels", "silhouette", "kl_divergence", "n_iter"])
 
 
-def _gpu_matrix(x, who, name, cols=None):
-    if not isinstance(x, torch.Tensor) or not x.is_cuda:
-        raise BsedError(f"{who}: {name} must be a GPU tensor (there is no CPU path)")
-    if x.dtype != torch.float32 or x.dim() != 2 or (cols is not None and x.shape[1] != cols) or x.shape[1] < 1:
-        raise BsedError(f"{who}: {name} must be (N, {cols or 'D'}) float32, got {tuple(x.shape)} {x.dtype}")
-    if x.device.index != torch._C._cuda_getDevice():
-        raise BsedError(f"{who}: {name} lives on cuda:{x.device.index} but the current device is "
-                        f"cuda:{torch._C._cuda_getDevice()}: wrap the call in torch.cuda.device(...)")
-    if not 2 <= x.shape[0] <= TSNE_MAX_POINTS:
-        raise BsedError(f"{who}: 2 to {TSNE_MAX_POINTS} points, got {x.shape[0]}")
-    return x
-
-
 def affinity_bytes(n):
     """the bytes of the dense (n, n) float32 affinities"""
     return 4 * int(n) * int(n)
-
-
-def _check_fits(n, device, who):
-    free, _total = torch.cuda.mem_get_info(device)
-    free += torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)   # what torch's cache can hand out
-    need = affinity_bytes(n)
-    if need > free:
-        raise BsedError(f"{who}: the affinities of {n} points need {need} bytes of device memory, {free} are free; "
-                        "there is no host fallback: draw fewer points (max_points)")
 
 
 def tsne_affinities_gpu(x, perplexity=30.0):
@@ -64,21 +44,19 @@ def tsne_affinities_gpu(x, perplexity=30.0):
     float64 = that sum, ``beta`` (N) float32 = the precision sklearn's perplexity search ends at for each row.  Four HIP
     launches, no host sync; the definitions are include/bsed.h's (``bsed_tsne_affinities``)."""
     who = "tsne_affinities_gpu"
-    x = _gpu_matrix(x, who, "x")
+    x, pitch = gpu_points(x, who, 2, TSNE_MAX_POINTS)
     N, D = x.shape
     perplexity = float(perplexity)
     if not 0.0 < perplexity < N:
         raise BsedError(f"{who}: the perplexity must lie in (0, N={N}), got {perplexity}")
-    if x.stride(1) != 1 or x.stride(0) < D:
-        x = x.contiguous()
-    _check_fits(N, x.device, who)
+    check_dense_fits(N, x.device, who, "affinities")
     lib = L.lib()
     ws_bytes = lib.bsed_tsne_affinities_workspace(N)
     ws = torch.empty(ws_bytes // 8, device=x.device, dtype=torch.float64)
     P = torch.empty((N, N), device=x.device, dtype=torch.float32)
     beta = torch.empty(N, device=x.device, dtype=torch.float32)
     sum_p = torch.empty(1, device=x.device, dtype=torch.float64)
-    L.call("bsed_tsne_affinities", ctypes.c_void_p(x.data_ptr()), x.stride(0), N, D, perplexity, L.ptr(P), L.ptr(beta),
+    L.call("bsed_tsne_affinities", ctypes.c_void_p(x.data_ptr()), pitch, N, D, perplexity, L.ptr(P), L.ptr(beta),
            L.ptr(sum_p, torch.float64), L.ptr(ws, torch.float64), ws_bytes, L.stream())
     return TsneAffinities(P, sum_p, beta)
 
@@ -89,7 +67,7 @@ class _Gradient:
     def __init__(self, aff, splits, who):
         if not isinstance(aff, TsneAffinities):
             raise BsedError(f"{who}: aff must be the TsneAffinities of tsne_affinities_gpu")
-        self.P = _gpu_matrix(aff.P, who, "aff.P")
+        self.P = gpu_matrix(aff.P, who, "aff.P", 2, TSNE_MAX_POINTS)
         self.N = self.P.shape[0]
         if self.P.shape[1] != self.N or not self.P.is_contiguous():
             raise BsedError(f"{who}: aff.P must be a contiguous (N, N) matrix, got {tuple(self.P.shape)}")
@@ -115,7 +93,7 @@ class _Gradient:
 
 
 def _map_tensor(y, n, who):
-    y = _gpu_matrix(y, who, "y", cols=2)
+    y = gpu_matrix(y, who, "y", 2, TSNE_MAX_POINTS, cols=2)
     if y.shape[0] != n:
         raise BsedError(f"{who}: y must be ({n}, 2), got {tuple(y.shape)}")
     return y.contiguous()
@@ -231,7 +209,7 @@ def tsne(x, perplexity=30.0, early_exaggeration=12.0, learning_rate="auto", max_
     one of the gradient times the gains.  ``kl_divergence`` is the divergence of the RETURNED map (one more evaluation;
     sklearn's ``kl_divergence_`` is the one of the map before its last step), ``n_iter`` sklearn's ``n_iter_``."""
     who = "tsne"
-    x = _gpu_matrix(x, who, "x")
+    x = gpu_matrix(x, who, "x", 2, TSNE_MAX_POINTS)        # checked before the init is made; the affinities take any pitch
     N = x.shape[0]
     y = _initial_map(x, init, seed, who)
     if learning_rate == "auto":
@@ -272,14 +250,10 @@ def domain_map(synth, real, **tsne_kw):
     tensor, the ``tsne`` map of the two sets together (synth first), ``labels`` (0 = synth, 1 = real, int64 numpy),
     ``silhouette`` = ``domain_gap``'s silhouette of the two domains taken ON THE MAP -- the number src/visualize.py
     prints --, ``kl_divergence`` and ``n_iter`` of the run."""
-    from . import domain_gap as DG
-    L._require_gpu()
-    s, r = (torch.as_tensor(v).float().cuda() for v in (synth, real))
-    if s.dim() != 2 or r.dim() != 2 or s.shape[1] != r.shape[1] or s.shape[0] < 1 or r.shape[0] < 1:
-        raise BsedError(f"domain_map: two non-empty (n, D) sets of the same D, got {tuple(s.shape)} and {tuple(r.shape)}")
-    res = tsne(torch.cat([s, r], dim=0).contiguous(), **tsne_kw)
-    labels = np.concatenate([np.zeros(s.shape[0], np.int64), np.ones(r.shape[0], np.int64)])
-    gap = DG.domain_gap(res.embedding[:s.shape[0]], res.embedding[s.shape[0]:])
+    x, ns, nr = two_domains(synth, real, "domain_map")
+    res = tsne(x, **tsne_kw)
+    labels = np.concatenate([np.zeros(ns, np.int64), np.ones(nr, np.int64)])
+    gap = DG.domain_gap(res.embedding[:ns], res.embedding[ns:])
     return DomainMap(res.embedding, labels, gap.silhouette, res.kl_divergence, res.n_iter)
 
 
@@ -287,9 +261,7 @@ def domain_map_of(model, synth_loader, real_loader, predictor, fpn=False, level=
                   **tsne_kw):
     """``domain_map`` of the embeddings ``domain_gap.embed`` makes of the two loaders (the reference maps frames:
     ``level="frame"``, with ``max_points`` drawn per domain -- it samples 1000 of each)"""
-    from . import domain_gap as DG
-    synth = DG.embed(model, synth_loader, predictor, fpn, level, max_points, seed)
-    real = DG.embed(model, real_loader, predictor, fpn, level, max_points, seed)
+    synth, real = embed_two(model, synth_loader, real_loader, predictor, fpn, level, max_points, seed)
     return domain_map(synth, real, seed=seed, **tsne_kw)
 
 

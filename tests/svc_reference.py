@@ -6,6 +6,8 @@ sklearn's ``SVC`` and ``cross_val_score``; tests/test_svc_gpu.py compares the ke
 values."""
 import numpy as np
 
+from d2_reference import d2_matrix  # noqa: F401  (the tests read it as R.d2_matrix)
+
 TAU = 1e-12
 CONVERGED, NOT_CONVERGED = 0, 1
 
@@ -61,16 +63,6 @@ def solver_case(name):
             X[other[2]] = X[other[1]]
         test = np.arange(N)
     return dict(x=X, y=y, train=train, test=test, C=C, gamma=np.float32(scale_gamma(X[train])))
-
-
-def d2_matrix(x):
-    """(N, D) float32 -> (N, N) float64 squared distances by direct differences"""
-    x = np.asarray(x, np.float32).astype(np.float64)
-    out = np.empty((x.shape[0], x.shape[0]))
-    for i in range(x.shape[0]):
-        diff = x - x[i]
-        out[i] = np.einsum("nd,nd->n", diff, diff)
-    return out
 
 
 def kernel_matrix(d2_32, gamma):

@@ -332,3 +332,54 @@ def test_domain_gap_of_a_model_equals_domain_gap_of_its_features():
     assert torch.equal(some, feats[0].reshape(4 * Tp, F)[keep.cuda()])
     assert torch.equal(some, DG.embed(crnn, synth, pred, level="frame", max_points=10, seed=3))
     assert crnn.training and pred.training
+
+
+def _svc_d2(xg):
+    """bsed_svc_d2 of a placed point matrix into a canary-guarded buffer -> (N, N) float32 numpy"""
+    from bsed_amd import _lib as L
+    N, D = xg.shape
+    buf, out = _guarded(N * N, torch.float32)
+    rc = L.lib().bsed_svc_d2(ctypes.c_void_p(xg.data_ptr()), xg.stride(0), N, D, ctypes.c_void_p(out.data_ptr()), L.stream())
+    assert rc == 0, L.lib().bsed_last_error().decode()
+    torch.cuda.synchronize()
+    assert _intact(buf, N * N), "d2: written outside its N * N elements"
+    return out.cpu().numpy().reshape(N, N).copy()
+
+
+SHARED_CORE_D = (1, 3, 32, 33, 37, 100)
+
+
+@pytest.mark.parametrize("misaligned", [False, True], ids=["aligned", "misaligned"])
+@pytest.mark.parametrize("N", [63, 64, 65, 130])
+def test_the_shared_tile_core_gives_pair_stats_and_svc_d2_the_same_bits(N, misaligned):
+    """pair_stats_kernel and d2_tile_kernel run one device function (csrc/d2_tile.h: d2_tile_acc), so the nearest
+    neighbour that bsed_pair_stats reports is, bit for bit, the smallest off-diagonal entry of the row of bsed_svc_d2,
+    at the smallest column that holds it.  Seeded normal points with one duplicated row (an exact 0 and a tie), every
+    label 0 (G = 1, S = 0); N around one tile and three tiles with a tail of two rows; D = 1, below a load of four, a
+    whole chunk, one and five past it (a second chunk that is almost all zero fill), four chunks with a tail of four;
+    both load paths; the automatic split, one split and three (more splits than column tiles at N <= 128)."""
+    for D in SHARED_CORE_D:
+        rng = np.random.default_rng(1000 * N + D)
+        x = rng.standard_normal((N, D)).astype(np.float32)
+        x[N - 1] = x[0]
+        d2 = _svc_d2(_place(x, misaligned))
+        assert np.array_equal(d2, d2.T) and (np.diag(d2) == 0).all() and d2[0, N - 1] == 0
+        off = d2.copy()
+        np.fill_diagonal(off, np.inf)
+        want_j = off.argmin(axis=1)                                   # the first, so the smallest, column of the minimum
+        want_d2 = off[np.arange(N), want_j]
+        for splits in (0, 1, 3):
+            got = launch(x, np.zeros(N, np.int32), 1, np.zeros(0, np.float32), splits, misaligned)
+            assert np.array_equal(got["nn_d2"].view(np.uint32), want_d2.view(np.uint32)), (D, splits)
+            assert np.array_equal(got["nn_index"], want_j), (D, splits)
+
+
+def test_the_shared_tile_core_with_one_point():
+    """N = 1: the only entry of d2 is the diagonal's exact 0, and the point has no neighbour: inf / -1"""
+    for D in SHARED_CORE_D:
+        x = np.random.default_rng(D).standard_normal((1, D)).astype(np.float32)
+        for misaligned in (False, True):
+            assert _svc_d2(_place(x, misaligned)).tolist() == [[0.0]]
+            for splits in (0, 1, 3):
+                got = launch(x, np.zeros(1, np.int32), 1, np.zeros(0, np.float32), splits, misaligned)
+                assert got["nn_d2"].tolist() == [np.inf] and got["nn_index"].tolist() == [-1], (D, misaligned, splits)
